@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """Headline benchmark (BASELINE.json): NLML+gradient evaluations/sec at N=16384, D=8, RBF + white noise, fp64.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps and K timed steps, writes the last timed step's outputs if --dump-outputs is
+given, and prints the headline line (metric, value, unit, higher_is_better, dtype, ms_per_step, config, build).
+Everything else below -- per-rank records, roofline, nlml_check, the secondary legs and the CPU baselines -- runs only
+with --full.
+
+--dump-outputs DIR writes what the timed path returned in its last step, `loss_and_grad(hp)`, as DIR/nlml.npy (float64
+scalar: NLML summed over ranks) and DIR/grad.npy (float64 [nhp]); inputs are fixed by seeds, so two builds can be
+compared output for output.
 
 N > 1 from a bare shell: bench.py starts its own N ranks (a child `python -m torch.distributed.run`, spawned before
 anything touches the GPU) and relays rank 0's JSON line; under a launcher that already set WORLD_SIZE (the driver's
@@ -12,7 +21,7 @@ build, Cholesky, L^-1, alpha, K^-1, fused gradient contraction at n = 16384, d =
 the shared-hyper-parameter all-reduce(sum) of [1 + nhp (+ status)] doubles over RCCL (grBCM co-training, GRBCM_MLE).
 At N = 1 that is exactly one exact-GP NLML+grad evaluation.  value = N * K / t (weak scaling, whole job).
 
-Extra objects on the same JSON line:
+Extra objects on the same JSON line (--full only):
   roofline      the MFMA GEMM core (all instantiations of pg_gemm_kernel) over one evaluation: algorithmic
                 flop of its launches / summed launch durations measured with HIP events inside the library
                 (pg_profile; single-stream profile mode), against the fp64 matrix peak; `frac_end_to_end` is
@@ -252,7 +261,13 @@ def main():
     ap.add_argument("--no-legs", action="store_true", help="headline + roofline only")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="start the ranks, run the collectives of the `dist` object and print it; no GPU work (launch self-test)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: per-rank records, roofline, nlml_check, secondary legs, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's NLML and gradient as DIR/nlml.npy and DIR/grad.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -386,17 +401,22 @@ def main():
     elapsed = time.perf_counter() - t0
     elapsed = max_over_ranks(elapsed)
     value = world * args.steps / elapsed
-    # every rank alone, no collective: what tells a slow box or a rank on the classic chain from the others
-    alone = pg.MLE(model.gpl)
-    alone.memoize = False
-    alone.loss_and_grad(hp[None, :].copy())
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(3):
+    if args.dump_outputs and rank == 0:       # the all-reduced NLML and gradient: the same on every rank
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "nlml.npy"), np.asarray(val, dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "grad.npy"), np.asarray(grad, dtype=np.float64))
+    if args.full:
+        # every rank alone, no collective: what tells a slow box or a rank on the classic chain from the others
+        alone = pg.MLE(model.gpl)
+        alone.memoize = False
         alone.loss_and_grad(hp[None, :].copy())
-    torch.cuda.synchronize()
-    ms_alone = 1e3 * (time.perf_counter() - t1) / 3
-    del alone
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(3):
+            alone.loss_and_grad(hp[None, :].copy())
+        torch.cuda.synchronize()
+        ms_alone = 1e3 * (time.perf_counter() - t1) / 3
+        del alone
 
     out = {
         "metric": "NLML+grad evals/sec at N=%d D=%d RBF" % (n, d), "value": value, "unit": "evals/s",
@@ -412,14 +432,15 @@ def main():
         "build": _lib.build_id(),
     }
 
-    mine = {"rank": rank, "device_index": dev_index, "device_name": torch.cuda.get_device_name(dev_index),
-            "ms_per_step": 1e3 * elapsed_local / args.steps, "ms_per_eval_alone": ms_alone, "coupled_chain": ops.coupled_chain(),
-            "coupled_panels_last_potrf": ops.last_coupled_panels(), "chain_timeouts": ops.chain_timeouts(),
-            "fallbacks": int(getattr(ops, "fallbacks", 0)), "chain_rearms": ops.chain_rearms()}
-    out["dist"] = dist_report(1 + (d + 2) + world, mine)      # [NLML, gradient (nhp = d + 2), one status word per rank]
+    if args.full:
+        mine = {"rank": rank, "device_index": dev_index, "device_name": torch.cuda.get_device_name(dev_index),
+                "ms_per_step": 1e3 * elapsed_local / args.steps, "ms_per_eval_alone": ms_alone, "coupled_chain": ops.coupled_chain(),
+                "coupled_panels_last_potrf": ops.last_coupled_panels(), "chain_timeouts": ops.chain_timeouts(),
+                "fallbacks": int(getattr(ops, "fallbacks", 0)), "chain_rearms": ops.chain_rearms()}
+        out["dist"] = dist_report(1 + (d + 2) + world, mine)      # [NLML, gradient (nhp = d + 2), one status word per rank]
 
     local = exp = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel: one profiled evaluation (events around every GEMM launch)
         local = pg.MLE(model.gpl)            # rank-local evaluation: no collective inside a rank-0-only section
         local.memoize = False
@@ -481,7 +502,7 @@ def main():
                                  "grad_inf": float(np.abs(g0).max())}
             assert rel < NLML_RTOL, "NLML at the published size moved: %r" % (out["nlml_check"],)
 
-    legs = rank == 0 and world == 1 and not args.no_legs
+    legs = args.full and rank == 0 and world == 1 and not args.no_legs
     if legs:
         # potrf alone and the covariance build, HIP events on torch's current stream (the library's caller stream)
         exp = model.gpl._device_data()[0]
@@ -672,7 +693,7 @@ def main():
     # ---- secondary metric: grBCM committee prediction throughput (BASELINE config 4)
     del model, loss, local, exp
     torch.cuda.empty_cache()
-    if not args.no_grbcm and not args.no_legs:
+    if args.full and not args.no_grbcm and not args.no_legs:
         nc, nls4, ng4, d4, m4, mb = 8, 8192, 1024, 16, 65536, 8192
         xg4, yg4 = synth_expert(ng4, d4, 7)
         sh = [synth_expert(nls4, d4, 100 + c) for c in range(nc)]
@@ -993,7 +1014,7 @@ def main():
 
     # ---- BASELINE config 5 in its stated layout (world > 1): ONE fp32 Matern-5/2 expert of 1024 + 32768 points per GPU, shared-hp
     # co-training objective, one all-reduce of [1 + nhp] + world status words per evaluation (GRBCM_MLE).  1 warm-up + 3 evaluations.
-    if world > 1 and not args.no_legs:
+    if args.full and world > 1 and not args.no_legs:
         torch.cuda.empty_cache()
         nls5, ng5, d5 = 32768, 1024, 16
         rng = np.random.default_rng(1234)

@@ -141,3 +141,14 @@ def test_bench_starts_its_own_ranks(tmp_path):
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
     rep = json.loads(line)["dist"]
     assert rep["world"] == 2 and rep["ranks"] == [0, 1] and rep["backend"] == "gloo" and rep["allreduce_us"] > 0
+
+
+def test_bench_options():
+    """bench.py offers --full and --dump-outputs, and refuses a run without timed steps before it starts any work."""
+    import subprocess
+
+    bench = os.path.join(os.path.dirname(HERE), "bench.py")
+    r = subprocess.run([sys.executable, bench, "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout, r.stderr[-2000:]
+    r = subprocess.run([sys.executable, bench, "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr, r.stderr[-2000:]
