@@ -86,8 +86,7 @@ int pg_kernel_grad_build(pg_handle h, int dtype, const pg_covspec* spec, const d
  * workspace of pg_potrf_worksize(dtype, n) elements: its first n * 128 elements receive the inverses of the 128x128
  * diagonal blocks ([n/128][128][128]) that drive every later solve (pg_potrs_vec, pg_trtri ... only read that part);
  * the rest (n + 2048 elements) is scratch of the call: the flag words through which the resident kernels of the coupled
- * chain hand over (csrc/chainstep.hip; zeroed by every call); with PG_PANEL_MODE=1 in the environment (experimental recursive
- * panel step) its buffers follow.
+ * chain hand over (csrc/chainstep.hip; zeroed by every call).
  * info: 0, or j + 1 when the leading minor of order j + 1 is not positive definite (LAPACK's convention), or -1 when a bounded
  * wait inside the coupled chain expired: NOT a property of the matrix -- kernels of the handle's panel and rows streams did not run
  * at the same time (seen while developing: under `rocprofv3 --pmc`, which runs one kernel at a time, before pg_create probed for
@@ -334,15 +333,9 @@ int pg_spin_probe(pg_handle h, int n, void* scratch, void* stream);
  * the coupled chain needs the look-ahead schedule, i.e. at least three outer panels; any caller stream works, the legacy
  * default stream included) -- tests / diagnostics */
 int pg_last_coupled_panels(pg_handle h);
-/* Experimental schedule of the coupled factorisation (part of tc.cholesky, gpr.py:69 / loss.py:97; OFF by default, PG_DEFER=1 in the
- * environment switches it on for new handles): from n = 6144 the columns right of about n / 2 take the leading half's updates as deferred
- * K = n/2-deep products beside the trailing half's chain instead of panel by panel.  Same factor to rounding; measured 3 % slower at
- * n = 8192.  pg_last_deferred_panels: how many column panels of the handle's LAST factorisation were deferred. */
-int pg_set_deferred_block(pg_handle h, int on);
-int pg_last_deferred_panels(pg_handle h);
 
-/* one 128x128 Cholesky leaf (factor + inverse) on its own; ablate != 0 skips phases -- timing diagnostics only */
-int pg_leaf_raw(pg_handle h, int dtype, void* A, long lda, void* inv, long ldi, int* info, int ablate, void* stream);
+/* one 128x128 Cholesky leaf (factor + inverse) on its own -- timing diagnostics */
+int pg_leaf_raw(pg_handle h, int dtype, void* A, long lda, void* inv, long ldi, int* info, void* stream);
 
 /* one rows kernel of the flag-coupled chain (chainstep.hip) on its own, every flag it would wait for preset: rows below tile
  * (k0, k0) of an n x n matrix, window from column o0, inv = a 128 x 128 lower-triangular block; flags: 8 ints of scratch --

@@ -530,16 +530,10 @@ class HipOps:
     def last_coupled_panels(self):
         return int(self.lib.pg_last_coupled_panels(self.h))
 
-    def set_deferred_block(self, on):
-        _lib.check(self.lib.pg_set_deferred_block(self.h, int(on)), "pg_set_deferred_block")
-
-    def last_deferred_panels(self):
-        return int(self.lib.pg_last_deferred_panels(self.h))
-
-    def leaf_raw(self, a, inv, info, ablate=0):
+    def leaf_raw(self, a, inv, info):
         self._chk(a, inv, info)
         _lib.check(self.lib.pg_leaf_raw(self.h, _code(a.dtype), _p(a), a.stride(0), _p(inv), inv.stride(0) if inv is not None else 0,
-                                        _p(info), int(ablate), self._st()), "pg_leaf_raw")
+                                        _p(info), self._st()), "pg_leaf_raw")
 
     def profile(self, on):
         _lib.check(self.lib.pg_profile(self.h, int(on)), "pg_profile")

@@ -26,7 +26,6 @@ static void release_ctx(pg_ctx* h) {
     (void)hipStreamDestroy(h->aux);
     if (h->rows) (void)hipStreamDestroy(h->rows);
     if (h->upd) (void)hipStreamDestroy(h->upd);
-    if (h->bg) (void)hipStreamDestroy(h->bg);
     for (int i = 0; i < 8; ++i) (void)hipEventDestroy(h->ev[i]);
     for (int i = 0; i < h->npool; ++i) (void)hipEventDestroy(h->pool[i]);
     free(h->pool);
@@ -136,11 +135,10 @@ static int gemm_raw_t(pg_handle h, int variant, int M, int N, int K, double alph
     p.sA = p.sB = p.sC = 0; p.batch = 1;
     p.nexp = 1; p.eA = p.eB = p.eC = 0; p.einfo = 0;
     p.part = nullptr; p.ldp = 0; p.info = nullptr; p.noxcd = 0;
-    // PG_RAW_STREAM=upd|bg (measurement only): run the product on one of the handle's CU-masked streams instead
+    // PG_RAW_STREAM=upd (measurement only): run the product on the handle's CU-masked update stream instead
     static const char* rs = getenv("PG_RAW_STREAM");
     hipStream_t on = ST(stream);
     if (rs && rs[0] == 'u' && h->upd) on = h->upd;
-    if (rs && rs[0] == 'b' && h->bg) on = h->bg;
     if (on == ST(stream)) return pg_gemm<T>(h, on, variant, p);
     PG_CHECK(hipEventRecord(h->ev[2], ST(stream)));      // (ev[4] / ev[5] belong to pg_alpha_nlml_async's side-stream fork)
     PG_CHECK(hipStreamWaitEvent(on, h->ev[2], 0));
@@ -245,7 +243,6 @@ int pg_create(pg_handle* h) {
     PG_CHECK(hipStreamCreateWithPriority(&c->aux, hipStreamNonBlocking, prio_hi));
     c->rows = nullptr;
     c->last_coupled = 0;
-    c->defer = getenv("PG_DEFER") ? atoi(getenv("PG_DEFER")) : 0;
     c->lookahead = 1;
     {
         const char* e = getenv("PG_NBO");
@@ -254,8 +251,6 @@ int pg_create(pg_handle* h) {
         const char* r = getenv("PG_REC_MIN");
         c->rec_min = r ? atoi(r) : 16384;
         if (c->rec_min < 0 || (c->rec_min > 0 && (c->rec_min < 512 || c->rec_min % 512))) c->rec_min = 16384;
-        const char* v = getenv("PG_PANEL_MODE");
-        c->panel_mode = v ? atoi(v) : 0;
     }
     {   // update stream on all but the last PG_RESERVED_CUS compute units; without it look-ahead stays off
         hipDeviceProp_t prop;
@@ -277,28 +272,11 @@ int pg_create(pg_handle* h) {
             c->lookahead = 0;
             (void)hipGetLastError();
         }
-        // The background stream of the fused factor-and-invert call (PG_BG_STREAM=1, replaces the rows stream) is an experiment:
-        // its overlap returned 0.5 ms of 8.7 at n = 8192 and nothing at 16384, and a handle with TWO CU-masked streams is
-        // fragile -- any fifth hardware queue in the process (a second stream of the caller's is enough) then costs the
-        // look-ahead 20-60 %, which the current panel / rows / update set does not show with up to seven queues.
-        c->bg = nullptr;
-        const char* envbg = getenv("PG_BG_STREAM");
-        if (envbg && atoi(envbg)) {
-            const char* envb = getenv("PG_BG_CUS");
-            int bgcus = envb ? atoi(envb) : PG_BG_CUS;
-            if (bgcus < 8 || bgcus > ncu - reserved) bgcus = ncu - reserved;
-            for (int i = 0; i < 64; ++i) mask[i] = 0;
-            for (int cu = 0; cu < bgcus; ++cu) mask[cu / 32] |= (1u << (cu % 32));
-            if (c->upd && hipExtStreamCreateWithCUMask(&c->bg, (uint32_t)words, mask) != hipSuccess) {
-                c->bg = nullptr;
-                (void)hipGetLastError();
-            }
-        }
     }
     {   // rows stream of the flag-coupled chain (chainstep.hip): non-blocking, same priority as the panel stream
         const char* envr = getenv("PG_ROWS_STREAM");
         c->rows = nullptr;
-        if (!(envr && !atoi(envr)) && !c->bg && c->upd &&
+        if (!(envr && !atoi(envr)) && c->upd &&
             hipStreamCreateWithPriority(&c->rows, hipStreamNonBlocking, prio_hi) != hipSuccess) {
             c->rows = nullptr;
             (void)hipGetLastError();
@@ -859,7 +837,7 @@ int pg_set_coupled_chain(pg_handle h, int on) {
         h->coupled = 0;
         return 0;
     }
-    if (!h->rows && h->upd && !h->bg) {
+    if (!h->rows && h->upd) {
         int prio_lo = 0, prio_hi = 0;
         PG_CHECK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
         if (hipStreamCreateWithPriority(&h->rows, hipStreamNonBlocking, prio_hi) != hipSuccess) {
@@ -874,15 +852,6 @@ int pg_coupled_chain(pg_handle h) { return h ? h->coupled : -1; }
 int pg_last_coupled_panels(pg_handle h) {
     if (!h) return -1;
     return h->last_coupled;
-}
-int pg_set_deferred_block(pg_handle h, int on) {
-    NEED(h, "null handle");
-    h->defer = on ? 1 : 0;
-    return 0;
-}
-int pg_last_deferred_panels(pg_handle h) {
-    if (!h) return -1;
-    return h->last_deferred;
 }
 int pg_profile_read(pg_handle h, double* flops, double* ms, long* launches) {
     NEED(h, "null handle");
@@ -946,11 +915,11 @@ int pg_build_potrf_trtri_checked(pg_handle h, int dtype, const pg_covspec* spec,
     return 0;
 }
 
-int pg_leaf_raw(pg_handle h, int dtype, void* A, long lda, void* inv, long ldi, int* info, int ablate, void* stream) {
+int pg_leaf_raw(pg_handle h, int dtype, void* A, long lda, void* inv, long ldi, int* info, void* stream) {
     JOIN(h, stream);
     NEED(h && A && info, "null pointer");
-    DISPATCH(dtype, pg_leaf<double>(ST(stream), (double*)A, lda, (double*)inv, ldi, info, 0, ablate),
-             pg_leaf<float>(ST(stream), (float*)A, lda, (float*)inv, ldi, info, 0, ablate));
+    DISPATCH(dtype, pg_leaf<double>(ST(stream), (double*)A, lda, (double*)inv, ldi, info, 0),
+             pg_leaf<float>(ST(stream), (float*)A, lda, (float*)inv, ldi, info, 0));
 }
 
 int pg_rowstep_raw(pg_handle h, int dtype, int n, void* A, long lda, int o0, int k0, const void* inv, int* flags, int* info, void* stream) {

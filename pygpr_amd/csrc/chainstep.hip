@@ -397,6 +397,7 @@ __global__ __launch_bounds__(CS_NTH, 4) void pg_rowstep_kernel(T* __restrict__ A
 
 __global__ void pg_flagset_kernel(int* flag, int value, long eF) { __hip_atomic_store(flag + blockIdx.x * eF, value, RLX_AGENT); }
 
+#define ROWS16_MAX 4096
 template <typename T>
 int pg_rowstep(hipStream_t st, T* A, long lda, int n, int o0, int k0, int has_next, const T* inv, int* done_k, int* brow_k,
                int* diag_next, const CsWait& tmo, int* info, int* early_k, int* browe_k, int allow_tlog, const CsBatch* cbp) {
@@ -410,15 +411,14 @@ int pg_rowstep(hipStream_t st, T* A, long lda, int n, int o0, int k0, int has_ne
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_done = true;
     }
-    static const int direct = getenv("PG_CS_K128") ? atoi(getenv("PG_CS_K128")) : 1;
-    static const int rows16_env = getenv("PG_CS_ROWS16") ? atoi(getenv("PG_CS_ROWS16")) : 4096;   // rows at or below which every workgroup takes 16 rows
-    static const int rows16_direct = getenv("PG_CS_ROWS16_DIRECT") ? atoi(getenv("PG_CS_ROWS16_DIRECT")) : 1;
-    const int rows16 = (rows16_env > 0 && m <= rows16_env) ? (rows16_direct ? 2 : 1) : 0;
+    // direct = 1: the K = 128 product against the leaf's inverse; rows16 = 2: at or below ROWS16_MAX rows every workgroup takes
+    // 16 rows, also with the direct product
+    const int rows16 = m <= ROWS16_MAX ? 2 : 0;
     hipLaunchKernelGGL(pg_rowstep_kernel<T>, dim3(8 + (m - NB) / (rows16 ? 16 : 32), cb.nexp), dim3(CS_NTH), lds, st, A, lda, o0, k0, has_next, inv, done_k,
-                       brow_k, diag_next, tmo, info, direct,
+                       brow_k, diag_next, tmo, info, 1,
                        // (the in-kernel time log lives behind the flag words of a factorisation's work buffer: never for a caller that
                        //  brings its own small flag array, pg_rowstep_raw)
-                       (allow_tlog && getenv("PG_CS_TLOG")) ? reinterpret_cast<long long*>(tmo.tmo) + 512 + 48 * (k0 / NB) : nullptr, direct ? early_k : nullptr,
+                       (allow_tlog && getenv("PG_CS_TLOG")) ? reinterpret_cast<long long*>(tmo.tmo) + 512 + 48 * (k0 / NB) : nullptr, early_k,
                        browe_k, rows16, cb);
     PG_CHECK(hipGetLastError());
     return 0;

@@ -7,7 +7,6 @@
 
 #define PG_TILE 128      // GEMM block tile and Cholesky leaf size
 #define PG_RESERVED_CUS 32   // default; PG_RESERVED_CUS in the environment overrides
-#define PG_BG_CUS 4096         // CUs the background stream may use, clamped to all non-reserved ones (measured best; PG_BG_CUS overrides)
 #define PG_PAD 256       // every matrix dimension handed to the O(n^3) kernels is a multiple of this
 
 
@@ -17,7 +16,6 @@ typedef float pg_f4 __attribute__((ext_vector_type(4)));
 struct pg_ctx {
     hipStream_t aux;          // look-ahead / panel stream (highest priority, non-blocking)
     hipStream_t rows;         // rows stream of the flag-coupled chain (chainstep.hip; highest priority, non-blocking)
-    hipStream_t bg;           // background stream (same CU mask as upd): L^-1 of the leading half during potrf's tail
     hipStream_t upd;          // trailing-update stream: CU mask leaves PG_RESERVED_CUS compute units to the panel chain
                               // (the 128x128 leaf needs a whole CU's LDS and starves beside a chip-filling SYRK)
     hipEvent_t ev[8];
@@ -29,9 +27,6 @@ struct pg_ctx {
     int coupled;              // the flag-coupled chain may be used (pg_set_coupled_chain; cleared by pg_create when kernels of the
                               // panel and rows streams do not run concurrently here, e.g. under a counter-collecting profiler)
     int last_coupled;         // panels the last factorisation ran on the flag-coupled chain (chainstep.hip); tests / diagnostics
-    int defer;                // deferred trailing block in the coupled factorisation (pg_set_deferred_block / PG_DEFER; default 0)
-    int last_deferred;        // column panels of the last factorisation whose updates by the first half came as deferred deep-K products (linalg.hip)
-    int panel_mode;           // how the rows below an outer panel ride its 128-column steps (linalg.hip, PG_PANEL_MODE)
     int side_pending;         // side-stream work (pg_alpha_nlml_async) that the next reader of its outputs must wait for: ev[5]
     hipStream_t side_owner;   // the caller stream that work was forked from: only a join on THAT stream clears side_pending
     int* tmo_host;            // pinned host word a timed-out wait of the coupled chain sets (chainstep.h); polled at every entry point

@@ -1,21 +1,11 @@
 // Cholesky leaf: factor one 128x128 diagonal block entirely in LDS (one workgroup) and produce
 // its inverse, which turns every triangular solve above it into an MFMA GEMM.
 //
-// Blocked right-looking with 16-wide micro-panels, software-pipelined; per micro-panel jb:
-//   A. wave 0 factors the 16x16 diagonal block in REGISTERS: lane r holds row r; per column the pivot and the
-//      multipliers are broadcast with v_readlane (1/sqrt by v_rsq + 2 Newton steps).  A non-positive / NaN pivot sets
-//      *info = global column + 1 (LAPACK convention, first failure wins) and stops.
-//      Meanwhile the other waves finish the trailing update of the PREVIOUS micro-panel (all tiles except its first
-//      tile column), which nothing in A or B depends on.
-//   B. panel solve  P <- P D^-T  by forward substitution, one thread per row (D broadcast from LDS)
-//   C. first tile column of the trailing update  T <- T - P P^T  (next diagonal block + next panel), MFMA
-// The inverse X = L^-1 is built inside the same loop by waves that would otherwise idle (block-row forward recurrence on
-// 16x16 tiles, X[p][q] = -D_p^-1 sum_{r=q}^{p-1} L[p][r] X[r][q] with X[q][q] = D_q^-1):
-//   - phase B of micro-panel jb (panel rows x D^-T, one thread per row) takes 16 more threads that run the same
-//     substitution on identity rows: that is Dinv[jb], at no extra time;
-//   - during phase A of micro-panel jb+1 the deferred-update work of waves 1-7 shrinks as jb grows while block row jb of X
-//     grows: they share one work list.  X[p][q] (p > q) lives in the upper tile (q, p) of S, which the factorisation never
-//     touches; after the loop only Dinv[7] and block row 7 are left.
+// Blocked right-looking with 16-wide micro-panels (the third form, leaf3_body below; rounds 1 and 2's forms are in DESIGN.md).
+// A non-positive / NaN pivot sets *info = global column + 1 (LAPACK convention, first failure wins).  The inverse X = L^-1 is built
+// inside the same loop by waves that would otherwise idle (block-row forward recurrence on 16x16 tiles,
+// X[p][q] = -D_p^-1 sum_{r=q}^{p-1} L[p][r] X[r][q] with X[q][q] = D_q^-1); X[p][q] (p > q) lives in the upper tile (q, p) of S,
+// which the factorisation never touches.
 // LDS: S[128][130] + 8 x [16][18] diagonal inverses, all in the dynamic region.
 #include "leaf.h"
 #include "chainstep.h"
@@ -221,415 +211,6 @@ __device__ __forceinline__ void inv_tile(T* S, const T* Dinv, int p, int q, int 
     for (int kk = 0; kk < 4; ++kk) acc = Mfma<T>::run(a[kk], b[kk], acc);
 #pragma unroll
     for (int r = 0; r < 4; ++r) Wt[Mfma<T>::row(lane, r) * LD + fr] = -acc[r];
-}
-
-// x <- x D^-T for one 16-long row x (forward substitution; D = factored 16x16 diagonal block in LDS, rd = reciprocals of
-// its diagonal).  Panel rows use it for P <- P D^-T; identity rows e_i give column i of D^-1.
-template <typename T>
-__device__ __forceinline__ void row_solve16(T (&x)[16], const T* D, const T* rd) {
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        T sacc = x[c];
-#pragma unroll
-        for (int k = 0; k < c; ++k) sacc -= x[k] * D[c * LD + k];
-        x[c] = sacc * rd[c];
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(NTH) void pg_leaf_kernel(T* __restrict__ A, long lda, T* __restrict__ inv, long ldi,
-                                                      int* __restrict__ info, int col0, int ablate, long eA, long eInv) {
-    A += blockIdx.x * eA;                     // batched experts: one workgroup each, one info word each
-    if (inv) inv += blockIdx.x * eInv;
-    info += blockIdx.x;
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    T* S = reinterpret_cast<T*>(smem_raw);
-    T* Dinv = S + NB * LD;                                  // [8][16][DLD]
-    int& fail = *reinterpret_cast<int*>(Dinv + 8 * 16 * DLD);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-
-    if (*info != 0) return;
-    if (tid == 0) fail = 0;
-    typedef T pair_t __attribute__((ext_vector_type(2)));
-    for (int idx = tid; idx < NB * NB / 2; idx += NTH) {       // two columns per thread, 64 pairs per row
-        const int i = idx >> 6, k = (idx & 63) * 2;
-        pair_t v = {(T)0, (T)0};
-        if (k <= i) {
-            v = *reinterpret_cast<const pair_t*>(A + (long)i * lda + k);
-            if (k + 1 > i) v[1] = (T)0;
-        }
-        *reinterpret_cast<pair_t*>(S + i * LD + k) = v;
-    }
-    __syncthreads();
-
-    T* Rd = Dinv + 8 * 16 * DLD + 2;   // [16] reciprocals of the current diagonal block's diagonal (behind the flag)
-    const bool want_inv = inv != nullptr && !(ablate & 2);   // ablate bit 1: no inverse
-    for (int jb = 0; jb < ((ablate & 1) ? 0 : NB / 16); ++jb) {   // ablate bit 0: skip the factorisation loop
-        const int c0 = jb * 16, r0 = c0 + 16;
-        if (wave == 0 && !(ablate & 8)) {   // bit 3: skip the diagonal step
-            // ---- A: factor the 16x16 diagonal block in registers of wave 0 (lane r = row r)
-            const int r = lane & 15;
-            T* D = S + c0 * LD + c0;
-            T row[16];
-#pragma unroll
-            for (int c = 0; c < 16; ++c) row[c] = D[r * LD + c];
-            bool ok = true;
-#pragma unroll
-            for (int c = 0; c < 16; ++c) {
-                const T piv = bcast_lane(row[c], c);
-                if (ok && !(piv > (T)0)) {   // wave-uniform
-                    ok = false;
-                    if (lane == 0) { fail = 1; atomicCAS(info, 0, col0 + c0 + c + 1); }
-                }
-                const T rs = ok ? inv_sqrt(piv) : (T)0;
-                const T lrc = row[c] * rs;           // lane c: sqrt(piv); lanes r < c: 0 (upper part is zero)
-                row[c] = lrc;
-                if (lane == c) Rd[c] = rs;
-#pragma unroll
-                for (int k = c + 1; k < 16; ++k) row[k] -= lrc * bcast_lane(lrc, k);
-            }
-            if (lane < 16) {
-#pragma unroll
-                for (int c = 0; c < 16; ++c) D[r * LD + c] = (c <= r) ? row[c] : (T)0;
-            }
-        } else if (wave > 0 && jb > 0) {
-            // ---- deferred part of the previous trailing update: tiles (ti, tj) with 1 <= tj <= ti; then block row
-            // jb - 1 of the inverse (its diagonal inverse was formed during the previous phase B)
-            const int pc0 = c0 - 16, pr0 = c0;           // previous panel's columns / first trailing row
-            const int pnt = (NB - pr0) / 16;
-            const int nrest = pnt * (pnt - 1) / 2;       // pairs (ti, tj): 1 <= tj <= ti <= pnt - 1
-            const int nx = want_inv ? jb - 1 : 0;        // tiles X[jb-1][q], q = 0 .. jb-2
-            for (int t = wave - 1; t < nrest + nx; t += NWV - 1) {
-                if (t < nrest) {
-                    int u = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-                    while (u * (u + 1) / 2 > t) --u;
-                    while ((u + 1) * (u + 2) / 2 <= t) ++u;
-                    const int ti = u + 1, tj = t - u * (u + 1) / 2 + 1;
-                    lds_tile_mm<T, true>(S + (pr0 + ti * 16) * LD + pr0 + tj * 16, LD, S + (pr0 + ti * 16) * LD + pc0, LD,
-                                         S + (pr0 + tj * 16) * LD + pc0, LD, 16, (T)-1, (T)1, lane);
-                } else {
-                    inv_tile<T>(S, Dinv, jb - 1, t - nrest, lane);
-                }
-            }
-        }
-        __syncthreads();
-        if (fail) return;
-        if (r0 >= NB) break;
-        const int nt = (NB - r0) / 16;   // 16-row tiles below the diagonal block
-        // ---- B: P <- P D^-T by forward substitution, one thread per row; D and 1/diag are broadcast reads from LDS
-        // the 16 threads after the panel rows run the same substitution on identity rows: row e_i D^-T = column i of D^-1
-        // (on wave 7, which has no panel rows -- NB - r0 <= 112 -- so the two kinds of row never share a wave and diverge)
-        if (tid < NB - r0) {
-            T* Prow = S + (r0 + tid) * LD + c0;
-            T x[16];
-#pragma unroll
-            for (int c = 0; c < 16; ++c) x[c] = Prow[c];
-            row_solve16<T>(x, S + c0 * LD + c0, Rd);
-#pragma unroll
-            for (int c = 0; c < 16; ++c) Prow[c] = x[c];
-        } else if (wave == NWV - 1 && lane < 16 && want_inv) {
-            T x[16];
-#pragma unroll
-            for (int c = 0; c < 16; ++c) x[c] = (c == lane) ? (T)1 : (T)0;
-            row_solve16<T>(x, S + c0 * LD + c0, Rd);
-            T* dst = Dinv + jb * 16 * DLD + lane;
-#pragma unroll
-            for (int c = 0; c < 16; ++c) dst[c * DLD] = x[c];
-        }
-        __syncthreads();
-        // ---- C (first tile column): next diagonal block and next panel, T <- T - P P^T
-        for (int t = wave; t < nt; t += NWV)
-            lds_tile_mm<T, true>(S + (r0 + t * 16) * LD + r0, LD, S + (r0 + t * 16) * LD + c0, LD, S + r0 * LD + c0, LD, 16,
-                                 (T)-1, (T)1, lane);
-        __syncthreads();
-    }
-
-    // L back to global (diagonal tiles of C above wrote the strictly upper 16x16 corners: mask them)
-    for (int idx = tid; idx < NB * NB / 2; idx += NTH) {
-        const int i = idx >> 6, k = (idx & 63) * 2;
-        pair_t v = *reinterpret_cast<const pair_t*>(S + i * LD + k);
-        if (k > i) v[0] = (T)0;
-        if (k + 1 > i) v[1] = (T)0;
-        *reinterpret_cast<pair_t*>(A + (long)i * lda + k) = v;
-    }
-    if (!want_inv) return;
-    // ---- block rows 0..6 of the inverse are final (last barrier of the loop): their stores go out first and overlap
-    // with what is left to compute, the last diagonal inverse and block row 7
-    auto store_inv_rows = [&](int row_lo, int row_hi) {
-        for (int idx = row_lo * 64 + tid; idx < row_hi * 64; idx += NTH) {
-            const int i = idx >> 6, k = (idx & 63) * 2;
-            const int pb = i >> 4, qb = k >> 4, ii = i & 15;
-            pair_t v = {(T)0, (T)0};
-            if (qb == pb) {
-                const T* Dv = Dinv + pb * 16 * DLD + ii * DLD + (k & 15);
-                v[0] = (k <= i) ? Dv[0] : (T)0;
-                v[1] = (k + 1 <= i) ? Dv[1] : (T)0;
-            } else if (qb < pb) {
-                const T* Xt = S + (16 * qb + ii) * LD + 16 * pb + (k & 15);   // X[pb][qb] lives in upper tile (qb, pb)
-                v[0] = Xt[0];
-                v[1] = Xt[1];
-            }
-            *reinterpret_cast<pair_t*>(inv + (long)i * ldi + k) = v;
-        }
-    };
-    store_inv_rows(0, 112);
-    if (tid < 16) {   // Rd still holds block 7's reciprocals
-        T x[16];
-#pragma unroll
-        for (int c = 0; c < 16; ++c) x[c] = (c == tid) ? (T)1 : (T)0;
-        row_solve16<T>(x, S + 112 * LD + 112, Rd);
-#pragma unroll
-        for (int c = 0; c < 16; ++c) Dinv[7 * 16 * DLD + c * DLD + tid] = x[c];
-    }
-    __syncthreads();
-    for (int q = wave; q < 7; q += NWV) inv_tile<T>(S, Dinv, 7, q, lane);
-    __syncthreads();
-    store_inv_rows(112, 128);
-}
-
-
-// ------------------------------------------------------------------------------------------------
-// Leaf, second form (default): the diagonal step and the panel solve are ONE register-resident tall-panel step.
-// Waves 0-2 each hold the 16 rows of the diagonal block in lanes 0-15 (redundantly) and 48 rows of the panel below it in
-// lanes 16-63; wave 3 holds the diagonal rows and 16 identity rows.  Per column c: the pivot and the multipliers l_kc come
-// from the diagonal lanes by v_readlane (wave-uniform SGPRs), so the same instructions that factor the diagonal block
-// perform the right-looking solve of the panel rows (and of the identity rows: D^-1) -- no LDS round trip and no barrier
-// between "A" and "B", no branches (a bad pivot is recorded with a compare/select and acted on after the 16 columns).
-// Waves 4-11 meanwhile run the deferred trailing update of the previous micro-panel and the inverse's block row, as before.
-// ------------------------------------------------------------------------------------------------
-template <typename T, bool WT>   // WT: tile and inverse move with write-through / L1-bypassing accesses (the coupled chain)
-__device__ __forceinline__ void leaf2_body(char* smem_raw, T* __restrict__ A, long lda, T* __restrict__ inv, long ldi,
-                                           int* __restrict__ info, int col0, int ablate, long long* tlog = nullptr) {
-#define LTL(i) do { if (tlog && threadIdx.x == 0) tlog[i] = wall_clock64(); } while (0)
-    const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(A, 0, (int)((127 * lda + 128) * sizeof(T)), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rI = __builtin_amdgcn_make_buffer_rsrc(inv, 0, inv ? (int)((127 * ldi + 128) * sizeof(T)) : 0, 0x00020000);
-    T* S = reinterpret_cast<T*>(smem_raw);
-    T* Dinv = S + NB * LD;                                  // [8][16][DLD]
-    int& fail = *reinterpret_cast<int*>(Dinv + 8 * 16 * DLD);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    constexpr int NAB = 4;                                  // waves of the tall-panel step (3 x 48 panel rows + identity rows)
-
-    if (*info != 0) return;
-    if (tid == 0) fail = 0;
-    typedef T pair_t __attribute__((ext_vector_type(2)));
-    // ablate bit 4: the round-2 data movement (whole tile loaded before the first step, L and the inverse stored after the last)
-    const bool prog = !(ablate & 16);
-    // Tile -> LDS in two sets, all loads issued up front.  Set A = columns 0-31 (what the first micro-panel's step and its first
-    // update column touch) goes to LDS at once; set B = the rest is written behind the first step's barrier, so that its load
-    // latency (and 3/4 of the tile's bytes) hides behind that step instead of in front of it.
-    constexpr int NA = (NB * 16 + NTH - 1) / NTH, NBS = (NB * 48 + NTH - 1) / NTH;
-    pair_t va[NA], vb[NBS];
-    auto tile_load = [&](int i, int k) -> pair_t {
-        pair_t v = pair_t{(T)0, (T)0};
-        if (k <= i) {
-            if (WT) v = ld_pair_wt(A, rA, (long)i * lda + k);
-            else v = *reinterpret_cast<const pair_t*>(A + (long)i * lda + k);
-        }
-        return v;
-    };
-#pragma unroll
-    for (int u = 0; u < NA; ++u) {
-        const int idx = tid + u * NTH, i = idx >> 4, k = (idx & 15) * 2;
-        va[u] = (idx < NB * 16) ? tile_load(i, k) : pair_t{(T)0, (T)0};
-    }
-#pragma unroll
-    for (int u = 0; u < NBS; ++u) {
-        const int idx = tid + u * NTH, i = idx / 48, k = (16 + idx % 48) * 2;
-        vb[u] = (idx < NB * 48) ? tile_load(i, k) : pair_t{(T)0, (T)0};
-    }
-#pragma unroll
-    for (int u = 0; u < NA; ++u) {
-        const int idx = tid + u * NTH, i = idx >> 4, k = (idx & 15) * 2;
-        if (k + 1 > i) va[u][1] = (T)0;
-        if (idx < NB * 16) *reinterpret_cast<pair_t*>(S + i * LD + k) = va[u];
-    }
-    auto set_b_to_lds = [&]() {
-#pragma unroll
-        for (int u = 0; u < NBS; ++u) {
-            const int idx = tid + u * NTH, i = idx / 48, k = (16 + idx % 48) * 2;
-            if (k + 1 > i) vb[u][1] = (T)0;
-            if (idx < NB * 48) *reinterpret_cast<pair_t*>(S + i * LD + k) = vb[u];
-        }
-    };
-    if (!prog || (ablate & 1)) set_b_to_lds();
-    __syncthreads();
-    LTL(16);
-
-    const bool want_inv = inv != nullptr && !(ablate & 2);
-    // 16 columns of L (all 128 rows: zeros above the diagonal block) -> global, by the threads t0, t0 + nth, ...
-    auto store_l_panel = [&](int jbp, int t0, int nth) {
-        const int cc0 = 16 * jbp;
-        for (int idx = t0; idx < NB * 8; idx += nth) {
-            const int i = idx >> 3, k = cc0 + (idx & 7) * 2;
-            pair_t v = {(T)0, (T)0};
-            if (i >= cc0) v = *reinterpret_cast<const pair_t*>(S + i * LD + k);
-            if (k > i) v[0] = (T)0;                                                // right of the diagonal inside the diagonal block
-            if (k + 1 > i) v[1] = (T)0;
-            if (WT) st_pair_wt(A, rA, (long)i * lda + k, v);
-            else *reinterpret_cast<pair_t*>(A + (long)i * lda + k) = v;
-        }
-    };
-    auto store_inv_rows = [&](int row_lo, int row_hi, int t0, int nth) {
-        for (int idx = row_lo * 64 + t0; idx < row_hi * 64; idx += nth) {
-            const int i = idx >> 6, k = (idx & 63) * 2;
-            const int pb = i >> 4, qb = k >> 4, ii = i & 15;
-            pair_t v = {(T)0, (T)0};
-            if (qb == pb) {
-                const T* Dv = Dinv + pb * 16 * DLD + ii * DLD + (k & 15);
-                v[0] = (k <= i) ? Dv[0] : (T)0;
-                v[1] = (k + 1 <= i) ? Dv[1] : (T)0;
-            } else if (qb < pb) {
-                const T* Xt = S + (16 * qb + ii) * LD + 16 * pb + (k & 15);
-                v[0] = Xt[0];
-                v[1] = Xt[1];
-            }
-            if (WT) st_pair_wt(inv, rI, (long)i * ldi + k, v);
-            else *reinterpret_cast<pair_t*>(inv + (long)i * ldi + k) = v;
-        }
-    };
-    constexpr int STW = 7;                                  // waves STW .. NWV-1 never have a tile of the first update column (nt <= 7)
-    for (int jb = 0; jb < ((ablate & 1) ? 0 : NB / 16); ++jb) {
-        const int c0 = jb * 16, r0 = c0 + 16;
-        if (wave < NAB) {
-            // ---- tall-panel step: lanes 0-15 = diagonal rows, lanes 16-63 = panel rows (waves 0-2) / identity rows (wave 3)
-            const int pl = lane - 16;                                   // panel slot of this lane
-            const int prow = r0 + 48 * wave + pl;                       // its row of S
-            const bool is_diag = lane < 16;
-            const bool is_panel = !is_diag && wave < 3 && prow < NB;
-            const bool is_ident = !is_diag && wave == 3 && pl < 16 && want_inv;
-            const T* src = S + (is_diag ? c0 + lane : (is_panel ? prow : c0)) * LD + c0;
-            T row[16];
-#pragma unroll
-            for (int c = 0; c < 16; ++c) {
-                const T v = src[c];
-                row[c] = (is_diag || is_panel) ? v : ((is_ident && c == pl) ? (T)1 : (T)0);
-            }
-            int first_bad = 16;
-            if (ablate & 32) {        // round 2's chain: 1 / sqrt(pivot) between two pivots
-#pragma unroll
-                for (int c = 0; c < 16; ++c) {
-                    const T piv = bcast_lane(row[c], c);                    // wave-uniform
-                    first_bad = (piv > (T)0) ? first_bad : min(first_bad, c);
-                    const T rs = inv_sqrt(piv);
-                    const T lrc = row[c] * rs;
-                    row[c] = lrc;
-#pragma unroll
-                    for (int k = c + 1; k < 16; ++k) row[k] -= lrc * bcast_lane(lrc, k);
-                }
-            } else {
-                // Square-root-free chain (L D L^T inside the micro-panel): between two pivots lie 1 / pivot (hardware seed + two
-                // Newton steps: four dependent operations against the seven of 1 / sqrt), one multiply and one update; the sixteen
-                // square roots follow afterwards, off the chain, as independent instruction streams.  Same numbers to rounding
-                // (tools/micro/tallstep.hip: 4.4e-16 against a long-double Cholesky for both forms; 1.44 -> 1.04 us per step).
-                //   u_rc = a_rc - sum_{j<c} u_rj u_cj / d_j,  d_c = u_cc,  L_rc = u_rc / sqrt(d_c)
-                T piv[16];
-#pragma unroll
-                for (int c = 0; c < 16; ++c) {
-                    piv[c] = bcast_lane(row[c], c);                         // wave-uniform
-                    first_bad = (piv[c] > (T)0) ? first_bad : min(first_bad, c);
-                    const T w = row[c] * recip(piv[c]);
-#pragma unroll
-                    for (int k = c + 1; k < 16; ++k) row[k] -= row[c] * bcast_lane(w, k);
-                }
-#pragma unroll
-                for (int c = 0; c < 16; ++c) row[c] *= inv_sqrt(piv[c]);
-            }
-            if (first_bad < 16) {                                        // wave-uniform (piv is)
-                if (wave == 0 && lane == 0) { fail = 1; atomicCAS(info, 0, col0 + c0 + first_bad + 1); }
-            } else {
-                // every lane that holds a real row writes it back whole: the four waves' copies of the diagonal rows are the same
-                // bits (same instructions on the same data), and what a diagonal row carries right of the diagonal is masked
-                // where L leaves the workgroup (nothing in LDS reads it) -- one store block instead of one per kind of lane
-                if (is_diag || is_panel) {
-                    T* P = S + (is_diag ? c0 + lane : prow) * LD + c0;
-#pragma unroll
-                    for (int c = 0; c < 16; ++c) P[c] = row[c];
-                } else if (is_ident) {
-                    T* dst = Dinv + jb * 16 * DLD + pl;                  // column pl of D^-1
-#pragma unroll
-                    for (int c = 0; c < 16; ++c) dst[c * DLD] = row[c];
-                }
-            }
-        } else if (jb > 0) {
-            // ---- deferred part of the previous trailing update: tiles (ti, tj) with 1 <= tj <= ti; then block row
-            // jb - 1 of the inverse (its diagonal inverse was formed by wave 3 in the previous step)
-            const int pc0 = c0 - 16, pr0 = c0;
-            const int pnt = (NB - pr0) / 16;
-            const int nrest = pnt * (pnt - 1) / 2;
-            const int nx = want_inv ? jb - 1 : 0;
-            // last step: the wave that finishes X[6][q] goes on to the sum of X[7][q] (rows 0-6 of X and block row 7 of L
-            // are final; only the last diagonal inverse, formed by wave 3 right now, is missing)
-            const bool last = want_inv && jb == NB / 16 - 1;
-            for (int t = wave - NAB; t < nrest + nx + (last ? 1 : 0); t += NWV - NAB) {
-                if (last && t == nrest + nx) {
-                    inv_tile_sum<T>(S, Dinv, jb, jb - 1, lane);          // q = 6: L[7][6] Dinv[6]
-                    continue;
-                }
-                if (t < nrest) {
-                    int u = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-                    while (u * (u + 1) / 2 > t) --u;
-                    while ((u + 1) * (u + 2) / 2 <= t) ++u;
-                    const int ti = u + 1, tj = t - u * (u + 1) / 2 + 1;
-                    lds_tile_mm<T, true>(S + (pr0 + ti * 16) * LD + pr0 + tj * 16, LD, S + (pr0 + ti * 16) * LD + pc0, LD,
-                                         S + (pr0 + tj * 16) * LD + pc0, LD, 16, (T)-1, (T)1, lane);
-                } else {
-                    inv_tile<T>(S, Dinv, jb - 1, t - nrest, lane);
-                    if (last) inv_tile_sum<T>(S, Dinv, jb, t - nrest, lane);
-                }
-            }
-            // ---- then, still beside the tall-panel step (the longer half of this phase), these waves send out what the PREVIOUS
-            // step made final: its 16 columns of L and block row jb - 2 of the inverse.  Nothing reads or writes those again
-            // except the reads of later updates, so after the last step only that step's own columns and two block rows of the
-            // inverse are left to store.  (Stores placed in the short update phase behind the barrier stretched every step.)
-            if (prog) {
-                store_l_panel(jb - 1, tid - 64 * NAB, NTH - 64 * NAB);
-                if (want_inv && jb >= 2) store_inv_rows(16 * (jb - 2), 16 * (jb - 1), tid - 64 * NAB, NTH - 64 * NAB);
-            }
-        }
-        __syncthreads();
-        LTL(17 + 2 * jb);
-        if (fail) return;
-        if (prog && jb == 0) set_b_to_lds();     // columns 32-127: nothing has touched them yet; the next barrier publishes them
-        if (r0 >= NB) break;
-        const int nt = (NB - r0) / 16;
-        // ---- first tile column of the trailing update: next diagonal block and next panel, T <- T - P P^T
-        for (int t = wave; t < nt; t += NWV)
-            lds_tile_mm<T, true>(S + (r0 + t * 16) * LD + r0, LD, S + (r0 + t * 16) * LD + c0, LD, S + r0 * LD + c0, LD, 16,
-                                 (T)-1, (T)1, lane);
-        __syncthreads();
-        LTL(18 + 2 * jb);
-    }
-
-    if (!prog || (ablate & 1)) {
-        for (int idx = tid; idx < NB * NB / 2; idx += NTH) {
-            const int i = idx >> 6, k = (idx & 63) * 2;
-            pair_t v = *reinterpret_cast<const pair_t*>(S + i * LD + k);
-            if (k > i) v[0] = (T)0;
-            if (k + 1 > i) v[1] = (T)0;
-            if (WT) st_pair_wt(A, rA, (long)i * lda + k, v);
-            else *reinterpret_cast<pair_t*>(A + (long)i * lda + k) = v;
-        }
-        if (!want_inv) return;
-        store_inv_rows(0, 112, tid, NTH);
-        if (ablate & 1) return;
-        for (int q = wave; q < 7; q += NWV) inv_tile_finish<T>(S, Dinv, 7, q, lane);   // sums and Dinv[7] are in place (last step)
-        __syncthreads();
-        store_inv_rows(112, 128, tid, NTH);
-        return;
-    }
-    // progressive form: the last step's columns of L, block row 6 of the inverse (final since the loop's last barrier) and, once
-    // its seven products are done, block row 7
-    if (want_inv && wave < 7) inv_tile_finish<T>(S, Dinv, 7, wave, lane);
-    if (wave >= STW) {
-        store_l_panel(NB / 16 - 1, tid - 64 * STW, NTH - 64 * STW);
-        if (want_inv) store_inv_rows(96, 112, tid - 64 * STW, NTH - 64 * STW);
-    }
-    (void)STW;
-    if (!want_inv) return;
-    __syncthreads();
-    LTL(34);
-    store_inv_rows(112, 128, tid, NTH);
-#undef LTL
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -903,7 +484,7 @@ __device__ __forceinline__ void leaf3_body(char* smem_raw, T* __restrict__ A, lo
         }
     };
     const int NF3 = nf3 & 15;                               // waves that run the factor's instructions (wave 0 for real)
-    // bit 4 (default; PG_LEAF3_ALONE=0 clears it): the waves that share wave 0's SIMD (4, 8: waves go round the four SIMDs) sit out the
+    // bit 4 (set by the launchers, LEAF3_NF): the waves that share wave 0's SIMD (4, 8: waves go round the four SIMDs) sit out the
     // slot beside the factor: their MFMA / LDS work took issue cycles from the pivot chain (a step 2.9 -> 2.2-2.7 us; n = 4096
     // 1.535 -> 1.475 ms, the nine remaining workers finish within the factor's time except in the last slot)
     const bool alone = (nf3 & 16) != 0;
@@ -915,9 +496,9 @@ __device__ __forceinline__ void leaf3_body(char* smem_raw, T* __restrict__ A, lo
         if (BLK && jb == 4) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the zero stores of block rows 0..3 are out before the early flag can be raised
         if (wave < ((BLK && sizeof(T) == 8) ? 1 : NF3)) {
             // ---- F: the diagonal block alone.  lanes 0-15: its rows; lanes 16-31: identity rows, which leave the loop as D^-1.
-            // (PG_LEAF3_NF = 2..4: waves 1 .. NF3-1 run the SAME instructions on the same data and store nothing -- an experiment on
+            // (nf3 & 15 = 2..4: waves 1 .. NF3-1 run the SAME instructions on the same data and store nothing -- an experiment on
             // whether company on the other SIMDs shares the instruction fetch of this 9 KB of straight-line code: it does not,
-            // the factor takes 5100-5400 clocks either way; default 1)
+            // the factor takes 5100-5400 clocks either way; the launchers pass 1)
             int first_bad;
             if constexpr (BLK && sizeof(T) == 8)
                 first_bad = leaf3_factor_blk((lds_f64*)(S + c0 * LD + c0), (lds_f64*)(Dinv + jb * 16 * DLD), (lds_f64*)(Dinv + 8 * 16 * DLD + 18), lane, true);
@@ -1001,7 +582,7 @@ __device__ __forceinline__ void leaf3_body(char* smem_raw, T* __restrict__ A, lo
                 for (int r = 0; r < 4; ++r) S[(r0 + fr) * LD + c0 + Mfma<T>::row(lane, r)] = x0[r];
             }
         } else if (worker) {
-            // (bit 6, PG_LEAF3_DIAG=1: timing diagnostic -- the slot's work starts only when the factor beside it has finished, so the
+            // (bit 6, never set by the launchers: timing diagnostic -- the slot's work starts only when the factor beside it has finished, so the
             // stamps give both durations without the other's interference)
             if (nf3 & 64) {
                 while (__hip_atomic_load(ecnt + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < jb + 2) __builtin_amdgcn_s_sleep(2);
@@ -1098,47 +679,6 @@ __device__ __forceinline__ void leaf3_body(char* smem_raw, T* __restrict__ A, lo
 #undef LTL
 }
 
-template <typename T>
-__global__ __launch_bounds__(NTH) void pg_leaf2_kernel(T* __restrict__ A, long lda, T* __restrict__ inv, long ldi,
-                                                       int* __restrict__ info, int col0, int ablate, long eA, long eInv) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    // batched experts: one workgroup each, one info word each
-    leaf2_body<T, false>(smem_raw, A + blockIdx.x * eA, lda, inv ? inv + blockIdx.x * eInv : nullptr, ldi, info + blockIdx.x, col0, ablate);
-}
-
-// The leaf of the flag-coupled chain (chainstep.hip): resident before its tile exists.  Waits until the `want` workgroups that
-// own the tile have published it (*ready; they store it write-through), loads it past this CU's L1, factors, stores L and the
-// inverse write-through, drains, and sets *done: no fence on either side (every handed-off byte is an sc1 store read by sc1
-// loads, or read behind the reader's own acquire).
-// *done is set on every path (bad pivot, earlier failure, timeout): the rows below wait for it.
-template <typename T, bool WT>
-__global__ __launch_bounds__(NTH) void pg_leaf2s_kernel(T* __restrict__ A, long lda, T* __restrict__ inv, int* __restrict__ info,
-                                                        int col0, int* ready, int want, int* done, CsWait tmo, long long* tlog, int ablate) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    if (tlog && threadIdx.x == 0) tlog[0] = wall_clock64();
-    if (threadIdx.x == 0) {
-        if (!cs_spin_ge(ready, want, tmo)) atomicCAS(info, 0, -1);
-        if (!WT) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    }
-    __syncthreads();
-    if (tlog && threadIdx.x == 0) tlog[1] = wall_clock64();
-    leaf2_body<T, WT>(smem_raw, A, lda, inv, NB, info, col0, ablate, tlog);
-    if (tlog && threadIdx.x == 0) tlog[2] = wall_clock64();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tlog && threadIdx.x == 0) tlog[3] = wall_clock64();
-    if (threadIdx.x == 0) {
-        if (!WT) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __hip_atomic_store(done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
 // The third form as kernels of its own: sharing a kernel with the second form (a run-time switch between two inlined bodies) left
 // the pivot loop two scalar registers for its broadcasts.
 template <typename T, bool WT, bool BLK = false>
@@ -1184,102 +724,45 @@ __global__ __launch_bounds__(NTH) void pg_leaf3_kernel(T* __restrict__ A, long l
     leaf3_body<T, false, BLK>(smem_raw, A + blockIdx.x * eA, lda, inv ? inv + blockIdx.x * eInv : nullptr, ldi, info + blockIdx.x, col0, nullptr, nf3);
 }
 
-static bool pg_leaf3_blk() {
-    static const bool v = !(getenv("PG_LEAF3_BLK") && !atoi(getenv("PG_LEAF3_BLK")));
-    return v;
-}
-bool pg_leaf_has_early() {   // the coupled leaf raises its early flag before its done flag (third form, write-through hand-off)
-    static const bool v = !(getenv("PG_LEAF3") && !atoi(getenv("PG_LEAF3"))) && !(getenv("PG_CS_LEAF_WT") && !atoi(getenv("PG_CS_LEAF_WT")));
-    return v;
-}
+// The leaf's LDS: the tile, the diagonal blocks' inverses and the blocked factor's staging area
+template <typename T> static size_t leaf_lds() { return (size_t)(NB * LD + 8 * 16 * DLD + 2 + 16 + F3_STAGE) * sizeof(T) + 16; }
+// Flags of leaf3_body: one column block per step (1) and the diagonal factor alone on its wave (16)
+#define LEAF3_NF (1 | 16)
+
+// The diagonal 16 x 16 factor: blocked on the matrix pipe in fp64 (leaf3_factor_blk), row per lane in fp32.  The coupled leaf moves
+// its tile and inverse with write-through accesses and raises its early flag once the first 64 rows of the inverse are stored.
 template <typename T> int pg_leaf_sync(hipStream_t st, T* A, long lda, T* inv, int* info, int col0, int* ready, int want, int* done,
                                        const CsWait& tmo, int* early, const CsBatch* cbp) {
+    constexpr bool blk = sizeof(T) == 8;
     const CsBatch cb = cbp ? *cbp : CsBatch{1, 0, 0, 0};
-    const size_t lds = (size_t)(NB * LD + 8 * 16 * DLD + 2 + 16 + F3_STAGE) * sizeof(T) + 16;
+    const size_t lds = leaf_lds<T>();
     static bool attr_done = false;
     if (!attr_done) {
-        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_leaf2s_kernel<T, true>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_leaf2s_kernel<T, false>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_leaf3s_kernel<T, true>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_leaf3s_kernel<T, false>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_leaf3s_kernel<T, true, true>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_leaf3s_kernel<T, false, true>),
+        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_leaf3s_kernel<T, true, blk>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_done = true;
     }
-    static const int wt = getenv("PG_CS_LEAF_WT") ? atoi(getenv("PG_CS_LEAF_WT")) : 1;
-    // Round 3 built two variants of the leaf's body and measured them against round 2's (same box, tools/probe_potrf_only.py and
-    // the in-kernel stamps of tools/probe_cs_tlog.py); round 2's form stays the default, the variants are kept behind switches:
-    //   PG_LEAF_PROG=1  tile loaded in two sets (columns 0-31 first), L columns and inverse block rows stored while the loop runs:
-    //                   load 2.2 -> 1.5 us, but the stores' LDS reads stretch every step by 0.1-0.3 us: n = 4096 1.63 -> 1.65 ms
-    //   PG_LEAF_LDL=1   square-root-free pivot chain (1.44 -> 1.04 us per 16-column step in isolation, tools/micro/tallstep.hip),
-    //                   no gain inside the kernel: a step's 2.9-3.5 us are the chain (1.4), the rows' LDS round trip (1.2) and
-    //                   two barriers, and the shorter chain only moves the waiting: n = 4096 1.63 -> 1.69 ms
-    static const int abl = ((getenv("PG_LEAF_PROG") && atoi(getenv("PG_LEAF_PROG"))) ? 0 : 16) |
-                           ((getenv("PG_LEAF_LDL") && atoi(getenv("PG_LEAF_LDL"))) ? 0 : 32) |
-                           ((getenv("PG_LEAF3") && !atoi(getenv("PG_LEAF3"))) ? 0 : 64);           // third form (default); PG_LEAF3=0: second
     long long* tl = getenv("PG_CS_TLOG") ? reinterpret_cast<long long*>(tmo.tmo) + 512 + 48 * (col0 / NB) : nullptr;
-    if (abl & 64) {
-        static const int nf3 = (getenv("PG_LEAF3_NF") ? std::max(1, std::min(4, atoi(getenv("PG_LEAF3_NF")))) : 1) |
-                               ((getenv("PG_LEAF3_ALONE") && !atoi(getenv("PG_LEAF3_ALONE"))) ? 0 : 16) |
-                               ((getenv("PG_LEAF3_DIAG") && atoi(getenv("PG_LEAF3_DIAG"))) ? 64 : 0);
-        // blocked diagonal factor (leaf3_factor_blk: fp64, default; PG_LEAF3_BLK=0: the row-per-lane factor) -- a kernel of its own per form
-        if (pg_leaf3_blk() && sizeof(T) == 8) {
-            if (wt) hipLaunchKernelGGL((pg_leaf3s_kernel<T, true, true>), dim3(cb.nexp), dim3(NTH), lds, st, A, lda, inv, info, col0, ready, want, done, tmo, tl, nf3, early, cb);
-            else hipLaunchKernelGGL((pg_leaf3s_kernel<T, false, true>), dim3(cb.nexp), dim3(NTH), lds, st, A, lda, inv, info, col0, ready, want, done, tmo, tl, nf3, early, cb);
-        } else if (wt) hipLaunchKernelGGL((pg_leaf3s_kernel<T, true>), dim3(cb.nexp), dim3(NTH), lds, st, A, lda, inv, info, col0, ready, want, done, tmo, tl, nf3, early, cb);
-        else hipLaunchKernelGGL((pg_leaf3s_kernel<T, false>), dim3(cb.nexp), dim3(NTH), lds, st, A, lda, inv, info, col0, ready, want, done, tmo, tl, nf3, early, cb);
-        PG_CHECK(hipGetLastError());
-        return 0;
-    }
-    if (cb.nexp > 1) { pg_set_error("pg_leaf_sync: the second leaf form (PG_LEAF3=0) does not batch experts"); return -2; }
-    if (wt) hipLaunchKernelGGL((pg_leaf2s_kernel<T, true>), dim3(1), dim3(NTH), lds, st, A, lda, inv, info, col0, ready, want, done, tmo,
-                               getenv("PG_CS_TLOG") ? reinterpret_cast<long long*>(tmo.tmo) + 512 + 48 * (col0 / NB) : nullptr, abl);
-    else hipLaunchKernelGGL((pg_leaf2s_kernel<T, false>), dim3(1), dim3(NTH), lds, st, A, lda, inv, info, col0, ready, want, done, tmo,
-                               getenv("PG_CS_TLOG") ? reinterpret_cast<long long*>(tmo.tmo) + 512 + 48 * (col0 / NB) : nullptr, abl);
+    hipLaunchKernelGGL((pg_leaf3s_kernel<T, true, blk>), dim3(cb.nexp), dim3(NTH), lds, st, A, lda, inv, info, col0, ready, want, done, tmo, tl,
+                       LEAF3_NF, early, cb);
     PG_CHECK(hipGetLastError());
     return 0;
 }
 template int pg_leaf_sync<double>(hipStream_t, double*, long, double*, int*, int, int*, int, int*, const CsWait&, int*, const CsBatch*);
 template int pg_leaf_sync<float>(hipStream_t, float*, long, float*, int*, int, int*, int, int*, const CsWait&, int*, const CsBatch*);
 
-template <typename T> int pg_leaf(hipStream_t st, T* A, long lda, T* inv, long ldi, int* info, int col0, int ablate, int nexp, long eA,
-                                  long eInv) {
-    const size_t lds = (size_t)(NB * LD + 8 * 16 * DLD + 2 + 16 + F3_STAGE) * sizeof(T) + 16;
+template <typename T> int pg_leaf(hipStream_t st, T* A, long lda, T* inv, long ldi, int* info, int col0, int nexp, long eA, long eInv) {
+    constexpr bool blk = sizeof(T) == 8;
+    const size_t lds = leaf_lds<T>();
     static bool attr_done = false;
-    static const int form = getenv("PG_LEAF") ? atoi(getenv("PG_LEAF")) : 2;   // 1: round-1 leaf (A / B / C phases), 2: fused tall-panel step
-    if (!(getenv("PG_LEAF_PROG") && atoi(getenv("PG_LEAF_PROG")))) ablate ^= 16;     // default: round 2's data movement (bit 4 set);
-    if (!(getenv("PG_LEAF_LDL") && atoi(getenv("PG_LEAF_LDL")))) ablate ^= 32;       // a caller's bit asks for the other form
-    if (!(getenv("PG_LEAF3") && !atoi(getenv("PG_LEAF3")))) ablate ^= 64;           // third form unless PG_LEAF3=0 (or the caller's bit 6)
     if (!attr_done) {
-        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_leaf_kernel<T>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_leaf2_kernel<T>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_leaf3_kernel<T>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_leaf3_kernel<T, true>),
+        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_leaf3_kernel<T, blk>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_done = true;
     }
-    if ((ablate & 64) && form != 1 && !(ablate & 15)) {      // third form (no ablation switches)
-        static const int nf3 = (getenv("PG_LEAF3_NF") ? std::max(1, std::min(4, atoi(getenv("PG_LEAF3_NF")))) : 1) |
-                               ((getenv("PG_LEAF3_ALONE") && !atoi(getenv("PG_LEAF3_ALONE"))) ? 0 : 16) |
-                               ((getenv("PG_LEAF3_DIAG") && atoi(getenv("PG_LEAF3_DIAG"))) ? 64 : 0);
-        if (pg_leaf3_blk() && sizeof(T) == 8) hipLaunchKernelGGL((pg_leaf3_kernel<T, true>), dim3(nexp), dim3(NTH), lds, st, A, lda, inv, ldi, info, col0, eA, eInv, nf3);
-        else hipLaunchKernelGGL(pg_leaf3_kernel<T>, dim3(nexp), dim3(NTH), lds, st, A, lda, inv, ldi, info, col0, eA, eInv, nf3);
-        PG_CHECK(hipGetLastError());
-        return 0;
-    }
-    if (form == 1) hipLaunchKernelGGL(pg_leaf_kernel<T>, dim3(nexp), dim3(NTH), lds, st, A, lda, inv, ldi, info, col0, ablate, eA, eInv);
-    else hipLaunchKernelGGL(pg_leaf2_kernel<T>, dim3(nexp), dim3(NTH), lds, st, A, lda, inv, ldi, info, col0, ablate, eA, eInv);
+    hipLaunchKernelGGL((pg_leaf3_kernel<T, blk>), dim3(nexp), dim3(NTH), lds, st, A, lda, inv, ldi, info, col0, eA, eInv, LEAF3_NF);
     PG_CHECK(hipGetLastError());
     return 0;
 }
-template int pg_leaf<double>(hipStream_t, double*, long, double*, long, int*, int, int, int, long, long);
-template int pg_leaf<float>(hipStream_t, float*, long, float*, long, int*, int, int, int, long, long);
+template int pg_leaf<double>(hipStream_t, double*, long, double*, long, int*, int, int, long, long);
+template int pg_leaf<float>(hipStream_t, float*, long, float*, long, int*, int, int, long, long);

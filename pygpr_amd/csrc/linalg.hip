@@ -394,21 +394,10 @@ template <typename T> static GemmP<T> gp0() {
     return p;
 }
 
-// inv_diag [n/128][128][128], then the flag words of the coupled chain (3 n/128 + 1 ints, and the in-kernel time log when
-// PG_CS_TLOG is set), then -- only in the experimental recursive-panel mode (PG_PANEL_MODE=1) -- the work area of the panel step:
-// W = inverse of the current outer panel's triangular factor (at most 2048 x 2048) and Xs = the panel's solved rows before they
-// are copied back (n x at most 2048).  The default mode's workspace is n * 128 + 128 n/128 + 2048 elements (round 2 always
-// carried W and Xs: +300 MB at n = 16384, 35x the default need of a 2048-point expert).
-#define NBO_MAX 2048
-static int pg_panel_mode_env() {
-    static const int v = getenv("PG_PANEL_MODE") ? atoi(getenv("PG_PANEL_MODE")) : 0;
-    return v;
-}
+// inv_diag [n/128][128][128], then the flag words of the coupled chain (5 n/128 + 1 ints, and the in-kernel time log when
+// PG_CS_TLOG is set): n * 128 + 128 n/128 + 2048 elements.
 static long pg_flag_elems(int n) { return 128L * (n / NB) + 2048; }   // elements of T (>= 4 bytes each)
-long pg_potrf_worksize_impl(int n) {
-    const long w = std::min<long>(n, NBO_MAX);
-    return (long)n * NB + pg_flag_elems(n) + (pg_panel_mode_env() == 1 ? w * w + (long)n * w : 0);
-}
+long pg_potrf_worksize_impl(int n) { return (long)n * NB + pg_flag_elems(n); }
 
 template <typename T>
 int pg_trtri_t(pg_ctx* ctx, hipStream_t st, int n, const T* L, long ldl, const T* invD, T* M, long ldm, int hmax, const ExpBatch* eb) {
@@ -461,23 +450,18 @@ int pg_trtri_t(pg_ctx* ctx, hipStream_t st, int n, const T* L, long ldl, const T
     return 0;
 }
 
-// Top level of the triangular inverse for the split [0, h1) | [h1, h1 + h2): S = (L21 M11)^T into the mirrored block
-// (first), then M21 = -M22 S^T (second).  The first product only needs L21 and M11.
+// Top level of the triangular inverse for the split [0, h1) | [h1, h1 + h2): S = (L21 M11)^T into the mirrored block,
+// then M21 = -M22 S^T.
 template <typename T>
-static int trtri_top(pg_ctx* ctx, hipStream_t st, int h1, int h2, const T* L, long ldl, T* M, long ldm, bool first, bool second) {
+static int trtri_top(pg_ctx* ctx, hipStream_t st, int h1, int h2, const T* L, long ldl, T* M, long ldm) {
     int rc;
-    if (first) {
-        GemmP<T> p = gp0<T>();
-        p.M = h1; p.N = h2; p.K = h1; p.A = M; p.lda = ldm; p.B = L + (long)h1 * ldl; p.ldb = ldl; p.C = M + h1; p.ldc = ldm; p.klo = 1;
-        if ((rc = pg_gemm<T>(ctx, st, GEMM_TT_128, p))) return rc;
-    }
-    if (second) {
-        GemmP<T> p = gp0<T>();
-        p.M = h2; p.N = h1; p.K = h2; p.A = M + (long)h1 * ldm + h1; p.lda = ldm; p.B = M + h1; p.ldb = ldm;
-        p.C = M + (long)h1 * ldm; p.ldc = ldm; p.alpha = (T)-1; p.khi = 1;
-        if ((rc = pg_gemm<T>(ctx, st, GEMM_NT_128, p))) return rc;
-    }
-    return 0;
+    GemmP<T> p = gp0<T>();
+    p.M = h1; p.N = h2; p.K = h1; p.A = M; p.lda = ldm; p.B = L + (long)h1 * ldl; p.ldb = ldl; p.C = M + h1; p.ldc = ldm; p.klo = 1;
+    if ((rc = pg_gemm<T>(ctx, st, GEMM_TT_128, p))) return rc;
+    p = gp0<T>();
+    p.M = h2; p.N = h1; p.K = h2; p.A = M + (long)h1 * ldm + h1; p.lda = ldm; p.B = M + h1; p.ldb = ldm;
+    p.C = M + (long)h1 * ldm; p.ldc = ldm; p.alpha = (T)-1; p.khi = 1;
+    return pg_gemm<T>(ctx, st, GEMM_NT_128, p);
 }
 
 long long pg_wait_ticks(const pg_ctx* ctx, int n) {
@@ -517,7 +501,7 @@ int pg_potrf_t(pg_ctx* ctx, hipStream_t st, int n, T* A, long lda, T* invD, int*
 // the M21 block of the inverse's buffer -- free until the last product writes it -- so the panel product is out of place.
 // A bad pivot in the leading half leaves info != 0: every later launch returns at once (GemmP::info), the second half keeps it.
 static int pg_rec_split(const pg_ctx* ctx, int n) {
-    if (ctx->rec_min <= 0 || n < ctx->rec_min || n < 2 * PG_PAD || ctx->bg || ctx->panel_mode) return 0;
+    if (ctx->rec_min <= 0 || n < ctx->rec_min || n < 2 * PG_PAD) return 0;
     return ((n / 2 + PG_PAD - 1) / PG_PAD) * PG_PAD;
 }
 
@@ -572,7 +556,7 @@ static int potrf_trtri_rec(pg_ctx* ctx, hipStream_t st, int n, T* A, long lda, T
     if ((rc = pg_potrf_t<T>(ctx, st, h2, A22, lda, invD + (long)(h1 / NB) * NB * NB, info, Minv + (long)h1 * ldm + h1, ldm, nullptr, nullptr,
                             col_off + h1, 1)))
         return rc;
-    return trtri_top<T>(ctx, st, h1, h2, A, lda, Minv, ldm, true, true);
+    return trtri_top<T>(ctx, st, h1, h2, A, lda, Minv, ldm);
 }
 
 // Look-ahead: for outer panel o let Chain(o) = its 8 (U, leaf, T) steps, Sa(o) = update of panel o+1's columns by
@@ -584,6 +568,23 @@ static int potrf_trtri_rec(pg_ctx* ctx, hipStream_t st, int n, T* A, long lda, T
 // stream may not use the last PG_RESERVED_CUS compute units: the chain's small kernels (and the leaf, which needs a
 // whole CU's LDS) always find free CUs instead of queueing behind 280 us SYRK tiles.  Everything is joined back onto
 // the caller's stream at the end.
+//
+// Flag-coupled chain (chainstep.hip) for the panels with at most COUPLED_ROWS rows left -- the chain-bound tail: leaves on the
+// panel stream, the rows below them on the handle's rows stream, coupled by flags in device memory instead of launches.
+// Its rows kernels update a block column by the previous panel too (the window of the left-looking product starts there), so
+// the per-panel update Sa disappears from the critical path; panels are at most COUPLED_PANEL wide there to keep that product
+// shorter than a leaf.
+// Measured (MI355X, fp64, build + factor): n = 4096 2.28 -> 1.68 ms, 8192 6.30 -> 5.19, 16384 30.75 -> 29.13 with the last 8192
+// rows coupled (2048: 30.41, 4096: 30.03, 6144: 29.62, 12288: 30.14, all: 31.48 -- while the trailing update still fills the
+// chip the resident rows workgroups hold the slots it needs).
+#define COUPLED_ROWS 8192
+#define COUPLED_PANEL 384   // round 3, same box: 512 -> 384: n = 4096 1.64 -> 1.60 ms, 8192 5.10 -> 5.03, 16384 equal
+// U launches of at most this many rows (and K a multiple of 64) run on 32 x 32 tiles
+#define U_SMALL_ROWS 8192
+// Sb launches with fewer 128 x 128 tiles than this run on 64 x 64 tiles
+// (swept 512 / 1024 / 2048: 2048 is 2 % faster at n = 8192 and neutral at 16384; re-swept with the eight-wave blocks,
+// 2048 / 1024 / 512 / 256: 2048 stays best at 8192, neutral at 16384)
+#define SB_SMALL_TILES 2048
 template <typename T>
 int pg_potrf_t(pg_ctx* ctx, hipStream_t st, int n, T* A, long lda, T* invD, int* info, T* Minv, long ldm, const BuildReq<T>* build,
                const ExpBatch* eb, int col_off, int keep_info) {
@@ -600,18 +601,6 @@ int pg_potrf_t(pg_ctx* ctx, hipStream_t st, int n, T* A, long lda, T* invD, int*
     // and half-width panels over the last 4096 / 8192 columns -- both within +-0.2 ms at n = 12288 / 16384: the schedule
     // is throughput-bound on the whole (the chain and the updates share the chip at 62-77 % MFMA use per CU), so shifting
     // work between its two streams does not shorten it.
-    // flag-coupled chain (chainstep.hip) for the panels with at most `sync_rows` rows left -- the chain-bound tail: leaves on the
-    // panel stream, the rows below them on the handle's rows stream, coupled by flags in device memory instead of launches.
-    // Its rows kernels update a block column by the previous panel too (the window of the left-looking product starts there), so
-    // the per-panel update Sa disappears from the critical path; panels are at most 384 wide there (PG_CS_PANEL) to keep that product
-    // shorter than a leaf.
-    // Measured (MI355X, fp64, build + factor): n = 4096 2.28 -> 1.68 ms, 8192 6.30 -> 5.19, 16384 30.75 -> 29.13 with the last 8192
-    // rows coupled (2048: 30.41, 4096: 30.03, 6144: 29.62, 12288: 30.14, all: 31.48 -- while the trailing update still fills the
-    // chip the resident rows workgroups hold the slots it needs).  With the experimental background inverse of the fused call
-    // running (PG_BG_STREAM=1), the rows workgroups starve beside its long tiles: n = 16384 fused 51.5 -> 52.5 ms, so above 8192
-    // that configuration keeps the classic chain.
-    static const int sync_env = getenv("PG_SYNC_ROWS") ? atoi(getenv("PG_SYNC_ROWS")) : -1;
-    const int sync_rows = sync_env >= 0 ? sync_env : ((Minv && ctx->bg && n > 8192) ? 0 : 8192);
     hipStream_t rows_stream = ctx->rows;      // the handle's own (capi.hip)
     // Experts together take the coupled chain too (round 4) -- one leaf workgroup and one grid row of rows workgroups per expert, flag
     // words in each expert's own work buffer -- where the batch is still latency-bound: experts of at least 2048 points and at most
@@ -620,19 +609,12 @@ int pg_potrf_t(pg_ctx* ctx, hipStream_t st, int n, T* A, long lda, T* invD, int*
     // the resident kernels only take slots from the trailing updates (8 x 4096 9.32 / 9.06, 8 x 9216 78.7 / 75.5; 16 x 2048 and 3 x 8192
     // equal), and below 2048 points three panels are too few (8 x 1024 0.79 / 0.73).  PG_CS_BATCHED=0: never; 2: whenever it can run.
     static const int cs_batched = getenv("PG_CS_BATCHED") ? atoi(getenv("PG_CS_BATCHED")) : 1;
-    const bool batch_cp = cs_batched && nexp <= 24 && pg_leaf_has_early() && (cs_batched == 2 || (n >= 2048 && (long)nexp * n <= 24576));
-    const bool want_cp = ctx->lookahead && !ctx->prof_on && ctx->coupled && rows_stream && sync_rows > 0 && ctx->panel_mode == 0 &&
-                         (nexp == 1 || batch_cp);
+    const bool batch_cp = cs_batched && nexp <= 24 && (cs_batched == 2 || (n >= 2048 && (long)nexp * n <= 24576));
+    const bool want_cp = ctx->lookahead && !ctx->prof_on && ctx->coupled && rows_stream && (nexp == 1 || batch_cp);
     std::vector<int> pb;      // panel o = columns [pb[o], pb[o+1])
-    static const int cs_panel = getenv("PG_CS_PANEL") ? atoi(getenv("PG_CS_PANEL")) : 384;   // round 3, same box: 512 -> 384: n = 4096 1.64 -> 1.60 ms, 8192 5.10 -> 5.03, 16384 equal
-    // experiment: wider coupled panels while the trailing update still bounds the step (deeper K for Sb), narrow ones in the chain-bound tail
-    static const int cs_panel_wide = getenv("PG_CS_PANEL_WIDE") ? atoi(getenv("PG_CS_PANEL_WIDE")) : 0;
-    static const int cs_wide_rows = getenv("PG_CS_WIDE_ROWS") ? atoi(getenv("PG_CS_WIDE_ROWS")) : 5120;
     for (int c = 0; c < n;) {
         pb.push_back(c);
-        int w = NBO;
-        if (want_cp && n - c <= sync_rows) w = std::min(NBO, (cs_panel_wide > 0 && n - c > cs_wide_rows) ? cs_panel_wide : cs_panel);
-        c += w;
+        c += (want_cp && n - c <= COUPLED_ROWS) ? std::min(NBO, COUPLED_PANEL) : NBO;
     }
     pb.push_back(n);
     const int npan = (int)pb.size() - 1;
@@ -662,19 +644,12 @@ int pg_potrf_t(pg_ctx* ctx, hipStream_t st, int n, T* A, long lda, T* invD, int*
         if ((rc = pool_event(ctx, 7 + 2 * npan, &ev))) return rc;      // ev_build: every column right of the first panel exists
         PG_CHECK(hipEventRecord(ev, us));
     }
-    // fused L^-1: split the diagonal at `split` columns; the leading part is inverted in the background once its
-    // columns are final (after the chain of panel split/NBO - 1), together with the first top-level product
-    // (below n = 5120 the cross-stream split costs more than the overlap returns: 3.66 vs 3.79 ms at n = 4096)
-    const int split = (Minv && la && ctx->bg && n / NBO >= 4 && n >= 5120 && nexp == 1) ? ((n + NBO - 1) / NBO / 2) * NBO : 0;
-    const long NBW = std::min<long>(n, NBO_MAX);
     T* flagw = invD + (long)n * NB;       // flag words of the coupled chain
-    T* Wt = flagw + pg_flag_elems(n);     // (PG_PANEL_MODE=1 only) inverse of the current panel's triangular factor, leading dimension = panel width
-    T* Xs = Wt + NBW * NBW;               // (PG_PANEL_MODE=1 only) the panel's solved rows (out of place), leading dimension = panel width
     const bool coupled = la && want_cp;
     int o_s = npan;                             // first coupled panel
     if (coupled)
         for (int o = 0; o < npan; ++o)
-            if (n - pb[o] <= sync_rows) { o_s = o; break; }
+            if (n - pb[o] <= COUPLED_ROWS) { o_s = o; break; }
     ctx->last_coupled = npan - o_s;
     const int nblk = n / NB;
     int* f_diag = reinterpret_cast<int*>(flagw);   // [nblk] workgroups that have published tile (b, b)
@@ -689,76 +664,14 @@ int pg_potrf_t(pg_ctx* ctx, hipStream_t st, int n, T* A, long lda, T* invD, int*
     // whole trailing update of the part before the coupled region (3 ms at n = 16384), never a multiple of the call
     const CsWait cw = {f_tmo, ctx->tmo_dev, pg_wait_ticks(ctx, n), ctx->chain_epoch};
     const CsBatch cbat = {nexp, eA, eI, (long)(eI * (long)sizeof(T) / (long)sizeof(int))};   // flag stride in ints
-    // two-phase hand-over (chainstep.hip): only the third leaf form raises the early flag
-    static const bool two_phase_env = !(getenv("PG_CS_TWO_PHASE") && atoi(getenv("PG_CS_TWO_PHASE")) == 0);
-    const bool two_phase = two_phase_env && pg_leaf_has_early();
     if (o_s < npan) {
         // (ps: behind the fork event; experts together: the same words in every expert's work buffer)
         PG_CHECK(hipMemset2DAsync(f_diag, (size_t)(nexp > 1 ? eI : pg_potrf_worksize_impl(n)) * sizeof(T), 0, (size_t)((5 * nblk + 1 + 3) / 4) * 16, (size_t)nexp, ps));
     }
-    // Coupled panels while the trailing update still bounds the step (more than `sa_rows` rows right of the panel): the next panel's
-    // columns take this panel's update as ONE product on the update stream ("Sa", then a flag for the next leaf) instead of through the
-    // rows kernels' two-panel window.  There the rows workgroups live on the reserved CUs only (77 KB of LDS do not fit beside the 64 x 64
-    // blocks of the trailing update), and their window products, squeezed onto 32 CUs, took as long as the update itself
-    // (n = 8192, steps 8-10: 34 | 158 | 228 us, the leaf of the next panel not even finding a CU for 190 us).
-    static const int sa_rows = getenv("PG_CS_SA_ROWS") ? atoi(getenv("PG_CS_SA_ROWS")) : 0;   // measured: slower at every setting (n = 8192: off 4.77, 6144: 4.83, 4608: 4.90, 3072: 4.98, 2048: 5.06 ms): the panel period there is the trailing update's own time
-    auto sa_after = [&](int o) { return sa_rows > 0 && o >= o_s && o + 1 < npan && (n - pb[o + 1]) > sa_rows; };
     std::vector<char> nf_split(npan + 1, 0);   // Sb(o) was launched as NEAR + FAR
-    // Deferred trailing block (round 5; pg_set_deferred_block / PG_DEFER=1, OFF by default: measured slower).
-    // A right-looking factorisation spends its throughput work first and ends in a chain-bound tail beside an idle chip (n = 8192: the
-    // last 19 of 64 steps).  With the switch on, the panels left of column cd = pb[od] (about n / 2) update only the columns left of
-    // cd2 = pb[oe]; the block right of cd2 receives everything those panels owe it LATER, panel by panel, as products K = cd deep
-    // ("BU(p)", one trapezoid launch per column panel p >= oe, its K range dealt to several workgroups per tile) on the update stream
-    // between the NEAR / FAR launches of the second half.  oe >= od + 1: the two-panel window of a rows kernel that works on a deferred
-    // panel then starts right of cd (nothing is applied twice).  Measured at n = 8192 (same box, potrf alone): 4.64 ms without, 4.78
-    // with -- the first half shrinks (3.3 -> 2.7 ms in the kernel trace), but a column panel of the deferred block is a few hundred
-    // tiles that run at 41-45 TFLOP/s beside the resident rows kernels (64 x 64 tiles; 128 x 128 with the K range dealt out: 5.36 ms),
-    // no better than the K = 384 updates they replace, and the second half waits for them (2.6 ms against 1.7).
-    static const int defer_min = getenv("PG_DEFER_MIN") ? atoi(getenv("PG_DEFER_MIN")) : 6144;
-    static const double defer_frac = getenv("PG_DEFER_FRAC") ? atof(getenv("PG_DEFER_FRAC")) : 0.5;
-    static const int defer_gap = getenv("PG_DEFER_GAP") ? std::max(1, atoi(getenv("PG_DEFER_GAP"))) : 1;
-    static const int defer_lead = getenv("PG_DEFER_LEAD") ? std::max(1, atoi(getenv("PG_DEFER_LEAD"))) : 3;
-    static const int nf_env0 = getenv("PG_CS_NEARFAR") ? atoi(getenv("PG_CS_NEARFAR")) : 1;
-    int od = -1, oe = -1, next_bu = 0;
-    if (ctx->defer && coupled && o_s == 0 && nexp == 1 && n >= defer_min && nf_env0 && sa_rows == 0) {
-        int o = 0;
-        while (o < npan && pb[o] < (int)(defer_frac * n)) ++o;
-        if (o >= 3 && o + defer_gap + 2 < npan) { od = o; oe = o + defer_gap; next_bu = oe; }
-    }
-    const bool defer = od > 0;
-    const int cd = defer ? pb[od] : 0, cd2 = defer ? pb[oe] : 0;
-    ctx->last_deferred = defer ? npan - oe : 0;
-    auto launch_bu = [&](int p) -> int {   // A[pb[p]:, panel p] -= L[pb[p]:, 0:cd] L[panel p, 0:cd]^T, lower tiles
-        GemmP<T> q = gp0<T>(); q.info = info;
-        q.M = n - pb[p]; q.N = pb[p + 1] - pb[p]; q.K = cd;
-        q.A = A + (long)pb[p] * lda; q.lda = lda; q.B = q.A; q.ldb = lda; q.C = A + (long)pb[p] * lda + pb[p]; q.ldc = lda;
-        q.alpha = (T)-1; q.beta = (T)1; q.tri = 1;
-        static const long bu_thresh = getenv("PG_BU_TILE_THRESH") ? atol(getenv("PG_BU_TILE_THRESH")) : 1024;
-        static const long bu_ksplit = getenv("PG_BU_KSPLIT") ? atol(getenv("PG_BU_KSPLIT")) : 1200;   // workgroups a launch should have
-        const long tiles = (long)(q.M / 128) * (q.N / 128);
-        const int variant = tiles < bu_thresh ? GEMM_NT_64 : GEMM_NT_128;
-        // A panel of the deferred block is a few hundred tiles, each K = cd deep: one workgroup per tile walks 4224 columns in 210 us
-        // whatever the launch's size.  The K range is dealt to `ks` workgroups per tile (the launch's batch dimension, all adding into
-        // the same C through the no-return fp64 atomics of the beta = 1 epilogue).
-        int ks = 1;
-        if (sizeof(T) == 8 && bu_ksplit > 0 && !ctx->no_atomic_c) {
-            const long bt = variant == GEMM_NT_64 ? 64 : 128, tn_ = q.N / bt, tm_ = q.M / bt;
-            const long wgs = tn_ * (tn_ + 1) / 2 + (tm_ - tn_) * tn_;
-            for (int k = 2; k <= 8; ++k)
-                if (cd % (k * 32) == 0 && wgs * (k - 1) < bu_ksplit) ks = k;
-        }
-        if (ks > 1) { q.K = cd / ks; q.batch = ks; q.sA = q.sB = cd / ks; q.sC = 0; }
-        int r = pg_gemm<T>(ctx, us, variant, q);
-        if (r) return r;
-        hipEvent_t e;
-        if ((r = pool_event(ctx, 10 + 4 * npan + p, &e))) return r;   // ev_bu[p]
-        PG_CHECK(hipEventRecord(e, us));
-        return 0;
-    };
     for (int o = 0; o < npan; ++o) {
         const int o0 = pb[o], oend = pb[o + 1];
         const bool cp = o >= o_s;
-        const bool sa_this = cp && sa_after(o), sa_prev = cp && o > o_s && sa_after(o - 1);
         if (cp) {
             hipStream_t rs = rows_stream;
             if (o == o_s) {
@@ -771,62 +684,47 @@ int pg_potrf_t(pg_ctx* ctx, hipStream_t st, int n, T* A, long lda, T* invD, int*
             for (int k0 = o0; k0 < oend; k0 += NB) {
                 const int kb = k0 / NB;
                 T* inv = invD + (long)kb * NB * NB;
+                // two-phase hand-over (chainstep.hip): the leaf raises its early flag once the first 64 rows of its inverse are stored
                 if ((rc = pg_leaf_sync<T>(ps, A + (long)k0 * lda + k0, lda, inv, info, k0 + col_off, f_diag + kb, PG_CS_NCRIT, f_done + kb, cw,
-                                          two_phase ? f_early + kb : nullptr, &cbat)))
+                                          f_early + kb, &cbat)))
                     return rc;
                 if (n - k0 - NB <= 0) break;
                 const int c = k0 + NB;                       // the block column this step brings up to date
                 const int oc = c < oend ? o : o + 1;         // its panel
-                // the classic part applied the panel before the first coupled one; so does Sa(o - 1) in the update-bound part
-                const int wstart = (oc == o_s || (oc == o && sa_prev)) ? pb[oc] : pb[oc - 1];
-                const bool last_sa = c == oend && sa_this;   // the next panel's first column is Sa(o)'s: this step only solves
-                if (c == oend && oc >= 2 && !last_sa) {      // first touch of panel oc: Sb(oc - 2) wrote these columns last
+                const int wstart = oc == o_s ? pb[oc] : pb[oc - 1];   // the classic part applied the panel before the first coupled one
+                if (c == oend && oc >= 2) {                  // first touch of panel oc: Sb(oc - 2) wrote these columns last
                     // (its NEAR launch when that panel was a coupled one: nf_split[oc - 2])
                     if ((rc = pool_event(ctx, nf_split[oc - 2] ? 9 + 3 * npan + (oc - 2) : 2 + 2 * (oc - 2) + 1, &ev))) return rc;
                     PG_CHECK(hipStreamWaitEvent(rs, ev, 0));
-                    if (defer && oc >= oe) {                 // a deferred panel: what the first half owes it arrives as BU(oc)
-                        if ((rc = pool_event(ctx, 10 + 4 * npan + oc, &ev))) return rc;
-                        PG_CHECK(hipStreamWaitEvent(rs, ev, 0));
-                    }
                 }
-                if (c == oend && oc == 1 && build_split && !last_sa) {   // first touch of a column the folded build wrote on the update stream
+                if (c == oend && oc == 1 && build_split) {   // first touch of a column the folded build wrote on the update stream
                     if ((rc = pool_event(ctx, 7 + 2 * npan, &ev))) return rc;
                     PG_CHECK(hipStreamWaitEvent(rs, ev, 0));
                 }
-                if (k0 == o0 && sa_prev) {                   // this panel's columns were last written by Sa(o - 1) on the update stream
-                    if ((rc = pool_event(ctx, 8 + 2 * npan + (o - 1), &ev))) return rc;
-                    PG_CHECK(hipStreamWaitEvent(rs, ev, 0));
-                }
-                if ((rc = pg_rowstep<T>(rs, A, lda, n, wstart, k0, last_sa ? 0 : 1, inv, f_done + kb, f_brow + kb, f_diag + kb + 1, cw, info,
-                                        (two_phase && !last_sa) ? f_early + kb : nullptr, f_browe + kb, 1, &cbat)))
+                if ((rc = pg_rowstep<T>(rs, A, lda, n, wstart, k0, 1, inv, f_done + kb, f_brow + kb, f_diag + kb + 1, cw, info, f_early + kb,
+                                        f_browe + kb, 1, &cbat)))
                     return rc;
             }
         }
-        const int mode = (oend < n && pg_panel_mode_env() == 1 && nexp == 1) ? ctx->panel_mode : 0;
-        const bool v2 = mode == 1;
-        const int tri_end = v2 ? oend : n;     // last row the panel stream's 128-column steps touch
         for (int k0 = o0; k0 < oend && !cp; k0 += NB) {
             T* Akk = A + (long)k0 * lda + k0;
             T* inv = invD + (long)(k0 / NB) * NB * NB;
             if (k0 > o0) {   // U: bring this column block up to date with the panel's earlier columns
                 GemmP<T> p = gp0<T>(); p.info = info;
-                p.M = tri_end - k0; p.N = NB; p.K = k0 - o0;
+                p.M = n - k0; p.N = NB; p.K = k0 - o0;
                 p.A = A + (long)k0 * lda + o0; p.lda = lda; p.B = p.A; p.ldb = lda; p.C = Akk; p.ldc = lda;
                 p.alpha = (T)-1; p.beta = (T)1;
                 batched(p, eA, eA, eA);
                 // fewer than two 64-row workgroups per CU: half the row tile keeps two waves on every SIMD (gemm.h); in the
                 // chain-bound tail the launch's latency is what counts: 32 x 32 tiles with a 64-deep K tile
-                static const int u32rows = getenv("PG_U32_ROWS") ? atoi(getenv("PG_U32_ROWS")) : 8192;
-                int uv = (p.M <= u32rows && p.K % 64 == 0) ? GEMM_NT_32x32 : (p.M <= 12288 ? GEMM_NT_32x64 : GEMM_NT_64);
+                int uv = (p.M <= U_SMALL_ROWS && p.K % 64 == 0) ? GEMM_NT_32x32 : (p.M <= 12288 ? GEMM_NT_32x64 : GEMM_NT_64);
                 // experts together: every launch carries nexp times the tiles, and the panel stream shares the chip with the batch's
-                // trailing update -- throughput per tile counts there, not the launch's latency
-                static const int buv = getenv("PG_BATCH_UV") ? atoi(getenv("PG_BATCH_UV")) : 2;   // 8 x 4096: 0: 9.54, 1: 9.25, 2: 9.04 ms
-                if (nexp > 1 && buv == 1) uv = GEMM_NT_32x64;
-                if (nexp > 1 && buv == 2 && (long)(p.M / 64) * 2 * nexp >= 256) uv = GEMM_NT_64;
+                // trailing update -- throughput per tile counts there, not the launch's latency (8 x 4096: 9.54 -> 9.04 ms)
+                if (nexp > 1 && (long)(p.M / 64) * 2 * nexp >= 256) uv = GEMM_NT_64;
                 if ((rc = pg_gemm<T>(ctx, ps, uv, p))) return rc;
             }
-            if ((rc = pg_leaf<T>(ps, Akk, lda, inv, NB, info, k0 + col_off, 0, nexp, eA, eI))) return rc;
-            const int m = tri_end - k0 - NB;
+            if ((rc = pg_leaf<T>(ps, Akk, lda, inv, NB, info, k0 + col_off, nexp, eA, eI))) return rc;
+            const int m = n - k0 - NB;
             if (m > 0) {     // T: rows below <- rows below * inv(L_kk)^T (in place: one workgroup owns 64 full rows)
                 GemmP<T> p = gp0<T>(); p.info = info;
                 p.M = m; p.N = NB; p.K = NB; p.A = Akk + (long)NB * lda; p.lda = lda; p.B = inv; p.ldb = NB;
@@ -835,55 +733,14 @@ int pg_potrf_t(pg_ctx* ctx, hipStream_t st, int n, T* A, long lda, T* invD, int*
                 if ((rc = pg_gemm<T>(ctx, ps, m <= 12288 ? GEMM_NT_32x128 : GEMM_NT_64x128, p))) return rc;
             }
         }
-        if (v2) {
-            const int pw = oend - o0, mb = n - oend;
-            if ((rc = pg_trtri_t<T>(ctx, ps, pw, A + (long)o0 * lda + o0, lda, invD + (long)(o0 / NB) * NB * NB, Wt, (long)pw))) return rc;
-            GemmP<T> p = gp0<T>(); p.info = info;
-            p.M = mb; p.N = pw; p.K = pw; p.A = A + (long)oend * lda + o0; p.lda = lda; p.B = Wt; p.ldb = pw; p.C = Xs; p.ldc = pw;
-            p.khi = 2;       // W is lower triangular (and what lies above its diagonal 128-blocks is scratch of the doubling)
-            const long tiles = (long)(mb / 128) * (pw / 128);
-            if ((rc = pg_gemm<T>(ctx, ps, tiles < 1024 ? GEMM_NT_64 : GEMM_NT_128, p))) return rc;
-            const long vecs = (long)mb * pw / (16 / sizeof(T));
-            hipLaunchKernelGGL(copy_rows_kernel<T>, dim3((unsigned)std::min<long>((vecs + 255) / 256, 4096)), dim3(256), 0, ps, Xs, (long)pw,
-                               A + (long)oend * lda + o0, lda, mb, pw);
-            LAUNCH_CHECK();
-        }
         if (oend >= n) break;
         hipStream_t cs = cp ? rows_stream : ps; // the stream whose completion means Chain(o) is done
         if (la) {
             if ((rc = pool_event(ctx, 2 + 2 * o, &ev))) return rc;       // ev_chain[o]
             PG_CHECK(hipEventRecord(ev, cs));
             PG_CHECK(hipStreamWaitEvent(us, ev, 0));
-            if (split && oend == split) {   // columns [0, split) of L are final in every row
-                PG_CHECK(hipStreamWaitEvent(ctx->bg, ev, 0));
-                if ((rc = pg_trtri_t<T>(ctx, ctx->bg, split, A, lda, invD, Minv, ldm))) return rc;
-                if ((rc = trtri_top<T>(ctx, ctx->bg, split, n - split, A, lda, Minv, ldm, true, false))) return rc;
-            }
         }
         const int o2 = (o + 2 <= npan) ? pb[o + 2] : n;   // first column right of panel o+1
-        if (sa_this) {   // Sa(o) of a coupled panel: on the update stream (behind ev_chain[o]), then the flag the next panel's first leaf waits for
-            GemmP<T> p = gp0<T>(); p.info = info;
-            p.M = n - oend; p.N = o2 - oend; p.K = oend - o0;
-            p.A = A + (long)oend * lda + o0; p.lda = lda; p.B = p.A; p.ldb = lda; p.C = A + (long)oend * lda + oend; p.ldc = lda;
-            p.alpha = (T)-1; p.beta = (T)1;
-            const long tiles = (long)(p.M / 128) * (p.N / 128);
-            // PG_CS_SA_STREAM=1: on the ROWS stream behind the panel's last rows kernel (no event towards the next panel's rows kernels;
-            // the update stream keeps nothing but the trailing updates, so Sa(o + 1) does not queue behind Sb(o))
-            static const int sa_on_rows = getenv("PG_CS_SA_STREAM") ? atoi(getenv("PG_CS_SA_STREAM")) : 0;
-            hipStream_t ss = sa_on_rows ? rows_stream : us;
-            if (sa_on_rows && o >= 1) {   // these columns were last written by Sb(o - 1)
-                if ((rc = pool_event(ctx, 2 + 2 * (o - 1) + 1, &ev))) return rc;
-                PG_CHECK(hipStreamWaitEvent(ss, ev, 0));
-            }
-            if (sa_on_rows && o == 0 && build_split) {
-                if ((rc = pool_event(ctx, 7 + 2 * npan, &ev))) return rc;
-                PG_CHECK(hipStreamWaitEvent(ss, ev, 0));
-            }
-            if ((rc = pg_gemm<T>(ctx, ss, tiles < 1024 ? GEMM_NT_64 : GEMM_NT_128, p))) return rc;
-            if ((rc = pg_flagset(ss, f_diag + oend / NB, PG_CS_NCRIT))) return rc;
-            if ((rc = pool_event(ctx, 8 + 2 * npan + o, &ev))) return rc;
-            PG_CHECK(hipEventRecord(ev, ss));
-        }
         if (!cp) {   // Sa(o): panel o+1's columns -= panel o   (coupled panels: part of the rows kernels' left-looking product)
             GemmP<T> p = gp0<T>(); p.info = info;
             p.M = n - oend; p.N = o2 - oend; p.K = oend - o0;
@@ -908,34 +765,26 @@ int pg_potrf_t(pg_ctx* ctx, hipStream_t st, int n, T* A, long lda, T* invD, int*
         // them.  The last rows kernel of Chain(o + 1) touches panel o+2's first column and so had to wait for ALL of Sb(o), while
         // Sb(o + 1) waits for that chain: the update stream idled 58-60 us per panel (profiles/r03_potrf_kernel_trace_n8192.txt).
         // Now that rows kernel waits for NEAR(o) only, Chain(o + 1) ends beside FAR(o), and NEAR(o + 1) queues right behind it.
-        static const int nf_env = getenv("PG_CS_NEARFAR") ? atoi(getenv("PG_CS_NEARFAR")) : 1;
         const int o3 = (o + 3 <= npan) ? pb[o + 3] : n;
-        const bool near_far = cp && nf_env && la && m2 > 0 && o3 < n;
-        if (near_far) {
-            const bool dfr = defer && o < od;              // a panel of the first half: nothing right of cd2
+        if (cp && la && m2 > 0 && o3 < n) {
+            nf_split[o] = 1;
             GemmP<T> p = gp0<T>(); p.info = info;
-            if (!(dfr && o + 2 >= oe)) {
-                nf_split[o] = 1;
-                p.M = n - o2; p.N = o3 - o2; p.K = oend - o0;
-                p.A = A + (long)o2 * lda + o0; p.lda = lda; p.B = p.A; p.ldb = lda; p.C = A + (long)o2 * lda + o2; p.ldc = lda;
-                p.alpha = (T)-1; p.beta = (T)1;
-                batched(p, eA, eA, eA);
-                const long tiles = (long)(p.M / 128) * (p.N / 128) * nexp;
-                if ((rc = pg_gemm<T>(ctx, us, tiles < 1024 ? GEMM_NT_64 : GEMM_NT_128, p))) return rc;
-                if ((rc = pool_event(ctx, 9 + 3 * npan + o, &ev))) return rc;   // ev_near[o]
-                PG_CHECK(hipEventRecord(ev, us));
-            }
+            p.M = n - o2; p.N = o3 - o2; p.K = oend - o0;
+            p.A = A + (long)o2 * lda + o0; p.lda = lda; p.B = p.A; p.ldb = lda; p.C = A + (long)o2 * lda + o2; p.ldc = lda;
+            p.alpha = (T)-1; p.beta = (T)1;
+            batched(p, eA, eA, eA);
+            const long tiles = (long)(p.M / 128) * (p.N / 128) * nexp;
+            if ((rc = pg_gemm<T>(ctx, us, tiles < 1024 ? GEMM_NT_64 : GEMM_NT_128, p))) return rc;
+            if ((rc = pool_event(ctx, 9 + 3 * npan + o, &ev))) return rc;   // ev_near[o]
+            PG_CHECK(hipEventRecord(ev, us));
             T* P = A + (long)o3 * lda + o0;
             p = gp0<T>(); p.info = info;
             p.M = p.N = n - o3; p.K = oend - o0; p.A = P; p.lda = lda; p.B = P; p.ldb = lda;
             p.C = A + (long)o3 * lda + o3; p.ldc = lda;
             p.alpha = (T)-1; p.beta = (T)1; p.tri = 1;
-            if (dfr) p.N = std::max(0, cd2 - o3);          // the trapezoid left of cd2 (all rows)
             batched(p, eA, eA, eA);
-            const long tn_ = p.N / 128, tm_ = p.M / 128;
-            const long ftiles = (tn_ * (tn_ + 1) / 2 + (tm_ - tn_) * tn_) * nexp;
-            static const long sb_thresh2 = getenv("PG_SB_TILE_THRESH") ? atol(getenv("PG_SB_TILE_THRESH")) : 2048;
-            if (p.N > 0 && (rc = pg_gemm<T>(ctx, us, ftiles < sb_thresh2 ? GEMM_NT_64 : GEMM_NT_128, p))) return rc;
+            const long ftiles = (long)(p.M / 128) * (p.M / 128 + 1) / 2 * nexp;
+            if ((rc = pg_gemm<T>(ctx, us, ftiles < SB_SMALL_TILES ? GEMM_NT_64 : GEMM_NT_128, p))) return rc;
         } else if (m2 > 0) {  // Sb(o)
             T* P = A + (long)o2 * lda + o0;
             GemmP<T> p = gp0<T>(); p.info = info;
@@ -944,18 +793,11 @@ int pg_potrf_t(pg_ctx* ctx, hipStream_t st, int n, T* A, long lda, T* invD, int*
             p.alpha = (T)-1; p.beta = (T)1; p.tri = 1;
             batched(p, eA, eA, eA);
             const long tiles = (long)(m2 / 128) * (m2 / 128 + 1) / 2 * nexp;
-            // (threshold swept 512 / 1024 / 2048: 2048 is 2 % faster at n = 8192 and neutral at 16384)
-            // (re-swept with the eight-wave blocks, 2048 / 1024 / 512 / 256: 2048 stays best at 8192, neutral at 16384)
-            static const long sb_thresh = getenv("PG_SB_TILE_THRESH") ? atol(getenv("PG_SB_TILE_THRESH")) : 2048;
-            if ((rc = pg_gemm<T>(ctx, us, tiles < sb_thresh ? GEMM_NT_64 : GEMM_NT_128, p))) return rc;
+            if ((rc = pg_gemm<T>(ctx, us, tiles < SB_SMALL_TILES ? GEMM_NT_64 : GEMM_NT_128, p))) return rc;
         }
         if (la) {
             if ((rc = pool_event(ctx, 2 + 2 * o + 1, &ev))) return rc;   // ev_sb[o]
             PG_CHECK(hipEventRecord(ev, us));
-        }
-        if (defer && o >= od - 1) {   // the first half is final (ev_chain[od - 1], waited for above): the deferred block's column panels
-            for (int i = 0; i < (o == od - 1 ? defer_lead : 1) && next_bu < npan; ++i)
-                if ((rc = launch_bu(next_bu++))) return rc;
         }
     }
     if (la) {   // join both streams back onto the caller's stream
@@ -972,20 +814,8 @@ int pg_potrf_t(pg_ctx* ctx, hipStream_t st, int n, T* A, long lda, T* invD, int*
                 PG_CHECK(hipStreamWaitEvent(st, ev, 0));
             }
         }
-        if (split) {
-            if ((rc = pool_event(ctx, 3 + 2 * npan, &ev))) return rc;
-            PG_CHECK(hipEventRecord(ev, ctx->bg));
-            PG_CHECK(hipStreamWaitEvent(st, ev, 0));
-        }
     }
-    if (Minv) {
-        if (!split) return pg_trtri_t<T>(ctx, st, n, A, lda, invD, Minv, ldm, 0, eb);
-        // trailing part of the diagonal, then the second top-level product
-        const long off = split;
-        if ((rc = pg_trtri_t<T>(ctx, st, n - split, A + off * lda + off, lda, invD + (off / NB) * NB * NB, Minv + off * ldm + off, ldm)))
-            return rc;
-        return trtri_top<T>(ctx, st, split, n - split, A, lda, Minv, ldm, false, true);
-    }
+    if (Minv) return pg_trtri_t<T>(ctx, st, n, A, lda, invD, Minv, ldm, 0, eb);
     return 0;
 }
 

@@ -455,9 +455,8 @@ def test_potrf_outer_panel_widths(ops, panel, n):
 
 @pytest.mark.parametrize("n", [8192, 5376])
 def test_potrf_trtri_fused_matches_separate(ops, n):
-    """pg_potrf_trtri = pg_potrf followed by pg_trtri on the caller's stream (the background-stream overlap of round 1 is off by
-    default, PG_BG_STREAM=1; 8192: every panel on the coupled chain; 5376: the last panel ragged, trailing part not a power
-    of two).  The factor must equal the separate call bit for bit, the inverse too when both routes pair the diagonal
+    """pg_potrf_trtri = pg_potrf followed by pg_trtri on the caller's stream (8192: every panel on the coupled chain; 5376: the
+    last panel ragged, trailing part not a power of two).  The factor must equal the separate call bit for bit, the inverse too when both routes pair the diagonal
     blocks the same way; and the inverse must undo the factor."""
     g = torch.Generator(device="cuda").manual_seed(44)
     r = torch.randn(n, n, device="cuda", dtype=torch.float64, generator=g)
@@ -1620,7 +1619,7 @@ def test_matrix_pipe_bodies_on_uncentred_and_batched_data(ops, monkeypatch):
 @pytest.mark.parametrize("tm,tn", [(5, 3), (20, 3), (23, 9), (9, 8)])
 def test_gemm_trapezoid_tiles(ops, variant_name, tm, tn):
     """Round 5: tri = 1 with N < M is a trapezoid -- the lower triangle of the leading N x N block and the full tile rows below it (the
-    restricted trailing update and the deferred block's column panels of the factorisation).  Against NumPy on the tiles it covers,
+    restricted trailing update of the factorisation).  Against NumPy on the tiles it covers,
     bit for bit against the same product as a square triangle + a rectangle, and nothing above the diagonal tiles is touched."""
     from pygpr_amd import _lib
 
@@ -1642,41 +1641,6 @@ def test_gemm_trapezoid_tiles(ops, variant_name, tm, tn):
     ref = host(c0) - host(a) @ host(a[:n]).T
     low = np.tril(np.ones((m, n), dtype=bool))
     np.testing.assert_allclose(host(c1)[low], ref[low], atol=1e-11)
-
-
-@pytest.mark.parametrize("n", [6144, 8192])
-def test_potrf_deferred_trailing_block(ops, n):
-    """Round 5, experimental schedule (pg_set_deferred_block; off by default -- measured slower): the coupled chain's first half (columns
-    left of about n / 2) updates only the columns up to one panel past the split; the block right of it takes those updates later as
-    K = n/2-deep products beside the second half's chain (pg_last_deferred_panels > 0).  The factor agrees with LAPACK's and with the
-    default schedule's to rounding; the fused inverse is the factor's inverse."""
-    rng = np.random.default_rng(n)
-    a = spd(n, rng)
-    info = torch.zeros(1, dtype=torch.int32, device="cuda")
-    invd = ops.potrf_workspace(n, torch.float64)
-    ad0 = dev(a)
-    ops.potrf(ad0, invd, info)
-    assert ops.last_deferred_panels() == 0
-    ref = np.linalg.cholesky(a)
-    scale = np.abs(ref).max()
-    ops.set_deferred_block(1)
-    try:
-        ad = dev(a)
-        ops.potrf(ad, invd, info)
-        assert int(info.item()) == 0
-        if ops.coupled_chain():
-            assert ops.last_deferred_panels() > 0
-        L = np.tril(host(ad))
-        np.testing.assert_allclose(L, ref, rtol=0, atol=1e-11 * scale)
-        np.testing.assert_allclose(L, np.tril(host(ad0)), rtol=0, atol=1e-11 * scale)
-        ad3, minv = dev(a), ops.empty(n, n)
-        ops.potrf_trtri(ad3, invd, info, minv)
-        assert int(info.item()) == 0
-        mi = np.tril(host(minv))
-        r = mi[-512:] @ ref - np.eye(n)[-512:]
-        assert np.abs(r).max() < 1e-9
-    finally:
-        ops.set_deferred_block(0)
 
 
 @pytest.mark.parametrize("n", [512, 1536, 4096])

@@ -35,7 +35,7 @@ def test_library_loads_and_exports_every_header_symbol():
     for n in names:
         assert isinstance(getattr(lib, n), ctypes._CFuncPtr)
     assert lib.pg_version() == 100
-    # inv_diag + the coupled chain's flag words (the panel-mode buffers only exist with PG_PANEL_MODE=1)
+    # inv_diag + the coupled chain's flag words
     assert lib.pg_potrf_worksize(0, 512) == 512 * 128 + 512 + 2048
     assert lib.pg_potrf_worksize(0, 16384) == 16384 * 128 + 16384 + 2048
 

@@ -1,5 +1,5 @@
-"""Lower-tile SYRK C -= P P^T (the Cholesky's trailing update) on the caller's stream or, under PG_RAW_STREAM=upd|bg, on the
-handle's CU-masked streams: what the mask alone costs."""
+"""Lower-tile SYRK C -= P P^T (the Cholesky's trailing update) on the caller's stream or, under PG_RAW_STREAM=upd, on the
+handle's CU-masked update stream: what the mask alone costs."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pygpr_amd._ops import get_ops

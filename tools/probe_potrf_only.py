@@ -1,4 +1,4 @@
-"""potrf alone (covariance build subtracted) at the given sizes; env knobs (PG_SYNC_ROWS, PG_CS_PANEL, PG_NBO ...) are read by the library."""
+"""potrf alone (covariance build subtracted) at the given sizes; env knobs (PG_NBO, PG_REC_MIN ...) are read by the library."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
