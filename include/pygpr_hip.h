@@ -33,6 +33,8 @@ extern "C" {
 #define PG_KIND_MATERN52 1 /* new (not in the reference), same hp layout */
 #define PG_KIND_SQDIST 2   /* pg_kernel_build only: the scaled squared distance itself, sum_k l_k^2 (x_k - x'_k)^2 --
                               Squared_exponential.distance (covar.py:102-127) when l = 1 */
+#define PG_KIND_MATERN32 3 /* new (not in the reference), same hp layout: sigma^2 (1 + sqrt3 r) exp(-sqrt3 r) */
+#define PG_KIND_MATERN12 4 /* new (not in the reference), same hp layout: sigma^2 exp(-r) (exponential / Ornstein-Uhlenbeck) */
 #define PG_MAX_COMP 4
 #define PG_MAX_DIM 64
 

@@ -8,6 +8,7 @@ Same names, hyper-parameter layout and shapes as the reference:
   * `Compose`              sum of children, hp concatenated in list order, dK concatenated on dim -3
                            (covar.py:28-81)
   * `Matern52`             NEW (no reference counterpart), same hp layout as the SE.
+  * `Matern32`, `Matern12` NEW, the rest of the Matern family (nu = 3/2 and 1/2, the exponential kernel), same hp layout.
 Leading batch dims on hp and/or x follow the reference's flatten-to-one-batch-dim rule.  Tensors come
 back on the device of `x` (CPU in -> CPU out); the arithmetic always runs on the GPU in the dtype of
 `x` (float64, or float32 as an explicit opt-in) -- unlike the reference, nothing here touches torch's
@@ -182,6 +183,19 @@ class Matern52(Squared_exponential):
     K = sig^2 (1 + sqrt5 r + 5 r^2/3) exp(-sqrt5 r).  Not in the reference."""
 
     _kind = _lib.PG_KIND_MATERN52
+
+
+class Matern32(Squared_exponential):
+    """Matern-3/2 with the SE parameterisation: r = |(x-x').ls|, K = sig^2 (1 + sqrt3 r) exp(-sqrt3 r)."""
+
+    _kind = _lib.PG_KIND_MATERN32
+
+
+class Matern12(Squared_exponential):
+    """Matern-1/2 (the exponential / Ornstein-Uhlenbeck kernel) with the SE parameterisation: r = |(x-x').ls|,
+    K = sig^2 exp(-r).  dK/dl_k = -sig^2 exp(-r) l_k (x_k-x'_k)^2 / r, 0 at r = 0 (its limit)."""
+
+    _kind = _lib.PG_KIND_MATERN12
 
 
 class White_noise(_DeviceKernel):

@@ -2,7 +2,7 @@
 //
 // pg_kbuild: K[i][j] = sum_c k_c(r_i, c_j) (+ (sum sigma_n^2 + jitter) on the diagonal of a symmetric
 // build); k_c is the ARD squared exponential of PyGPR/covar.py:129-167 (hp = [sigma, l_1..l_d], l are
-// INVERSE length scales, no 1/2 in the exponent) or Matern-5/2 with the same hp layout.  Distances are
+// INVERSE length scales, no 1/2 in the exponent) or Matern-5/2, -3/2, -1/2 with the same hp layout.  Distances are
 // direct sums of squared differences (exactly symmetric, never negative) instead of the reference's
 // GEMM expansion (covar.py:102-127).  One 64x64 output tile per 256-thread workgroup; both point tiles
 // are staged in LDS k-major ([d][64]); each thread owns a 4x4 micro-tile whose columns are two 16-byte
@@ -12,7 +12,8 @@
 //
 // pg_nlml_grad: g_k = 1/2 sum_ij (K^-1 - a a^T)_ij dK_ij/dtheta_k over the lower triangle, with dK
 // recomputed from the point tiles on the fly: dK/dsigma = 2K/sigma, dK/dl_k = -2 l_k D_k^2 K
-// (covar.py:169-206), dK/dsigma_n = 2 sigma_n I (covar.py:247-269).  The reference materialises
+// (covar.py:169-206), dK/dsigma_n = 2 sigma_n I (covar.py:247-269); the Matern kinds as dK/dl_k = coef base l_k D_k^2
+// (kind_hcoef: coef / 2).  The reference materialises
 // dK[nhp,n,n] and solves against it (loss.py:116-121); this is the same number by the K^-1 route.
 #include "kbuild.h"
 #include "kfun.h"
@@ -29,9 +30,44 @@ template <> struct VecOf<float> { typedef float type __attribute__((ext_vector_t
 template <typename T> __device__ __forceinline__ T comp_value(int kind, T sig2, T sqd) {
     if (kind == PG_KIND_RBF) return sig2 * pg_exp(-sqd);
     if (kind == PG_KIND_SQDIST) return sqd;    // Squared_exponential.distance (covar.py:102-127): the scaled squared distance itself
-    const T s5 = (T)2.23606797749978969641;
     const T r = sqrt(sqd);
+    if (kind == PG_KIND_MATERN12) return sig2 * pg_exp(-r);
+    if (kind == PG_KIND_MATERN32) {
+        const T s3 = (T)1.73205080756887729353;
+        return sig2 * ((T)1 + s3 * r) * pg_exp(-s3 * r);
+    }
+    const T s5 = (T)2.23606797749978969641;
     return sig2 * ((T)1 + s5 * r + (T)(5.0 / 3.0) * sqd) * pg_exp(-s5 * r);
+}
+
+// Half the factor `coef` of the length-scale derivative dK/dl_k = coef base l_k D_k^2, per stationary kind (base: see pg_grad_kernel)
+__device__ __forceinline__ double kind_hcoef(int kind) {
+    if (kind == PG_KIND_RBF) return -1.0;
+    if (kind == PG_KIND_MATERN52) return 0.5 * -(5.0 / 3.0);
+    if (kind == PG_KIND_MATERN32) return -1.5;
+    return -0.5;                               // PG_KIND_MATERN12
+}
+
+// Covariance value kv and the factor `base` of dK/dl_k for a Matern kind from the scaled squared distance (direct differences: the
+// Matern-1/2 factor 1/r is only formed from an exact sq, so it is bounded by |D_k| after the multiplication by l_k D_k^2; 0 at sq = 0,
+// the derivative's limit there).
+template <typename T> __device__ __forceinline__ void matern_val(int kind, T sig2, T sq, T& kv, T& base) {
+    const T rr = sqrt(sq);
+    if (kind == PG_KIND_MATERN12) {
+        const T ex = sig2 * pg_exp(-rr);
+        kv = ex;
+        base = sq == (T)0 ? (T)0 : ex / rr;
+    } else if (kind == PG_KIND_MATERN32) {
+        const T s3 = (T)1.73205080756887729353;
+        const T ex = pg_exp(-s3 * rr);
+        kv = sig2 * ((T)1 + s3 * rr) * ex;
+        base = sig2 * ex;
+    } else {                                   // PG_KIND_MATERN52
+        const T s5 = (T)2.23606797749978969641;
+        const T ex = pg_exp(-s5 * rr);
+        kv = sig2 * ((T)1 + s5 * rr + (T)(5.0 / 3.0) * sq) * ex;
+        base = sig2 * ((T)1 + s5 * rr) * ex;
+    }
 }
 
 template <typename T>
@@ -164,11 +200,21 @@ __device__ __forceinline__ void kb_body(const pg_covspec& spec, const T* xr, con
             for (int r = 0; r < 4; ++r)
 #pragma unroll
                 for (int c = 0; c < 4; ++c) out[r][c] += sq[r][c];
-        } else {
+        } else if (kind == PG_KIND_MATERN52) {
 #pragma unroll
             for (int r = 0; r < 4; ++r)
 #pragma unroll
                 for (int c = 0; c < 4; ++c) out[r][c] += comp_value<T>(PG_KIND_MATERN52, s2, sq[r][c]);
+        } else if (kind == PG_KIND_MATERN32) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) out[r][c] += comp_value<T>(PG_KIND_MATERN32, s2, sq[r][c]);
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) out[r][c] += comp_value<T>(PG_KIND_MATERN12, s2, sq[r][c]);
         }
     }
     const T dg = sg2[PG_MAX_COMP];
@@ -397,11 +443,13 @@ int pg_kbuild(hipStream_t st, const pg_covspec& spec, const double* hp, const T*
     static const int fast_env = getenv("PG_KB_FAST") ? atoi(getenv("PG_KB_FAST")) : 1;
     const int presc = (presc_env && spec.ncomp == 1) ? ((fast_env && sizeof(T) == 8 && spec.kind[0] == PG_KIND_RBF && !accumulate) ? 2 : 1) : 0;
     // One stationary component, d <= 16, no accumulate pass: the distance on the matrix pipe (kmfma.hip).  PG_KB_MFMA = 0: never;
-    // 1 (default): wherever the VALU bodies have no fast form -- d > 8, Matern-5/2, fp32; 2: also for the fp64 squared exponential at
+    // 1 (default): wherever the VALU bodies have no fast form -- d > 8, Matern-5/2 and -3/2, fp32; 2: also for the fp64 squared exponential at
     // d <= 8, which the fast body of round 3 serves at 0.63-0.66 of the HBM peak.
     const int mfma_env = getenv("PG_KB_MFMA") ? atoi(getenv("PG_KB_MFMA")) : 1;      // (read per call: tests compare the bodies in one process)
     // (mirrored, lower-only and cross builds of one (kind, dtype, d) all take the same body: their values agree bit for bit)
-    if (mfma_env && spec.ncomp == 1 && !accumulate && d <= 16 && (spec.kind[0] == PG_KIND_RBF || spec.kind[0] == PG_KIND_MATERN52) &&
+    // (Matern-1/2 never: it is 1 - r near 0, so the expansion's error in sq reaches K as its square root -- DESIGN.md)
+    if (mfma_env && spec.ncomp == 1 && !accumulate && d <= 16 &&
+        (spec.kind[0] == PG_KIND_RBF || spec.kind[0] == PG_KIND_MATERN52 || spec.kind[0] == PG_KIND_MATERN32) &&
         (mfma_env >= 2 || presc != 2 || d > 8))
         return pg_kbuild_mfma<T>(st, spec, hp, Xr, ldr, nr, Xc, ldc, nc, d, symmetric, mirror ? 1 : 0, jitter, K, ldk, c0, c1, S, strips, nexp, eX,
                                  ehp, eK, eXr);
@@ -468,11 +516,8 @@ __global__ __launch_bounds__(256) void pg_kgrad_kernel(pg_covspec spec, const do
             base = kv;
             coef = (T)-2;
         } else {
-            const T s5 = (T)2.23606797749978969641;
-            const T rr = sqrt(sq), ex = pg_exp(-s5 * rr);
-            kv = (T)(sg * sg) * ((T)1 + s5 * rr + (T)(5.0 / 3.0) * sq) * ex;
-            base = (T)(sg * sg) * ((T)1 + s5 * rr) * ex;
-            coef = (T)(-5.0 / 3.0);
+            matern_val<T>(spec.kind[cp], (T)(sg * sg), sq, kv, base);
+            coef = (T)(2.0 * kind_hcoef(spec.kind[cp]));
         }
         dK[(long)o * slab + e] = kv * (T)(2.0 / sg);
         for (int k = 0; k < d; ++k) {
@@ -628,10 +673,10 @@ __global__ __launch_bounds__(256) void pg_grad_kernel(pg_covspec spec, const dou
                     kv = (double)(sig2 * pg_exp(-sq));
                     base = kv;
                 } else {
-                    const T s5 = (T)2.23606797749978969641;
-                    const T rr = sqrt(sq), ex = pg_exp(-s5 * rr);
-                    kv = (double)(sig2 * ((T)1 + s5 * rr + (T)(5.0 / 3.0) * sq) * ex);
-                    base = (double)(sig2 * ((T)1 + s5 * rr) * ex);
+                    T kt, bt;
+                    matern_val<T>(kind, sig2, sq, kt, bt);
+                    kv = (double)kt;
+                    base = (double)bt;
                 }
                 acc[0] += w * kv;
                 const double wb = w * base;
@@ -813,10 +858,10 @@ __global__ __launch_bounds__(256) void pg_grad_reduce_kernel(pg_covspec spec, co
             const int o = spec.off[c];
             if (p == o) { scale = 0.5 * 2.0 / hp[o]; mine = true; }       // dK/dsigma = 2K/sigma
             else if (p > o && p <= o + d) {
-                scale = (spec.kind[c] == PG_KIND_RBF) ? 0.5 * -2.0 * hp[p]   // -2 l_k D_k^2 K
-                                                      : 0.5 * -(5.0 / 3.0) * hp[p];
+                const double hc = kind_hcoef(spec.kind[c]);      // SE: -2 l_k D_k^2 K, Matern: coef base l_k D_k^2
+                scale = hc * hp[p];
                 // the fast contraction summed (l_k D_k)^2: -l_k S = -S' / l_k (l_k = 0: S' = 0 and the derivative is 0)
-                if (presc) scale = hp[p] != 0.0 ? ((spec.kind[c] == PG_KIND_RBF) ? -1.0 : -5.0 / 6.0) / hp[p] : 0.0;
+                if (presc) scale = hp[p] != 0.0 ? hc / hp[p] : 0.0;
                 mine = true;
             }
         }
@@ -855,7 +900,9 @@ int pg_nlml_grad_t(hipStream_t st, const pg_covspec& spec, const double* hp, con
     static const int fast_env = getenv("PG_GRAD_FAST") ? atoi(getenv("PG_GRAD_FAST")) : 1;
     // One stationary component, d <= 16: the contraction on the matrix pipe (kmfma.hip; PG_GRAD_MFMA=0 restores the VALU kernels)
     const int mfma_env = getenv("PG_GRAD_MFMA") ? atoi(getenv("PG_GRAD_MFMA")) : 1;   // (read per call: tests compare the bodies in one process)
-    if (mfma_env && spec.ncomp == 1 && d <= 16 && n >= 1 && (spec.kind[0] == PG_KIND_RBF || spec.kind[0] == PG_KIND_MATERN52)) {
+    // (not Matern-1/2: its factor e^-r / r is unbounded near r = 0, and the expansion's cancellation error is u |x|^2 sum |G| -- DESIGN.md)
+    if (mfma_env && spec.ncomp == 1 && d <= 16 && n >= 1 &&
+        (spec.kind[0] == PG_KIND_RBF || spec.kind[0] == PG_KIND_MATERN52 || spec.kind[0] == PG_KIND_MATERN32)) {
         int nblk = 0;
         if ((rc = pg_grad_mfma<T>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp, &nblk))) return rc;
         hipLaunchKernelGGL(pg_grad_reduce_kernel, dim3(nhp, 1, nexp), dim3(256), 0, st, spec, hp, work, nblk, nhp, d, grad, 1, gb);

@@ -15,8 +15,9 @@
 //
 // a = (x - x_0) l: coordinates relative to the first point (stationary kernels do not care; the expansion's absolute error is
 // eps |a|^2, so uncentred data would lose digits) times the inverse length scales.  What stays on the VALU is what is per ELEMENT:
-// the exponential, the weight, the clamp -- about 25 operations, independent of d.  One stationary component (+ white noise), d <= 16;
-// everything else keeps the kernels of kbuild.hip.  PG_KB_MFMA=0 / PG_GRAD_MFMA=0 switch back.
+// the exponential, the weight, the clamp -- about 25 operations, independent of d.  One stationary component (+ white noise), d <= 16,
+// of the kinds with a body here (squared exponential, Matern-5/2, Matern-3/2: all 1 - O(r^2) near r = 0, so the expansion's error in sq
+// enters K linearly); everything else -- Matern-1/2 among it -- keeps the kernels of kbuild.hip.  PG_KB_MFMA=0 / PG_GRAD_MFMA=0 switch back.
 #include "kbuild.h"
 #include "kfun.h"
 #include "kmfma.h"
@@ -91,6 +92,27 @@ template <> struct KmVal<float, PG_KIND_MATERN52> {
         kv = base + (5.0f / 3.0f) * sq * e;
     }
 };
+// Matern-3/2: K = sigma^2 (1 + sqrt3 r) e^(-sqrt3 r), base = sigma^2 e^(-sqrt3 r) (coef -3)
+template <> struct KmVal<double, PG_KIND_MATERN32> {
+    static __device__ __forceinline__ void run(double sq, double sig2, const double* tab, double& kv, double& base) {
+        (void)sig2;
+        const double s3 = 1.73205080756887729353;
+        const double r = pg_sqrt_pos(sq), e = pg_exp_tab(-s3 * r, tab);
+        base = e;
+        kv = s3 * r * e + e;
+    }
+};
+template <> struct KmVal<float, PG_KIND_MATERN32> {
+    static __device__ __forceinline__ void run(float sq, float sig2, const double*, float& kv, float& base) {
+        const float s3 = 1.7320508076f;
+        const float r = km_sqrtf(sq), e = sig2 * km_expf(-s3 * r);
+        base = e;
+        kv = s3 * r * e + e;
+    }
+};
+template <int KIND> struct KmHasBody {
+    static constexpr bool value = KIND == PG_KIND_RBF || KIND == PG_KIND_MATERN52 || KIND == PG_KIND_MATERN32;
+};
 
 // ------------------------------------------------------------------------------------------------
 // covariance build: symmetric lower-only builds and cross builds of ONE stationary component (+ white noise on the diagonal)
@@ -106,6 +128,7 @@ __global__ __launch_bounds__(256) void pg_kbuild_mfma_kernel(pg_covspec spec, co
                                                              int nr, const T* __restrict__ Xc, long ldc, int nc, int d, int symmetric,
                                                              double jitter, T* __restrict__ K, long ldk, int ctile0, int ctile1, int S,
                                                              long eX, long ehp, long eK, long eXr) {
+    static_assert(KmHasBody<KIND>::value, "no matrix-pipe body for this kind");
     typedef PtTile<T, DP> PT;
     typedef typename Mfma<T>::acc_t acc_t;
     constexpr int LDP = PT::LDP, NS = DP / 4;
@@ -207,18 +230,23 @@ int pg_kbuild_mfma(hipStream_t st, const pg_covspec& spec, const double* hp, con
                    int symmetric, int mirror, double jitter, T* K, long ldk, int c0, int c1, int S, long strips, int nexp, long eX, long ehp,
                    long eK, long eXr) {
     const int kind = spec.kind[0];
+    if (kind != PG_KIND_RBF && kind != PG_KIND_MATERN52 && kind != PG_KIND_MATERN32) {
+        pg_set_error("pg_kbuild: no matrix-pipe body for kernel kind %d", kind);
+        return -2;
+    }
 #define KB_ARGS st, spec, hp, Xr, ldr, nr, Xc, ldc, nc, d, symmetric, jitter, K, ldk, c0, c1, S, strips, nexp, eX, ehp, eK, eXr
+#define KB_KIND(DP, KIND) return mirror ? kb_mfma_launch<T, DP, KIND, true>(KB_ARGS) : kb_mfma_launch<T, DP, KIND, false>(KB_ARGS)
 #define KB_GO(DP)                                                                                                          \
     do {                                                                                                                   \
-        if (kind == PG_KIND_RBF) return mirror ? kb_mfma_launch<T, DP, PG_KIND_RBF, true>(KB_ARGS)                         \
-                                               : kb_mfma_launch<T, DP, PG_KIND_RBF, false>(KB_ARGS);                       \
-        return mirror ? kb_mfma_launch<T, DP, PG_KIND_MATERN52, true>(KB_ARGS)                                             \
-                      : kb_mfma_launch<T, DP, PG_KIND_MATERN52, false>(KB_ARGS);                                           \
+        if (kind == PG_KIND_RBF) KB_KIND(DP, PG_KIND_RBF);                                                                 \
+        if (kind == PG_KIND_MATERN52) KB_KIND(DP, PG_KIND_MATERN52);                                                       \
+        KB_KIND(DP, PG_KIND_MATERN32);                                                                                     \
     } while (0)
     if (d <= 4) KB_GO(4);
     if (d <= 8) KB_GO(8);
     KB_GO(16);
 #undef KB_GO
+#undef KB_KIND
 #undef KB_ARGS
 }
 template int pg_kbuild_mfma<double>(hipStream_t, const pg_covspec&, const double*, const double*, long, int, const double*, long, int, int, int, int,
@@ -239,6 +267,7 @@ template <typename T, int DP, int KIND, bool GRIDX_COL = true>
 __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void pg_grad_mfma_kernel(pg_covspec spec, const double* __restrict__ hp, const T* __restrict__ X, long ldx, int n,
                                                            int d, const T* __restrict__ Kinv, long ldk, const T* __restrict__ alpha,
                                                            double* __restrict__ part, int nhp, GradBatch gb, int gch) {
+    static_assert(KmHasBody<KIND>::value, "no matrix-pipe body for this kind");
     typedef PtTile<T, DP> PT;
     typedef typename Mfma<T>::acc_t acc_t;
     constexpr int LDP = PT::LDP, NS = DP / 4;
@@ -377,6 +406,15 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void pg_grad_mfma_kern
                             const f2 t = sq * -1.44269504088896341f;
                             const f2 e = {__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
                             kv = base = e * (float)sig2x2;
+                        } else if (KIND == PG_KIND_MATERN32) {
+                            sq.x = sq.x < 0.0f ? 0.0f : sq.x;                          // (select, not max: a NaN stays a NaN)
+                            sq.y = sq.y < 0.0f ? 0.0f : sq.y;
+                            const f2 rr = {__builtin_amdgcn_sqrtf(sq.x), __builtin_amdgcn_sqrtf(sq.y)};
+                            const f2 t = rr * (-1.7320508076f * 1.44269504088896341f);
+                            f2 e = {__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
+                            e = e * (float)sig2x2;
+                            base = e;
+                            kv = rr * 1.7320508076f * e + e;
                         } else {
                             sq = __builtin_elementwise_max(sq, (f2){0.0f, 0.0f});
                             const f2 rr = {__builtin_amdgcn_sqrtf(sq.x), __builtin_amdgcn_sqrtf(sq.y)};
@@ -501,14 +539,22 @@ int pg_grad_mfma(hipStream_t st, const pg_covspec& spec, const double* hp, const
     const int gch = gch_env > 0 ? std::min(gch_env, 64) : std::max(2, std::min(tiles / 16, 32));
     *nblk = tiles * ((tiles + gch - 1) / gch);
     const int kind = spec.kind[0];
+    if (kind != PG_KIND_RBF && kind != PG_KIND_MATERN52 && kind != PG_KIND_MATERN32) {
+        pg_set_error("pg_nlml_grad: no matrix-pipe body for kernel kind %d", kind);
+        return -2;
+    }
+#define GR_KIND(DP, KIND) return grad_mfma_launch<T, DP, KIND>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, part, nhp, tiles, gb, nexp, gch)
 #define GR_GO(DP)                                                                                                                          \
-    return kind == PG_KIND_RBF                                                                                                             \
-               ? grad_mfma_launch<T, DP, PG_KIND_RBF>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, part, nhp, tiles, gb, nexp, gch)       \
-               : grad_mfma_launch<T, DP, PG_KIND_MATERN52>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, part, nhp, tiles, gb, nexp, gch)
-    if (d <= 4) { GR_GO(4); }
-    if (d <= 8) { GR_GO(8); }
+    do {                                                                                                                                   \
+        if (kind == PG_KIND_RBF) GR_KIND(DP, PG_KIND_RBF);                                                                                 \
+        if (kind == PG_KIND_MATERN52) GR_KIND(DP, PG_KIND_MATERN52);                                                                       \
+        GR_KIND(DP, PG_KIND_MATERN32);                                                                                                     \
+    } while (0)
+    if (d <= 4) GR_GO(4);
+    if (d <= 8) GR_GO(8);
     GR_GO(16);
 #undef GR_GO
+#undef GR_KIND
 }
 template int pg_grad_mfma<double>(hipStream_t, const pg_covspec&, const double*, const double*, long, int, int, const double*, long, const double*,
                                   double*, int, int, const GradBatch&, int, int*);
