@@ -208,6 +208,30 @@ int pg_nlml_grad_batched(pg_handle h, int dtype, const pg_covspec* spec, const d
                          int n, int d, const void* Kinv, long ldk, long k_stride, const void* alpha, long alpha_stride, double* grad,
                          long grad_stride, int nhp, double* work, long lwork, int nexp, void* stream);
 
+/* Derivatives of a prediction with respect to the test points (the reference's predict, gpr.py:76-120, has none): for expert e
+ *   out_u[p][k] (+)= sum_i u_i  dk(Xq_p, Z_i) / dXq_pk        (u != NULL)
+ *   out_b[p][k] (+)= sum_i B_pi dk(Xq_p, Z_i) / dXq_pk        (B != NULL; both given: one pass over the pairs for both)
+ * with dk/dx_pk = 2 c base(r) l_k^2 (Xq_pk - Z_ik), summed over the stationary children of spec (white noise has no cross term):
+ * -2 k l_k^2 D_k (squared exponential), -5/3 s^2 (1 + sqrt5 r) e^-sqrt5 r l_k^2 D_k (Matern-5/2), -3 s^2 e^-sqrt3 r l_k^2 D_k
+ * (Matern-3/2), -s^2 e^-r / r l_k^2 D_k (Matern-1/2).  Matern-1/2 has no derivative where a test point meets a training point (r = 0):
+ * that pair contributes 0, the library's convention for its base (as in pg_nlml_grad).
+ * With alpha = K^-1 y and V = K* K^-1 (m x n) the derivatives of gpr.py:80-85 (mean), 98-104 (diagonal variance) and 108-120 (full
+ * covariance, with G the upstream gradient and S = G + G^T) are
+ *   d mean_p / dx*_p = out_u with u = alpha, Z = x;   d var_p / dx*_p = -2 out_b with B = V, Z = x;
+ *   dL / dx*_p = out_b(B = S, Z = x*) - out_b(B = S V, Z = x).
+ * Xq [m x d] (ldq), Z [n x d] (ldz; may be Xq), u [n], B [m x n] row-major with leading dimension ldb, or (trans_b != 0) stored
+ * transposed, B[i * ldb + p]; out_u / out_b [m x d] with leading dimensions ldou / ldob, in the model's dtype.  Rows of B and entries of
+ * u beyond m / n are never read.  accumulate != 0 adds to the outputs (a further pass of a Compose longer than PG_MAX_COMP).
+ * Batched experts: expert e reads hp + e * hp_stride, Xq + e * xq_stride, Z + e * z_stride, u + e * u_stride, B + e * b_stride and
+ * writes out_u + e * ou_stride, out_b + e * ob_stride (elements; a stride of 0 shares an operand, never an output).
+ * Direct differences, fp64 accumulation for both dtypes; a NaN coordinate of a test point gives NaN in that row only.
+ * work: pg_kernel_xgrad_worksize(h, m, n, d, nexp) doubles (the partial sums of the chunks the training points are split into). */
+long pg_kernel_xgrad_worksize(pg_handle h, int m, int n, int d, int nexp);
+int pg_kernel_xgrad(pg_handle h, int dtype, const pg_covspec* spec, const double* hp, long hp_stride, const void* Xq, long ldq, long xq_stride,
+                    int m, const void* Z, long ldz, long z_stride, int n, int d, const void* u, long u_stride, void* out_u, long ldou,
+                    long ou_stride, const void* B, long ldb, long b_stride, int trans_b, void* out_b, long ldob, long ob_stride, int accumulate,
+                    double* work, long lwork, int nexp, void* stream);
+
 /* Predictive mean and variance from Ks[n_pad x m_pad] = k(X, Xp) (train rows, test columns):
  *   mean[j] = sum_i Ks[i][j] alpha[i]                 (gpr.py:80-85)
  *   var[j]  = kss - sum_i (Minv Ks)[i][j]^2           (gpr.py:98-104: diag(K**) - rowsum(K* o (K^-1 K*^T)^T))

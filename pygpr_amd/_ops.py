@@ -306,6 +306,51 @@ class HipOps:
                                              x.shape[1], _p(kinv), kinv.stride(0), _p(alpha), _p(grad), grad.numel(),
                                              _p(work), work.numel(), self._st()), "pg_nlml_grad")
 
+    # -- derivatives in the test points -------------------------------------------------------
+    def kernel_xgrad(self, spec, hp, xq, z, u=None, b=None, out_u=None, out_b=None, trans_b=False, accumulate=False):
+        """out_u[p][k] = sum_i u_i dk(xq_p, z_i)/dxq_pk and / or out_b[p][k] = sum_i B_pi dk(xq_p, z_i)/dxq_pk (pg_kernel_xgrad, one pass
+        over the pairs for both): xq [m, d], z [n, d], u [>= n], b [m, >= n] (trans_b: [n, >= m], b[i][p]); outputs [m, d] allocated when
+        None.  Returns (out_u, out_b)."""
+        m, d = xq.shape
+        out = self.kernel_xgrad_batched(spec, hp[None], xq, z[None], None if u is None else u[None], None if b is None else b[None],
+                                        None if out_u is None else out_u[None], None if out_b is None else out_b[None], trans_b, accumulate,
+                                        nexp=1)
+        return tuple(None if t is None else t[0] for t in out)
+
+    def kernel_xgrad_batched(self, spec, hp_all, xq, z_all, u_all=None, b_all=None, out_u=None, out_b=None, trans_b=False, accumulate=False,
+                             nexp=None):
+        """The same for nexp experts in one launch (+ the reduce): hp_all [nexp | 1, nhp]; xq [m, d] (shared) or [nexp, m, d]; z_all
+        [nexp | 1, n, d]; u_all [nexp, >= n]; b_all [nexp, m, >= n] (trans_b: [nexp, n, >= m]); outputs [nexp, m, d].  A Compose longer
+        than one pg_covspec runs one pass per spec, the later ones accumulating."""
+        assert u_all is not None or b_all is not None
+        nexp = nexp or max(hp_all.shape[0], z_all.shape[0], xq.shape[0] if xq.dim() == 3 else 1,
+                           *(t.shape[0] for t in (u_all, b_all) if t is not None))
+        m, d = xq.shape[-2], xq.shape[-1]
+        n = z_all.shape[-2]
+        dt = xq.dtype
+        self._chk(hp_all, xq, z_all, u_all, b_all)
+        assert hp_all.dtype == torch.float64 and z_all.dtype == dt
+        if u_all is not None and out_u is None:
+            out_u = self.empty(nexp, m, d, dtype=dt)
+        if b_all is not None and out_b is None:
+            out_b = self.empty(nexp, m, d, dtype=dt)
+        for t in (out_u, out_b):
+            assert t is None or (t.is_cuda and t.dtype == dt and t.dim() == 3 and t.stride(-1) == 1)
+
+        def es(t):    # expert stride; 0 shares the operand
+            return t.stride(0) if (t is not None and t.dim() == 3 and t.shape[0] > 1) else 0
+
+        work = self.empty(max(1, int(self.lib.pg_kernel_xgrad_worksize(self.h, m, n, d, nexp))), dtype=torch.float64)
+        for i, sp in enumerate(_passes(spec)):
+            _lib.check(self.lib.pg_kernel_xgrad(
+                self.h, _code(dt), C.byref(sp), _p(hp_all), hp_all.stride(0) if hp_all.shape[0] > 1 else 0, _p(xq), xq.stride(-2), es(xq), m,
+                _p(z_all), z_all.stride(-2), es(z_all), n, d, _p(u_all), u_all.stride(0) if (u_all is not None and u_all.shape[0] > 1) else 0,
+                _p(out_u), out_u.stride(1) if out_u is not None else 0, out_u.stride(0) if out_u is not None else 0,
+                _p(b_all), b_all.stride(-2) if b_all is not None else 0, es(b_all), int(bool(trans_b)),
+                _p(out_b), out_b.stride(1) if out_b is not None else 0, out_b.stride(0) if out_b is not None else 0,
+                int(bool(accumulate) or i > 0), _p(work), work.numel(), nexp, self._st()), "pg_kernel_xgrad")
+        return out_u, out_b
+
     # -- prediction ---------------------------------------------------------------------------
     def predict_mean_q(self, ks, minv, alpha, mean, var, kss, work):
         """mean = Ks^T alpha; var = kss - colsum((Minv Ks)^2) (var None: mean only)."""

@@ -607,6 +607,31 @@ int pg_nlml_value(pg_handle h, int dtype, int n, const void* L, long ldl, const 
 
 long pg_nlml_grad_worksize(int n, int nhp) { return pg_nlml_grad_worksize_impl(n, nhp); }
 
+long pg_kernel_xgrad_worksize(pg_handle h, int m, int n, int d, int nexp) { return h ? pg_xgrad_worksize_impl(h->ncu, m, n, d, nexp) : -1; }
+
+int pg_kernel_xgrad(pg_handle h, int dtype, const pg_covspec* spec, const double* hp, long hp_stride, const void* Xq, long ldq, long xq_stride,
+                    int m, const void* Z, long ldz, long z_stride, int n, int d, const void* u, long u_stride, void* out_u, long ldou,
+                    long ou_stride, const void* B, long ldb, long b_stride, int trans_b, void* out_b, long ldob, long ob_stride, int accumulate,
+                    double* work, long lwork, int nexp, void* stream) {
+    JOIN(h, stream);
+    NEED(h && hp && Xq && Z && work, "null pointer");
+    NEED(!u == !out_u && !B == !out_b, "u / B need their outputs (and the reverse)");
+    NEED(u || B, "neither u nor B given");
+    if (check_spec(spec, __func__)) return -1;
+    NEED(m >= 0 && n >= 0 && d >= 1 && d <= PG_MAX_DIM, "bad shape (0 <= m, n; 1 <= d <= PG_MAX_DIM)");
+    NEED(nexp >= 1 && nexp <= 65535 && (m + 63) / 64 <= 65535, "1 <= nexp <= 65535, m <= 64 * 65535");
+    NEED(ldq >= d && ldz >= d, "ldq, ldz >= d");
+    NEED(!B || ldb >= (trans_b ? m : n), "ldb too small");
+    NEED((!u || ldou >= d) && (!B || ldob >= d), "ldou, ldob >= d");
+    DISPATCH(dtype,
+             pg_xgrad_t<double>(ST(stream), h->ncu, *spec, hp, hp_stride, (const double*)Xq, ldq, xq_stride, m, (const double*)Z, ldz, z_stride, n,
+                                d, (const double*)u, u_stride, (double*)out_u, ldou, ou_stride, (const double*)B, ldb, b_stride, trans_b,
+                                (double*)out_b, ldob, ob_stride, accumulate, work, lwork, nexp),
+             pg_xgrad_t<float>(ST(stream), h->ncu, *spec, hp, hp_stride, (const float*)Xq, ldq, xq_stride, m, (const float*)Z, ldz, z_stride, n,
+                               d, (const float*)u, u_stride, (float*)out_u, ldou, ou_stride, (const float*)B, ldb, b_stride, trans_b,
+                               (float*)out_b, ldob, ob_stride, accumulate, work, lwork, nexp));
+}
+
 int pg_nlml_grad(pg_handle h, int dtype, const pg_covspec* spec, const double* hp, const void* X, long ldx, int n, int d,
                  const void* Kinv, long ldk, const void* alpha, double* grad, int nhp, double* work, long lwork,
                  void* stream) {

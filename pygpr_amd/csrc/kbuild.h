@@ -20,3 +20,9 @@ template <typename T>
 int pg_centres(hipStream_t st, const T* X, long ldx, int n, const T* Cn, long ldc, int m, int d, T* D, long ldd, int* idx);
 template <typename T>
 int pg_kgrad(hipStream_t st, const pg_covspec& spec, const double* hp, const T* X, long ldx, int n, int d, T* dK);
+// xgrad.hip: out[p][k] (+)= sum_i W_pi dk(Xq_p, Z_i)/dXq_pk for W = u (vector) and / or B (matrix); see pg_kernel_xgrad
+long pg_xgrad_worksize_impl(int ncu, int m, int n, int d, int nexp);
+template <typename T>
+int pg_xgrad_t(hipStream_t st, int ncu, const pg_covspec& spec, const double* hp, long hp_stride, const T* Xq, long ldq, long xq_stride, int m,
+               const T* Z, long ldz, long z_stride, int n, int d, const T* u, long u_stride, T* out_u, long ldou, long ou_stride, const T* B,
+               long ldb, long b_stride, int trans_b, T* out_b, long ldob, long ob_stride, int accumulate, double* work, long lwork, int nexp);

@@ -40,36 +40,6 @@ template <typename T> __device__ __forceinline__ T comp_value(int kind, T sig2, 
     return sig2 * ((T)1 + s5 * r + (T)(5.0 / 3.0) * sqd) * pg_exp(-s5 * r);
 }
 
-// Half the factor `coef` of the length-scale derivative dK/dl_k = coef base l_k D_k^2, per stationary kind (base: see pg_grad_kernel)
-__device__ __forceinline__ double kind_hcoef(int kind) {
-    if (kind == PG_KIND_RBF) return -1.0;
-    if (kind == PG_KIND_MATERN52) return 0.5 * -(5.0 / 3.0);
-    if (kind == PG_KIND_MATERN32) return -1.5;
-    return -0.5;                               // PG_KIND_MATERN12
-}
-
-// Covariance value kv and the factor `base` of dK/dl_k for a Matern kind from the scaled squared distance (direct differences: the
-// Matern-1/2 factor 1/r is only formed from an exact sq, so it is bounded by |D_k| after the multiplication by l_k D_k^2; 0 at sq = 0,
-// the derivative's limit there).
-template <typename T> __device__ __forceinline__ void matern_val(int kind, T sig2, T sq, T& kv, T& base) {
-    const T rr = sqrt(sq);
-    if (kind == PG_KIND_MATERN12) {
-        const T ex = sig2 * pg_exp(-rr);
-        kv = ex;
-        base = sq == (T)0 ? (T)0 : ex / rr;
-    } else if (kind == PG_KIND_MATERN32) {
-        const T s3 = (T)1.73205080756887729353;
-        const T ex = pg_exp(-s3 * rr);
-        kv = sig2 * ((T)1 + s3 * rr) * ex;
-        base = sig2 * ex;
-    } else {                                   // PG_KIND_MATERN52
-        const T s5 = (T)2.23606797749978969641;
-        const T ex = pg_exp(-s5 * rr);
-        kv = sig2 * ((T)1 + s5 * rr + (T)(5.0 / 3.0) * sq) * ex;
-        base = sig2 * ((T)1 + s5 * rr) * ex;
-    }
-}
-
 template <typename T>
 __device__ __forceinline__ void stage_points(T* dst, const T* __restrict__ X, long ldx, int npts, int p0, int d, int tid,
                                              const double* __restrict__ scale = nullptr, double mul = 1.0) {

@@ -21,6 +21,7 @@ from typing import Sequence
 import torch
 from torch import Tensor
 
+from . import _lib
 from ._ops import JITTER, get_ops, pad_to
 from .covar import Covar, layout, spec_of
 
@@ -196,6 +197,7 @@ class Exact_GP(GPR):
         # eager_inverse: form L^-1 inside update() (fused with the Cholesky) and take alpha = L^-T (L^-1 y) from two
         # triangular mat-vecs.  Worth it whenever predictive variances follow (grBCM experts); wasted work otherwise.
         self.eager_inverse = eager_inverse
+        self._upd_count = 0     # bumped by every change of the model's state: a backward checks it against its forward (_state_token)
         return None
 
     # ---- device residency -------------------------------------------------------------------
@@ -214,6 +216,16 @@ class Exact_GP(GPR):
         self._data = None
         self._pbuf = None
         self.need_upd = True
+        self._upd_count = getattr(self, "_upd_count", 0) + 1
+
+    def set_params(self, params: Tensor) -> None:
+        super().set_params(params)
+        self._upd_count = getattr(self, "_upd_count", 0) + 1
+
+    def _state_token(self):
+        """What a prediction's backward needs unchanged since its forward: the update counter and the identity and version of x, y and
+        params (in-place edits bump a tensor's version, as torch's own saved-tensor check sees them)."""
+        return (self._upd_count, id(self._x), self._x._version, id(self._y), self._y._version, id(self.params), self.params._version)
 
     def _device_data(self):
         """x / y on the device, one _Data per leading index of x, uploaded once per (tensor identity, version): in-place
@@ -348,6 +360,7 @@ class Exact_GP(GPR):
                 if info:
                     raise _lin_alg_error(info)
             self.need_upd = False
+            self._upd_count += 1
         return None
 
     def _minv(self, e):
@@ -514,6 +527,16 @@ class Exact_GP(GPR):
         return means, covs
 
     def predict(self, xp: Tensor, var: str = "full") -> Sequence[Tensor]:
+        """[mean, var | covariance | NotImplemented] at xp (gpr.py:76-120).  With grad mode on and xp.requires_grad the outputs come out of
+        a torch.autograd.Function whose forward is this same path (identical values) and whose backward differentiates them in xp
+        (`_PredictFn`)."""
+        want = var if var in ("full", "diag") else "none"
+        if torch.is_grad_enabled() and isinstance(xp, Tensor) and xp.requires_grad:
+            out = _PredictFn.apply(self, want, xp, self.params, self._x, self._y)
+            return [out, NotImplemented] if want == "none" else list(out)
+        return self._predict_plain(xp, var)
+
+    def _predict_plain(self, xp: Tensor, var: str) -> Sequence[Tensor]:
         ops = get_ops()
         want = var if var in ("full", "diag") else "none"
         xpd = ops.to_device(xp if xp.dim() == 2 else xp.reshape(-1, xp.shape[-2], xp.shape[-1]), self.dtype)
@@ -535,6 +558,114 @@ class Exact_GP(GPR):
         else:
             covars = covs[0].contiguous().to(xp.device)
         return [ys, covars]
+
+    # ---- derivatives in the test points ---------------------------------------------------------
+    def predict_grad(self, xp: Tensor, var: str = "diag") -> Sequence[Tensor]:
+        """[mean, var, dmean, dvar] (var="diag") or [mean, dmean] (var="none") without autograd: dmean[..., p, :] = d mean_p / d xp_p and
+        dvar[..., p, :] = d var_p / d xp_p, shape [m, d] ([nc, m, d] for a batched model), in the model's dtype on xp's device.  Mean and
+        variance are `predict`'s own (same path, same bits).  Both derivatives come out of one contraction launch (pg_kernel_xgrad:
+        u = alpha, B = V = K* K^-1); V is only formed when the variance's derivative is asked for."""
+        if var not in ("diag", "none"):
+            raise ValueError("predict_grad: var must be 'diag' or 'none', got %r" % (var,))
+        with torch.no_grad():
+            mean, cov = self._predict_plain(xp, var)
+            xpd = self._xp_device(xp)
+            dmean, dvar = self._xgrad(xpd, var)
+        dmean = self._grad_out(dmean, xp)
+        if var == "none":
+            return [mean, dmean]
+        return [mean, cov, dmean, self._grad_out(-2.0 * dvar, xp)]
+
+    def _xp_device(self, xp):
+        return get_ops().to_device(xp if xp.dim() == 2 else xp.reshape(-1, xp.shape[-2], xp.shape[-1]), self.dtype)
+
+    def _grad_out(self, g, xp):
+        """[nexp, m, d] per-expert rows -> [m, d] for one expert, [nc, m, d] for a batched model, on xp's device."""
+        return (g[0] if not self.batched else g).to(xp.device)
+
+    def _xgrad(self, xpd, want, g_mu=None, g_var=None, g_cov=None):
+        """Derivatives in the test points of every expert's prediction at xpd ([m, d] shared, or [nexp, m, d]; device, model dtype).
+        Without upstream gradients (predict_grad): (out_u, out_b) [nexp, m, d] with out_u = d mean / dx* and out_b = sum_i V_pi dk_pi
+        (want "diag"; -1/2 of d var / dx*).  With them (the autograd backward): the vector-Jacobian product [nexp, m, d] of
+        g_mu [nexp, m] and g_var [nexp, m] (want "diag") or g_cov [nexp, m, m] (want "full").  Every expert in one batched contraction per
+        chunk of test points; the weights V^T = K^-1 K*^T come from the GEMM core (pg_potrs against the cached L^-1) in buffers of their own
+        -- never the forward's shared K* buffer."""
+        ops = get_ops()
+        self._device_experts()
+        self.update()
+        spec, _ = spec_of(self.cov, self._x.shape[-1])
+        experts = self._experts
+        nb = len(experts)
+        if xpd.dim() == 3 and xpd.shape[0] not in (1, nb):
+            raise RuntimeError("batch dimension of xp (%d) does not match the %d experts" % (xpd.shape[0], nb))
+        n_pad = experts[0].n_pad
+        m, d = xpd.shape[-2], xpd.shape[-1]
+        bat = self._bat if (self._bat is not None and len(experts) > 1) else None
+        hp_all = bat["hp"] if bat is not None else torch.stack([e.hp for e in experts])
+        alpha_all = bat["alpha"] if bat is not None else torch.stack([e.alpha for e in experts])
+        bwd = g_mu is not None
+        out_u = ops.empty(nb, m, d, dtype=self.dtype)
+        out_b = ops.empty(nb, m, d, dtype=self.dtype) if want != "none" else None
+        chunk = m if want == "full" else _CHUNK
+        for s in range(0, m, chunk):
+            xq = xpd[..., s: s + chunk, :]
+            xq = xq if xq.is_contiguous() else xq.contiguous()
+            mc = xq.shape[-2]
+            m_pad = pad_to(mc)
+            ou, ob = out_u[:, s: s + mc], (out_b[:, s: s + mc] if out_b is not None else None)
+            if want == "none":
+                ops.kernel_xgrad_batched(spec, hp_all, xq, self._x_all, u_all=alpha_all, out_u=ou, nexp=nb)
+                continue
+            sym = None
+            if want == "full":       # S = G + G^T, zero-padded
+                sym = ops.zeros(nb, m_pad, m_pad, dtype=self.dtype)
+                sym[:, :mc, :mc] = g_cov + g_cov.transpose(-1, -2)
+            wt = ops.empty(nb, n_pad, m_pad, dtype=self.dtype)      # V^T (diag) or -K^-1 K*^T S = -(S V)^T (full), train-major
+            ks = ops.empty(n_pad, m_pad, dtype=self.dtype)
+            for b, e in enumerate(experts):
+                ops.kernel_build(spec, e.hp, e.x, xq if xq.dim() == 2 else xq[b % xq.shape[0]], ks)      # K*^T = k(x, xp)
+                rhs = ks
+                if sym is not None:
+                    rhs = ops.zeros(n_pad, m_pad, dtype=self.dtype)
+                    ops.gemm_raw(_lib.GEMM_NN, n_pad, m_pad, m_pad, -1.0, ks, sym[b], 0.0, rhs)
+                wt[b] = ops.potrs(e.chol, e.invd, rhs, minv=self._minv(e))
+            if want == "diag":
+                ops.kernel_xgrad_batched(spec, hp_all, xq, self._x_all, u_all=alpha_all, b_all=wt, out_u=ou, out_b=ob, trans_b=True, nexp=nb)
+            else:    # the K** term (z = the test points, weights S), then the K* term and the mean's, accumulated onto it
+                ops.kernel_xgrad_batched(spec, hp_all, xq, xq if xq.dim() == 3 else xq[None], b_all=sym, out_b=ob, nexp=nb)
+                ou.zero_()
+                ops.kernel_xgrad_batched(spec, hp_all, xq, self._x_all, u_all=alpha_all, b_all=wt, out_u=ou, out_b=ob, trans_b=True,
+                                         accumulate=True, nexp=nb)
+        if not bwd:
+            return out_u, out_b
+        g = out_u * g_mu[..., None]
+        if want == "diag":
+            g = g - 2.0 * (out_b * g_var[..., None])
+        elif want == "full":
+            g = g + out_b
+        return g
+
+    def _predict_vjp(self, xp, want, grads):
+        """The backward of predict(xp, want) for the upstream gradients of its outputs: d<grads, outputs>/dxp in xp's shape, dtype, device.
+        Experts that predict at one shared xp [m, d] add up; xp [nc, m, d] gets each expert's rows."""
+        ops = get_ops()
+        xpd = self._xp_device(xp)
+        nb = len(self._device_experts())
+        m = xpd.shape[-2]
+
+        def dev(t, shape):
+            return ops.zeros(*shape, dtype=self.dtype) if t is None else ops.to_device(t.reshape(shape), self.dtype)
+
+        g_mu = dev(grads[0], (nb, m))
+        if want == "none":
+            g = self._xgrad(xpd, want, g_mu)
+        elif want == "diag":
+            g = self._xgrad(xpd, want, g_mu, g_var=dev(grads[1], (nb, m)))
+        else:
+            g = self._xgrad(xpd, want, g_mu, g_cov=dev(grads[1], (nb, m, m)))
+        if xpd.dim() == 2 or xpd.shape[0] == 1:
+            g = g.sum(0) if nb > 1 else g[0]
+        return g.reshape(xp.shape).to(device=xp.device, dtype=xp.dtype)
 
     def predict_var(self, xp: Tensor, **kwargs: Tensor) -> Tensor:
         return self.predict(xp, var="diag")[1]
@@ -578,3 +709,35 @@ class Exact_GP(GPR):
         self.update()
         out = self._stack([e.alpha[: e.n] for e in self._experts])
         return out.reshape(self._y.shape) if (not self.batched and self._y.dim() > 1) else out
+
+
+class _PredictFn(torch.autograd.Function):
+    """Exact_GP.predict as an autograd node in the test points.  forward: the library's prediction, unchanged (no grad: same values as a
+    call without autograd).  backward: the vector-Jacobian product in xp through pg_kernel_xgrad (Exact_GP._xgrad):
+      mean      d/dx*_p = g_mu_p sum_i alpha_i dk(x*_p, x_i)
+      diag var  d/dx*_p = -2 g_var_p sum_i V_pi dk(x*_p, x_i)                       (K** has a constant diagonal)
+      full cov  d/dx*_p = sum_q S_pq dk(x*_p, x*_q) - sum_i (S V)_pi dk(x*_p, x_i)   (S = G + G^T)
+    Gradients flow to xp only: params / x / y that require grad make the backward raise NotImplementedError, and so does -- as a
+    RuntimeError -- any change of the model (set_params, update, edits of x / y) between forward and backward."""
+
+    @staticmethod
+    def forward(ctx, model, want, xp, params, x, y):
+        with torch.no_grad():
+            ys, covars = model._predict_plain(xp, want)
+        ctx.model, ctx.want, ctx.token = model, want, model._state_token()
+        ctx.save_for_backward(xp)
+        return ys if want == "none" else (ys, covars)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        for i, name in ((3, "params"), (4, "x"), (5, "y")):
+            if ctx.needs_input_grad[i]:
+                raise NotImplementedError("Exact_GP.predict: gradients flow to the test points xp only, but the model's `%s` requires grad"
+                                          % name)
+        model = ctx.model
+        if model._state_token() != ctx.token:
+            raise RuntimeError("Exact_GP.predict: the model changed (set_params / update / an edit of x or y) between the forward and the "
+                               "backward of this prediction")
+        (xp,) = ctx.saved_tensors
+        g = model._predict_vjp(xp, ctx.want, grads) if ctx.needs_input_grad[2] else None
+        return None, None, g, None, None, None
