@@ -173,6 +173,21 @@ int pg_trmv(pg_handle h, int dtype, int n, const void* Minv, long ldm, int trans
 int pg_alpha_batched(pg_handle h, int dtype, int n, const void* Minv, long ldm, long m_stride, const void* y, long y_stride, void* u,
                      long u_stride, void* alpha, long alpha_stride, void* work, long work_stride, int nexp, void* stream);
 
+/* Condition a fitted factor on k new points, hyper-parameters unchanged (new: the reference has no such entry point).  On entry L, inv_diag,
+ * Minv = L^-1, u = L^-1 y and alpha = K^-1 y describe n points padded to n_pad (identity pad; zeros past n in u and alpha).  With
+ * Kt = k(Xn, X) [k x n] (a cross build: no noise; zero past column n) and Knn = k(Xn, Xn) + noise + jitter I [k x k]:
+ *   Vt = Kt Minv^T, S = Knn - Vt Vt^T = Ls Ls^T, Lsi = Ls^-1;
+ *   L <- [[L, 0], [Vt, Ls]], Minv <- [[Minv, 0], [-Lsi Vt Minv, Lsi]], u <- [u; Lsi (y_new - Vt u)], alpha <- Minv^T u,
+ * and every 128-block of inv_diag that rows n .. n+k-1 cross receives those rows of the new Minv's diagonal block.  O(n^2 k) work: three
+ * reads of Minv's lower triangle (its strictly upper part is never read), fp64 accumulation for both dtypes.  Asynchronous: *info is set
+ * on the device to 0, or to n + c + 1 when the pivot c of S is not > 0 (NaN included) -- then L, inv_diag, Minv, u and alpha are left
+ * bit for bit as they were.  Rows and columns from n + k on stay the identity.  1 <= k <= 128, n + k <= n_pad, n_pad % 256 == 0.
+ * work: pg_chol_append_worksize(dtype, n_pad, k) elements of dtype. */
+long pg_chol_append_worksize(int dtype, int n_pad, int k);
+int pg_chol_append(pg_handle h, int dtype, int n, int k, int n_pad, void* L, long ldl, void* inv_diag, void* Minv, long ldm,
+                   const void* Kt, long ldkt, const void* Knn, long ldknn, const void* y_new, void* u, void* alpha, void* work, int* info,
+                   void* stream);
+
 /* out[0] = 1/2 y^T alpha + sum_i log L_ii + n/2 log 2pi   (loss.py:47-49, 107-109); n = real points */
 int pg_nlml_value(pg_handle h, int dtype, int n, const void* L, long ldl, const void* y, const void* alpha,
                   double* out, void* stream);

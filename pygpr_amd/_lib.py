@@ -56,6 +56,8 @@ _SIGS = {
     "pg_lauum_batched": (_i, [_vp, _i, _i, _vp, _l, _l, _vp, _l, _l, _i, _vp]),
     "pg_nlml_grad_batched": (_i, [_vp, _i, C.POINTER(CovSpec), _vp, _l, _vp, _l, _l, _i, _i, _vp, _l, _l, _vp, _l, _vp, _l, _i, _vp, _l, _i, _vp]),
     "pg_alpha_nlml_async": (_i, [_vp, _i, _i, _i, _vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pg_chol_append_worksize": (_l, [_i, _i, _i]),
+    "pg_chol_append": (_i, [_vp, _i, _i, _i, _i, _vp, _l, _vp, _vp, _l, _vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pg_nlml_value": (_i, [_vp, _i, _i, _vp, _l, _vp, _vp, _vp, _vp]),
     "pg_nlml_grad_worksize": (_l, [_i, _i]),
     "pg_nlml_grad": (_i, [_vp, _i, C.POINTER(CovSpec), _vp, _vp, _l, _i, _i, _vp, _l, _vp, _vp, _i, _vp, _l, _vp]),

@@ -278,6 +278,20 @@ class HipOps:
         _lib.check(self.lib.pg_trmv(self.h, _code(minv.dtype), minv.shape[0], _p(minv), minv.stride(0), int(trans),
                                     _p(x), _p(y), _p(work), self._st()), "pg_trmv")
 
+    def chol_append_worksize(self, n_pad, k, dtype):
+        return int(self.lib.pg_chol_append_worksize(_code(dtype), int(n_pad), int(k)))
+
+    def chol_append(self, n, k, chol, invd, minv, kt, knn, y_new, u, alpha, work, info):
+        """Condition the factor of n points on k <= 128 more (pg_chol_append): chol, invd, minv, u, alpha [n_pad] are updated in place
+        when info[0] comes out 0 and left untouched otherwise; kt [>= k, n_pad] = k(x_new, x) (zero past n), knn [>= k, >= k] =
+        k(x_new, x_new) + noise + jitter I, y_new [k]; work: chol_append_worksize elements.  Asynchronous: read info after a sync."""
+        self._chk(chol, invd, minv, kt, knn, y_new, u, alpha, work, info)
+        assert info.dtype == torch.int32
+        n_pad = chol.shape[0]
+        _lib.check(self.lib.pg_chol_append(
+            self.h, _code(chol.dtype), int(n), int(k), n_pad, _p(chol), chol.stride(0), _p(invd), _p(minv), minv.stride(0), _p(kt),
+            kt.stride(0), _p(knn), knn.stride(0), _p(y_new), _p(u), _p(alpha), _p(work), _p(info), self._st()), "pg_chol_append")
+
     def tril(self, a, n):
         self._chk(a)
         _lib.check(self.lib.pg_tril(self.h, _code(a.dtype), n, _p(a), a.stride(0), self._st()), "pg_tril")

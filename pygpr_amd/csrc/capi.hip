@@ -533,6 +533,28 @@ int pg_trmv(pg_handle h, int dtype, int n, const void* Minv, long ldm, int trans
              pg_trmv_t<float>(h, ST(stream), n, (const float*)Minv, ldm, trans, (const float*)x, (float*)y, (float*)work));
 }
 
+long pg_chol_append_worksize(int dtype, int n_pad, int k) {
+    if (dtype != PG_F64 && dtype != PG_F32) return -1;
+    return pg_chol_append_worksize_impl(dtype == PG_F64 ? 8 : 4, n_pad, k);
+}
+
+int pg_chol_append(pg_handle h, int dtype, int n, int k, int n_pad, void* L, long ldl, void* inv_diag, void* Minv, long ldm, const void* Kt,
+                   long ldkt, const void* Knn, long ldknn, const void* y_new, void* u, void* alpha, void* work, int* info, void* stream) {
+    JOIN(h, stream);
+    NEED(h && L && inv_diag && Minv && Kt && Knn && y_new && u && alpha && work && info, "null pointer");
+    NEED(n_pad > 0 && n_pad % PG_PAD == 0, "n_pad must be a positive multiple of 256");
+    NEED(k >= 1 && k <= PG_APPEND_KMAX, "1 <= k <= 128");
+    NEED(n >= 1 && n + k <= n_pad, "1 <= n and n + k <= n_pad");
+    NEED(ldl >= n_pad && ldm >= n_pad, "ldl, ldm >= n_pad");
+    NEED(ldkt >= n && ldknn >= k, "ldkt >= n, ldknn >= k");
+    NEED(L != Minv && u != alpha, "L / Minv and u / alpha must not alias");
+    DISPATCH(dtype,
+             pg_chol_append_t<double>(h, ST(stream), n, k, n_pad, (double*)L, ldl, (double*)inv_diag, (double*)Minv, ldm, (const double*)Kt,
+                                      ldkt, (const double*)Knn, ldknn, (const double*)y_new, (double*)u, (double*)alpha, work, info),
+             pg_chol_append_t<float>(h, ST(stream), n, k, n_pad, (float*)L, ldl, (float*)inv_diag, (float*)Minv, ldm, (const float*)Kt,
+                                     ldkt, (const float*)Knn, ldknn, (const float*)y_new, (float*)u, (float*)alpha, work, info));
+}
+
 int pg_alpha_batched(pg_handle h, int dtype, int n, const void* Minv, long ldm, long m_stride, const void* y, long y_stride, void* u,
                      long u_stride, void* alpha, long alpha_stride, void* work, long work_stride, int nexp, void* stream) {
     JOIN(h, stream);

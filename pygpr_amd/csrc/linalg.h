@@ -74,3 +74,9 @@ template <typename T> int pg_symmetrize_t(hipStream_t, int n, T* A, long lda);
 template <typename T>
 int pg_grbcm_finish_full_t(hipStream_t, int m, const double* sums, long lds, const T* mean_g, const T* var_g, const T* cov, long ldc,
                            T* mean);
+// append.hip: conditioning a fitted factor on k <= PG_APPEND_KMAX new points (pg_chol_append)
+#define PG_APPEND_KMAX 128
+long pg_chol_append_worksize_impl(int tsize, int n_pad, int k);
+template <typename T>
+int pg_chol_append_t(pg_ctx*, hipStream_t, int n, int k, int n_pad, T* L, long ldl, T* invd, T* Minv, long ldm, const T* Kt, long ldkt,
+                     const T* Knn, long ldknn, const T* yn, T* u, T* alpha, void* work, int* info);

@@ -32,6 +32,7 @@ _CHUNK = 8192  # test points per device batch
 _BATCH_MAX_N = int(os.environ.get("PG_BATCH_MAX_N", "12288"))
 _FULL_VT_BYTES = 16 << 30   # predict(var="full"): experts whose V^T fit this together share one rank-n update launch (and at most
                             # 40 % of the device memory that is free when the call starts: `_group_budget`)
+_APPEND_K = 128         # points per pg_chol_append block (Exact_GP.append)
 _BATCH_EAGER_N = 4096   # batched experts up to this size form L^-1 with the factor even when nobody asked for variances: the
                         # batched inverse + three batched mat-vec launches are cheaper than one substitution sweep per expert
 
@@ -114,6 +115,15 @@ def _stacked_pair(a, b):
     return torch.as_strided(a, (2,) + tuple(a.shape), (step,) + tuple(a.stride()))
 
 
+def _blockdiag_eye(a, n_pad):
+    """[n_pad, n_pad] copy of the square a with the identity below and right of it."""
+    out = torch.zeros(n_pad, n_pad, dtype=a.dtype, device=a.device)
+    m = a.shape[0]
+    out[:m, :m] = a
+    out[m:, m:].diagonal().fill_(1)
+    return out
+
+
 class GPR:
     """Base class for Gaussian process regression models (PyGPR/gpr.py:13-43)."""
 
@@ -154,6 +164,9 @@ class GPR:
     def update(self) -> None:
         raise NotImplementedError
 
+    def append(self, x_new: Tensor, y_new: Tensor) -> None:
+        raise NotImplementedError("%s has no incremental append; assign x / y and refit" % type(self).__name__)
+
     def predict(self, xp: Tensor, var: str) -> Sequence[Tensor]:
         raise NotImplementedError
 
@@ -173,11 +186,12 @@ class _Data:
 class _Expert:
     """Device state of one expert (its data may be shared with other experts: batched params on unbatched x)."""
 
-    __slots__ = ("x", "y", "n", "n_pad", "chol", "invd", "alpha", "minv", "minv_valid", "work", "hp", "info")
+    # u = L^-1 y: held from the first append after a fit on (Exact_GP.append keeps it current), None otherwise
+    __slots__ = ("x", "y", "n", "n_pad", "chol", "invd", "alpha", "minv", "minv_valid", "work", "hp", "info", "u")
 
     def __init__(self, data):
         self.x, self.y, self.n, self.n_pad = data.x, data.y, data.n, data.n_pad
-        self.chol = self.invd = self.alpha = self.minv = self.work = self.hp = self.info = None
+        self.chol = self.invd = self.alpha = self.minv = self.work = self.hp = self.info = self.u = None
         self.minv_valid = False
 
 
@@ -333,6 +347,7 @@ class Exact_GP(GPR):
 
             def enqueue_serial():
                 for b, e in enumerate(experts):
+                    e.u = None
                     e.hp = ops.to_device(hp_rows[b % hp_rows.shape[0]], torch.float64)
                     if e.chol is None:
                         e.chol = ops.empty(e.n_pad, e.n_pad, dtype=self.dtype)
@@ -371,6 +386,107 @@ class Exact_GP(GPR):
             ops.trtri(e.chol, e.invd, e.minv)
             e.minv_valid = True
         return e.minv
+
+    # ---- conditioning on new observations --------------------------------------------------------
+    def append(self, x_new: Tensor, y_new: Tensor) -> None:
+        """Condition the model on k new observations in place, hyper-parameters unchanged; returns None.  x_new is [k, d] ([1, k, d] or
+        [k, d] when x is [1, n, d]), y_new has y's layout with k in its last dimension; both follow the model's dtype and device.
+        Afterwards model.x / model.y are new tensors equal to torch.cat of the old and the new (the x / y setters are not used), and the
+        model reads exactly as a fresh fit on them does, to rounding.
+
+        A fitted model extends its factor by blocks of at most 128 points (pg_chol_append: O(n^2 k), three passes over L^-1) instead of
+        refitting in O(n^3): L^-1 is formed once if it is not held, and kept from then on.  A model that needs an update anyway (never fitted,
+        after set_params or an edit of x / y) only takes the data; the next update() fits the lot.  If a pivot of the new block fails
+        (e.g. a NaN in x_new) the call raises torch.linalg.LinAlgError and the model is left exactly as it was.  Batched models (more than
+        one expert) raise NotImplementedError, and so does GRBCM, unchanged."""
+        x_old, y_old = self._x, self._y
+        d = x_old.shape[-1]
+        nb_params = self.params.reshape(-1, self.params.shape[-1]).shape[0] if isinstance(self.params, Tensor) else 1
+        if (x_old.dim() == 3 and x_old.shape[0] > 1) or (y_old.dim() > 1 and y_old.reshape(-1, y_old.shape[-1]).shape[0] > 1) or nb_params > 1:
+            raise NotImplementedError("Exact_GP.append: batched models (more than one expert) are not supported")
+        if x_new.dim() == 3 and x_new.shape[0] == 1 and x_old.dim() == 3:
+            x_new = x_new[0]
+        if x_new.dim() != 2 or x_new.shape[1] != d:
+            raise ValueError("Exact_GP.append: x_new must be [k, %d], got %s" % (d, tuple(x_new.shape)))
+        k = x_new.shape[0]
+        if y_new.numel() != k or y_old.shape[-1] != x_old.shape[-2]:
+            raise ValueError("Exact_GP.append: y_new must hold %d values in y's layout, got %s" % (k, tuple(y_new.shape)))
+        if k == 0:
+            return None
+        xh = x_new.detach().to(device=x_old.device, dtype=x_old.dtype)
+        yh = y_new.detach().reshape(y_old.shape[:-1] + (k,)).to(device=y_old.device, dtype=y_old.dtype)
+        x_cat = torch.cat([x_old, xh[None] if x_old.dim() == 3 else xh], dim=-2)
+        y_cat = torch.cat([y_old, yh], dim=-1)
+        experts = self._device_experts()
+        if self.need_upd:                      # the next update() fits the combined data from scratch
+            self._x, self._y = x_cat, y_cat
+            self._data_changed()
+            return None
+        self._append_fitted(experts[0], xh, yh.reshape(k), x_cat, y_cat)
+        return None
+
+    def _append_fitted(self, e, xh, yh, x_cat, y_cat):
+        ops = get_ops()
+        dt = self.dtype
+        spec, _ = spec_of(self.cov, self._x.shape[-1])
+        k, n0 = xh.shape[0], e.n
+        total = n0 + k
+        n_pad = pad_to(total)
+        xd = torch.cat([e.x, ops.to_device(xh, dt)], dim=0)                     # [n + k, d]: every point on the device
+        yd = ops.to_device(yh, dt)
+        minv = self._minv(e)
+        if e.u is None:
+            e.u = ops.zeros(e.n_pad, dtype=dt)
+            ops.trmv(minv, e.y, e.u, 0)
+        # growth, or more than one block: work on copies (blockdiag(., I) when growing) and swap them in only once every block went in
+        copy = n_pad > e.n_pad or k > _APPEND_K
+        if copy:
+            chol, minv_w = _blockdiag_eye(e.chol, n_pad), _blockdiag_eye(minv, n_pad)
+            invd = ops.empty(ops.potrf_worksize(n_pad, dt), dtype=dt)
+            invd.zero_()
+            blocks = invd[: n_pad * 128].view(n_pad // 128, 128, 128)
+            nb0 = e.n_pad // 128
+            blocks[:nb0] = e.invd[: e.n_pad * 128].view(nb0, 128, 128)
+            blocks[nb0:] = torch.eye(128, dtype=dt, device=ops.device)
+            u, alpha = ops.zeros(n_pad, dtype=dt), ops.zeros(n_pad, dtype=dt)
+            u[: e.n_pad], alpha[: e.n_pad] = e.u, e.alpha
+        else:
+            chol, minv_w, invd, u, alpha = e.chol, minv, e.invd, e.u, e.alpha
+        kmax = min(k, _APPEND_K)
+        kpad = pad_to(kmax, 128)
+        kt = ops.empty(kpad, n_pad, dtype=dt)
+        knn = ops.empty(kpad, kpad, dtype=dt)
+        work = ops.empty(ops.chol_append_worksize(n_pad, kmax, dt), dtype=dt)
+        info = torch.zeros(1, dtype=torch.int32, device=ops.device)
+        for s in range(0, k, _APPEND_K):
+            kc = min(_APPEND_K, k - s)
+            xc = xd[n0 + s: n0 + s + kc]
+            ops.kernel_build(spec, e.hp, xc, xd[: n0 + s], kt)                   # k(Xn, X): zero past n (cross build, no noise)
+            ops.kernel_build(spec, e.hp, xc, None, knn, jitter=JITTER)            # k(Xn, Xn) + noise + jitter I, as update() builds K
+            ops.chol_append(n0 + s, kc, chol, invd, minv_w, kt, knn, yd[s: s + kc], u, alpha, work, info)
+            bad = int(info.item())
+            if bad:
+                raise _lin_alg_error(bad)
+        # every block is in: publish
+        if copy:
+            e.chol, e.invd, e.minv, e.u, e.alpha = chol, invd, minv_w, u, alpha
+            if e.work is not None:
+                e.work = ops.empty((n_pad // 256 + 1) * n_pad, dtype=dt)
+            self._pbuf = None
+        if n_pad > e.n_pad:
+            y_all = ops.zeros(1, n_pad, dtype=dt)
+            y_all[0, :n0] = e.y[:n0]
+        else:
+            y_all = self._y_all[:1]
+        y_all[0, n0:total] = yd
+        dta = _Data()
+        dta.n, dta.n_pad, dta.x, dta.y = total, n_pad, xd, y_all[0]
+        e.x, e.y, e.n, e.n_pad = xd, y_all[0], total, n_pad
+        self._x_all, self._y_all = xd[None], y_all
+        self._x, self._y = x_cat, y_cat
+        self._data = [dta]
+        self._data_key = (id(self._x), self._x._version, id(self._y), self._y._version)
+        self._upd_count += 1
 
     def _kss_diag(self, b: int) -> float:
         """diag of cov.kernel(params, xp): sum sigma_c^2 + sum sigma_n^2 (White_noise sees xp=None,
