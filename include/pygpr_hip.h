@@ -12,6 +12,15 @@
  *   - matrices are row-major with a leading dimension in elements; dtype is PG_F64 or PG_F32
  *   - the O(n^3) entry points need n_pad % 256 == 0; pg_kernel_build fills the padding with identity
  *     (symmetric build) or zeros (cross build), so padded factors are block-diag(L, I)
+ *   - alignment: the entry points whose kernels move 16-byte words at base + r * ld + c (the GEMM core, the factorisation chain,
+ *     the covariance tiles, the fused gradient, the triangular mat-vecs -- everything except the scalar ones named next) REFUSE,
+ *     before anything is enqueued, a matrix or vector operand whose base pointer, leading dimension or expert stride is not a
+ *     multiple of 16 bytes (2 fp64 / 4 fp32 elements); any ld >= width that keeps that rule is honoured, gaps are neither read nor
+ *     written.  Scalar throughout, any ld >= width: pg_tril, pg_symmetrize, pg_logdet, pg_nlml_value, pg_grbcm_*,
+ *     pg_sqdist_argmin, pg_kernel_grad_build, pg_kernel_xgrad, pg_chol_append (and the X / hp operands of every entry point)
+ *   - triangular operands: L and Minv are read on and below their diagonal 128 x 128 blocks only (what lies above those blocks may
+ *     hold anything, NaN included); outputs described as "lower" are written on the lower triangle, may be written inside the
+ *     diagonal 128-blocks above the diagonal, and are never touched above those blocks
  *   - calls are asynchronous on `stream`; return 0 = enqueued, <0 = bad argument / HIP error
  *     (text via pg_last_error()); numerical failure (non-PD pivot) is reported LAPACK-style in a
  *     device int `info` that the caller reads after synchronising
@@ -65,7 +74,9 @@ int pg_destroy(pg_handle h);
  * sum(sigma_n^2) + jitter as in gpr.py:68 / loss.py:38); lower_only skips tiles above the diagonal.
  * Otherwise a cross build K[i][j] = k(Xr_i, Xc_j) (covar.py:152-161; no noise term, covar.py:243).
  * accumulate != 0: K += (the sum over children of Compose.kernel, covar.py:57-60, continued in a further pass;
- * the padding is then left alone).  d <= PG_MAX_DIM. */
+ * the padding is then left alone).  d <= PG_MAX_DIM.  Rows of Xr / Xc from nr / nc on are never read.  nr == 0 or nc == 0 is
+ * legal: the whole output is padding (identity / zeros; lower tiles only with lower_only) and Xr / Xc are not touched.
+ * Writes: all of rows_pad x cols_pad (lower_only: the 64 x 64 tiles on and below the diagonal; accumulate: [0, nr) x [0, nc) only). */
 int pg_kernel_build(pg_handle h, int dtype, const pg_covspec* spec, const double* hp, const void* Xr, long ldr,
                     int nr, const void* Xc, long ldc, int nc, int d, int lower_only, int accumulate, double jitter,
                     void* K, long ldk, int rows_pad, int cols_pad, void* stream);
@@ -148,16 +159,19 @@ int pg_trsm_lower(pg_handle h, int dtype, int n, int nrhs, const void* L, long l
                   const void* B, long ldb, void* X, long ldx, void* work, void* stream);
 
 /* Minv = L^-1 (lower; its strictly upper blocks are scratch).  First half of cholesky_solve against a
- * matrix right-hand side (gpr.py:100,112; loss.py:116). */
+ * matrix right-hand side (gpr.py:100,112; loss.py:116).  Writes the whole lower triangle of Minv (it does not rely on the caller's
+ * zeros); what it leaves above the diagonal is scratch, not zeros.  Reads L on and below its diagonal 128-blocks and the first
+ * n * 128 elements of inv_diag. */
 int pg_trtri(pg_handle h, int dtype, int n, const void* L, long ldl, const void* inv_diag, void* Minv, long ldm,
              void* stream);
 
 /* Kinv(lower triangle) = Minv^T Minv = K^-1: what loss.py:116 obtains column by column with
- * cholesky_solve(dkrn, L). */
+ * cholesky_solve(dkrn, L).  Writes the lower triangle only (plus, possibly, the rest of the diagonal 128-blocks); the blocks above
+ * the diagonal keep the caller's bits -- use pg_symmetrize for the full matrix.  Reads Minv on and below its diagonal 128-blocks. */
 int pg_lauum(pg_handle h, int dtype, int n, const void* Minv, long ldm, void* Kinv, long ldk, void* stream);
 
 /* K^-1 (lower triangle) from the factor in one call = pg_trtri followed by pg_lauum (LAPACK's potri; SURVEY 8b lists it
- * under that name).  work: n x n elements (receives L^-1); Kinv may alias L. */
+ * under that name).  work: n x n elements (receives L^-1 with leading dimension n, 16-byte aligned); Kinv may alias L. */
 int pg_potri(pg_handle h, int dtype, int n, const void* L, long ldl, const void* inv_diag, void* Kinv, long ldk,
              void* work, void* stream);
 

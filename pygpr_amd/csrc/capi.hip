@@ -5,6 +5,7 @@
 #include "chainstep.h"
 #include "linalg.h"
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -57,6 +58,17 @@ void pg_set_error(const char* fmt, ...) {
     do {                                                         \
         if (!(cond)) { pg_set_error("%s: %s", __func__, what); return -1; } \
     } while (0)
+// The GEMM core, the chain kernels, the covariance tiles, the gradient bodies and the triangular mat-vecs move 16-byte words
+// (vec_t) at base + r * ld + c with c a multiple of the vector width: every operand they touch needs a 16-byte aligned base and
+// 16-byte rows (and expert strides).  Checked here, before anything is enqueued; scalar kernels (pg_tril, pg_symmetrize, pg_logdet,
+// pg_nlml_value, the committee's element-wise entry points, pg_sqdist_argmin, pg_kernel_grad_build, pg_kernel_xgrad, pg_chol_append)
+// take any ld >= width.
+static bool rows16(int dtype, const void* p, long ld) {
+    const long e = dtype == PG_F32 ? 4 : 8;
+    return !p || (reinterpret_cast<uintptr_t>(p) % 16 == 0 && (ld * e) % 16 == 0);      // (a NULL operand is optional: nothing to align)
+}
+#define NEED16(p, ld) NEED(rows16(dtype, (p), (ld)), #p ": base and rows (" #ld ") must be 16-byte aligned")
+#define NEEDS16(p, stride) NEED(!(p) || ((stride) * (dtype == PG_F32 ? 4 : 8)) % 16 == 0, #p ": expert stride " #stride " must keep every expert 16-byte aligned")
 #define DISPATCH(dtype, CALL_D, CALL_F)                                      \
     do {                                                                     \
         if ((dtype) == PG_F64) return CALL_D;                                \
@@ -352,6 +364,7 @@ int pg_kernel_build(pg_handle h, int dtype, const pg_covspec* spec, const double
     NEED(nr >= 0 && nc >= 0 && rows_pad >= nr && cols_pad >= nc && ldk >= cols_pad, "inconsistent sizes");
     NEED(!sym || rows_pad == cols_pad, "symmetric build needs a square padded shape");
     NEED(ldk % (dtype == PG_F64 ? 2 : 4) == 0, "ldk must keep rows 16-byte aligned");
+    NEED16(K, ldk);
     DISPATCH(dtype,
              pg_kbuild<double>(ST(stream), *spec, hp, (const double*)Xr, ldr, nr, (const double*)Xc, ldc, nc, d, sym,
                                lower_only, accumulate, jitter, (double*)K, ldk, rows_pad, cols_pad),
@@ -372,6 +385,7 @@ int pg_kernel_build_batched(pg_handle h, int dtype, const pg_covspec* spec, cons
     NEED(!sym || rows_pad == cols_pad, "symmetric build needs a square padded shape");
     NEED(nexp == 1 || k_stride >= (long)rows_pad * ldk, "experts' matrices overlap");
     NEED(ldk % (dtype == PG_F64 ? 2 : 4) == 0, "ldk must keep rows 16-byte aligned");
+    NEED16(K, ldk); NEEDS16(K, k_stride);
     DISPATCH(dtype,
              pg_kbuild<double>(ST(stream), *spec, hp, (const double*)Xr, ldr, nr, (const double*)Xc, ldc, nc, d, sym, lower_only, 0, jitter,
                                (double*)K, ldk, rows_pad, cols_pad, 0, 0, nexp, xc_stride, hp_stride, k_stride, xr_stride),
@@ -397,6 +411,7 @@ int pg_build_potrf_trtri(pg_handle h, int dtype, const pg_covspec* spec, const d
     if (check_spec(spec, __func__, true)) return -1;
     NEED(n >= 0 && n_pad >= n && lda >= n_pad, "inconsistent sizes");
     NEED(lda % (dtype == PG_F64 ? 2 : 4) == 0, "lda must keep rows 16-byte aligned");
+    NEED16(A, lda); NEED16(inv_diag, 0); NEED16(Minv, ldm);
     AtomicGuard ag(h, A);
     DISPATCH(dtype, build_potrf_t<double>(h, ST(stream), spec, hp, X, ldx, n, d, jitter, A, lda, n_pad, inv_diag, info, Minv, ldm),
              build_potrf_t<float>(h, ST(stream), spec, hp, X, ldx, n, d, jitter, A, lda, n_pad, inv_diag, info, Minv, ldm));
@@ -415,6 +430,7 @@ int pg_build_potrf_trtri_batched(pg_handle h, int dtype, const pg_covspec* spec,
     NEED(inv_stride >= pg_potrf_worksize_impl(n_pad) || nexp == 1, "experts' workspaces overlap (stride < pg_potrf_worksize)");
     NEED(!Minv || (ldm >= n_pad && (m_stride >= (long)n_pad * ldm || nexp == 1)), "experts' inverses overlap");
     NEED(lda % (dtype == PG_F64 ? 2 : 4) == 0, "lda must keep rows 16-byte aligned");
+    NEED16(A, lda); NEEDS16(A, a_stride); NEED16(inv_diag, inv_stride); NEED16(Minv, ldm); NEEDS16(Minv, m_stride);
     maybe_rearm(h);      // a batched-only workload counts towards the re-arm like the single-matrix calls (one per call)
     AtomicGuard ag(h, A);
     DISPATCH(dtype,
@@ -432,6 +448,7 @@ int pg_potrf(pg_handle h, int dtype, int n, void* A, long lda, void* inv_diag, i
     NEED(h && A && inv_diag && info, "null pointer");
     AtomicGuard ag(h, A);
     NEED(lda >= n, "lda < n");
+    NEED16(A, lda); NEED16(inv_diag, 0);
     DISPATCH(dtype, pg_potrf_t<double>(h, ST(stream), n, (double*)A, lda, (double*)inv_diag, info, nullptr, 0),
              pg_potrf_t<float>(h, ST(stream), n, (float*)A, lda, (float*)inv_diag, info, nullptr, 0));
 }
@@ -442,6 +459,7 @@ int pg_potrf_trtri(pg_handle h, int dtype, int n, void* A, long lda, void* inv_d
     maybe_rearm(h);
     NEED(h && A && inv_diag && info && Minv, "null pointer");
     NEED(lda >= n && ldm >= n && A != Minv, "bad leading dimension / aliasing");
+    NEED16(A, lda); NEED16(inv_diag, 0); NEED16(Minv, ldm);
     AtomicGuard ag(h, A);
     DISPATCH(dtype, pg_potrf_t<double>(h, ST(stream), n, (double*)A, lda, (double*)inv_diag, info, (double*)Minv, ldm),
              pg_potrf_t<float>(h, ST(stream), n, (float*)A, lda, (float*)inv_diag, info, (float*)Minv, ldm));
@@ -453,6 +471,8 @@ int pg_potrs_vec(pg_handle h, int dtype, int n, const void* L, long ldl, const v
                  void* work, void* stream) {
     JOIN(h, stream);
     NEED(h && L && inv_diag && y && x && work, "null pointer");
+    NEED(ldl >= n, "ldl < n");
+    NEED16(L, ldl); NEED16(inv_diag, 0); NEED16(y, 0); NEED16(x, 0); NEED16(work, 0);
     DISPATCH(dtype,
              pg_potrs_vec_t<double>(h, ST(stream), n, (const double*)L, ldl, (const double*)inv_diag, (const double*)y,
                                     (double*)x, (double*)work),
@@ -465,6 +485,8 @@ int pg_trtri(pg_handle h, int dtype, int n, const void* L, long ldl, const void*
     JOIN(h, stream);
     NEED(h && L && inv_diag && Minv, "null pointer");
     NEED(L != Minv, "pg_trtri is out of place");
+    NEED(ldl >= n && ldm >= n, "leading dimension < n");
+    NEED16(L, ldl); NEED16(inv_diag, 0); NEED16(Minv, ldm);
     DISPATCH(dtype,
              pg_trtri_t<double>(h, ST(stream), n, (const double*)L, ldl, (const double*)inv_diag, (double*)Minv, ldm),
              pg_trtri_t<float>(h, ST(stream), n, (const float*)L, ldl, (const float*)inv_diag, (float*)Minv, ldm));
@@ -481,6 +503,7 @@ static int potrs_any(pg_handle h, int dtype, int n, int nrhs, const void* L, lon
     NEED(h && B && X && work && (Minv || (L && inv_diag)), "null pointer");
     NEED(ldb >= nrhs && ldx >= nrhs && (Minv ? ldm >= n : ldl >= n), "leading dimension too small");
     NEED(B != X, "out of place: X must not alias B");
+    NEED16(L, ldl); NEED16(inv_diag, 0); NEED16(Minv, ldm); NEED16(B, ldb); NEED16(X, ldx); NEED16(work, 0);
     DISPATCH(dtype,
              pg_potrs_t<double>(h, ST(stream), n, nrhs, (const double*)L, ldl, (const double*)inv_diag, (const double*)Minv, ldm,
                                 (const double*)B, ldb, (double*)X, ldx, (double*)work, both),
@@ -499,6 +522,8 @@ int pg_trsm_lower(pg_handle h, int dtype, int n, int nrhs, const void* L, long l
 int pg_lauum(pg_handle h, int dtype, int n, const void* Minv, long ldm, void* Kinv, long ldk, void* stream) {
     NEED(h && Minv && Kinv, "null pointer");
     NEED(Minv != Kinv, "pg_lauum is out of place");
+    NEED(ldm >= n && ldk >= n, "leading dimension < n");
+    NEED16(Minv, ldm); NEED16(Kinv, ldk);
     DISPATCH(dtype, pg_lauum_t<double>(h, ST(stream), n, (const double*)Minv, ldm, (double*)Kinv, ldk),
              pg_lauum_t<float>(h, ST(stream), n, (const float*)Minv, ldm, (float*)Kinv, ldk));
 }
@@ -509,6 +534,7 @@ int pg_potri(pg_handle h, int dtype, int n, const void* L, long ldl, const void*
     NEED(h && L && inv_diag && Kinv && work, "null pointer");
     NEED(work != L && work != Kinv, "pg_potri: work must not alias L or Kinv");
     NEED(ldl >= n && ldk >= n, "leading dimension < n");
+    NEED16(work, 0);
     int rc = pg_trtri(h, dtype, n, L, ldl, inv_diag, work, (long)n, stream);
     if (rc) return rc;
     return pg_lauum(h, dtype, n, work, (long)n, Kinv, ldk, stream);
@@ -528,6 +554,8 @@ int pg_trmv(pg_handle h, int dtype, int n, const void* Minv, long ldm, int trans
     NEED(h && Minv && x && y, "null pointer");
     NEED(!trans || work, "transposed product needs a workspace");
     NEED(x != y, "pg_trmv is out of place");
+    NEED(ldm >= n, "ldm < n");
+    NEED16(Minv, ldm); NEED16(x, 0); NEED16(y, 0); NEED16(work, 0);
     DISPATCH(dtype,
              pg_trmv_t<double>(h, ST(stream), n, (const double*)Minv, ldm, trans, (const double*)x, (double*)y, (double*)work),
              pg_trmv_t<float>(h, ST(stream), n, (const float*)Minv, ldm, trans, (const float*)x, (float*)y, (float*)work));
@@ -560,6 +588,7 @@ int pg_alpha_batched(pg_handle h, int dtype, int n, const void* Minv, long ldm, 
     JOIN(h, stream);
     NEED(h && Minv && y && u && alpha && work, "null pointer");
     NEED(ldm >= n && nexp >= 1 && nexp <= 65535, "bad size");
+    NEED16(Minv, ldm); NEEDS16(Minv, m_stride); NEED16(y, y_stride); NEED16(u, u_stride); NEED16(alpha, alpha_stride); NEED16(work, work_stride);
     DISPATCH(dtype,
              pg_alpha_batched_t<double>(ST(stream), n, (const double*)Minv, ldm, m_stride, (const double*)y, y_stride, (double*)u, u_stride,
                                         (double*)alpha, alpha_stride, (double*)work, work_stride, nexp),
@@ -573,6 +602,7 @@ int pg_alpha_nlml_batched(pg_handle h, int dtype, int n_real, int n, const void*
     JOIN(h, stream);
     NEED(h && Minv && y && u && alpha && work && out, "null pointer");
     NEED(n_real > 0 && n_real <= n && ldm >= n && nexp >= 1 && nexp <= 65535, "bad size");
+    NEED16(Minv, ldm); NEEDS16(Minv, m_stride); NEED16(y, y_stride); NEED16(u, u_stride); NEED16(alpha, alpha_stride); NEED16(work, work_stride);
     DISPATCH(dtype,
              pg_alpha_batched_t<double>(ST(stream), n, (const double*)Minv, ldm, m_stride, (const double*)y, y_stride, (double*)u, u_stride,
                                         (double*)alpha, alpha_stride, (double*)work, work_stride, nexp, n_real, out, out_stride),
@@ -587,6 +617,7 @@ int pg_lauum_batched(pg_handle h, int dtype, int n, const void* Minv, long ldm, 
     NEED(Minv != Kinv, "pg_lauum_batched is out of place");
     NEED(nexp >= 1 && nexp <= 65535 && ldm >= n && ldk >= n, "bad size");
     NEED(nexp == 1 || (m_stride >= (long)n * ldm && k_stride >= (long)n * ldk), "experts' matrices overlap");
+    NEED16(Minv, ldm); NEEDS16(Minv, m_stride); NEED16(Kinv, ldk); NEEDS16(Kinv, k_stride);
     ExpBatch eb;
     eb.nexp = nexp; eb.eA = k_stride; eb.eInv = 0; eb.eM = m_stride; eb.eX = 0; eb.ehp = 0;
     DISPATCH(dtype, pg_lauum_t<double>(h, ST(stream), n, (const double*)Minv, ldm, (double*)Kinv, ldk, &eb),
@@ -598,6 +629,8 @@ int pg_nlml_grad_batched(pg_handle h, int dtype, const pg_covspec* spec, const d
                          long grad_stride, int nhp, double* work, long lwork, int nexp, void* stream) {
     JOIN(h, stream);
     NEED(h && hp && X && Kinv && alpha && grad && work, "null pointer");
+    NEED(ldk >= n && ldx >= d, "leading dimension too small");
+    NEED16(Kinv, ldk); NEEDS16(Kinv, k_stride);
     if (check_spec(spec, __func__)) return -1;
     DISPATCH(dtype,
              pg_nlml_grad_t<double>(ST(stream), *spec, hp, (const double*)X, ldx, n, d, (const double*)Kinv, ldk, (const double*)alpha, grad,
@@ -611,6 +644,7 @@ int pg_alpha_nlml_async(pg_handle h, int dtype, int n_real, int n, const void* L
     JOIN(h, stream);
     NEED(h && L && Minv && y && u && alpha && work && out, "null pointer");
     NEED(n_real > 0 && n_real <= n && ldl >= n && ldm >= n, "bad size");
+    NEED16(L, ldl); NEED16(Minv, ldm); NEED16(y, 0); NEED16(u, 0); NEED16(alpha, 0); NEED16(work, 0);
     DISPATCH(dtype,
              pg_alpha_nlml_async_t<double>(h, ST(stream), n_real, n, (const double*)L, ldl, (const double*)Minv, ldm, (const double*)y,
                                            (double*)u, (double*)alpha, (double*)work, out),
@@ -659,6 +693,8 @@ int pg_nlml_grad(pg_handle h, int dtype, const pg_covspec* spec, const double* h
                  void* stream) {
     JOIN(h, stream);
     NEED(h && hp && X && Kinv && alpha && grad && work, "null pointer");
+    NEED(ldk >= n && ldx >= d, "leading dimension too small");
+    NEED16(Kinv, ldk);
     if (check_spec(spec, __func__)) return -1;
     DISPATCH(dtype,
              pg_nlml_grad_t<double>(ST(stream), *spec, hp, (const double*)X, ldx, n, d, (const double*)Kinv, ldk,
@@ -672,6 +708,8 @@ int pg_predict_mean_q(pg_handle h, int dtype, int n_pad, int m_pad, const void* 
     JOIN(h, stream);
     NEED(h && Ks && alpha && mean && work, "null pointer");
     NEED(!q || Minv, "variance needs Minv");
+    NEED(ldks >= m_pad && (!Minv || ldm >= n_pad), "bad leading dimension");
+    NEED16(Ks, ldks); NEED16(Minv, ldm); NEED16(alpha, 0); NEED16(work, 0);
     DISPATCH(dtype,
              pg_predict_mean_q_t<double>(h, ST(stream), n_pad, m_pad, (const double*)Ks, ldks, (const double*)Minv, ldm,
                                          (const double*)alpha, (double*)mean, (double*)q, kss, (double*)work),
@@ -684,6 +722,8 @@ int pg_predict_mean_q_kt(pg_handle h, int dtype, int n_pad, int m_pad, const voi
     JOIN(h, stream);
     NEED(h && Kt && alpha && mean && work, "null pointer");
     NEED(!q || Minv, "variance needs Minv");
+    NEED(ldkt >= n_pad && (!Minv || ldm >= n_pad), "bad leading dimension");
+    NEED16(Kt, ldkt); NEED16(Minv, ldm); NEED16(alpha, 0); NEED16(work, 0);
     DISPATCH(dtype,
              pg_predict_mean_q_kt_t<double>(h, ST(stream), n_pad, m_pad, (const double*)Kt, ldkt, (const double*)Minv, ldm,
                                             (const double*)alpha, (double*)mean, (double*)q, kss, (double*)work),
@@ -701,6 +741,7 @@ int pg_predict_mean_q_kt_batched(pg_handle h, int dtype, int n_pad, int m_pad, c
     if (var && check_spec(spec, __func__)) return -1;
     NEED(nexp >= 1 && nexp <= 65535, "1 <= nexp <= 65535");
     NEED(ldkt >= n_pad && (!Minv || ldm >= n_pad), "bad leading dimension");
+    NEED16(Kt, ldkt); NEEDS16(Kt, kt_stride); NEED16(Minv, ldm); NEEDS16(Minv, m_stride); NEED16(alpha, alpha_stride); NEED16(work, work_stride);
     NEED(nexp == 1 || (mean_stride >= m_pad && (!var || (var_stride >= m_pad && work_stride >= (long)(n_pad / 64) * m_pad))),
          "experts' outputs / workspaces overlap");
     static const pg_covspec none = {};
@@ -717,6 +758,8 @@ int pg_trmm_lower(pg_handle h, int dtype, int n_pad, int m_pad, const void* Minv
                   void* V, long ldv, void* stream) {
     JOIN(h, stream);
     NEED(h && Minv && Ks && V, "null pointer");
+    NEED(ldm >= n_pad && ldks >= m_pad && ldv >= m_pad, "bad leading dimension");
+    NEED16(Minv, ldm); NEED16(Ks, ldks); NEED16(V, ldv);
     DISPATCH(dtype,
              pg_trmm_lower_t<double>(h, ST(stream), n_pad, m_pad, (const double*)Minv, ldm, (const double*)Ks, ldks,
                                      (double*)V, ldv),
@@ -728,6 +771,8 @@ int pg_syrk_tn_sub(pg_handle h, int dtype, int m_pad, int n_pad, const void* V, 
                    void* stream) {
     JOIN(h, stream);
     NEED(h && V && C, "null pointer");
+    NEED(ldv >= m_pad && ldc >= m_pad, "bad leading dimension");
+    NEED16(V, ldv); NEED16(C, ldc);
     AtomicGuard ag(h, C);
     DISPATCH(dtype, pg_syrk_tn_sub_t<double>(h, ST(stream), m_pad, n_pad, (const double*)V, ldv, (double*)C, ldc, lower_only),
              pg_syrk_tn_sub_t<float>(h, ST(stream), m_pad, n_pad, (const float*)V, ldv, (float*)C, ldc, lower_only));
@@ -740,6 +785,7 @@ int pg_trmm_lower_kt_batched(pg_handle h, int dtype, int n_pad, int m_pad, const
     NEED(nexp >= 1 && nexp <= 65535, "1 <= nexp <= 65535");
     NEED(ldm >= n_pad && ldkt >= n_pad && ldvt >= n_pad && Kt != Vt, "bad leading dimension / aliasing");
     NEED(nexp == 1 || vt_stride >= (long)m_pad * ldvt, "experts' outputs overlap");
+    NEED16(Minv, ldm); NEEDS16(Minv, m_stride); NEED16(Kt, ldkt); NEEDS16(Kt, kt_stride); NEED16(Vt, ldvt); NEEDS16(Vt, vt_stride);
     DISPATCH(dtype,
              pg_trmm_lower_kt_t<double>(h, ST(stream), n_pad, m_pad, (const double*)Minv, ldm, m_stride, (const double*)Kt, ldkt, kt_stride,
                                         (double*)Vt, ldvt, vt_stride, nexp),
@@ -754,6 +800,7 @@ int pg_syrk_nt_sub_batched(pg_handle h, int dtype, int m_pad, int n_pad, const v
     NEED(nexp >= 1 && nexp <= 65535, "1 <= nexp <= 65535");
     NEED(ldvt >= n_pad && ldc >= m_pad, "bad leading dimension");
     NEED(nexp == 1 || (vt_stride >= (long)m_pad * ldvt && c_stride >= (long)m_pad * ldc), "experts' matrices overlap");
+    NEED16(Vt, ldvt); NEEDS16(Vt, vt_stride); NEED16(C, ldc); NEEDS16(C, c_stride);
     AtomicGuard ag(h, C);
     DISPATCH(dtype,
              pg_syrk_nt_sub_t<double>(h, ST(stream), m_pad, n_pad, (const double*)Vt, ldvt, vt_stride, (double*)C, ldc, c_stride, nexp, lower_only),
@@ -990,6 +1037,7 @@ int pg_gemm_raw(pg_handle h, int dtype, int variant, int M, int N, int K, double
              variant == GEMM_TT_128 || variant == GEMM_NT_64 || variant == GEMM_NT_64x128 || variant == GEMM_NT_32x64 ||
              variant == GEMM_NT_32x128 || variant == GEMM_TT_64 || variant == GEMM_NT_32x32 || variant == GEMM_TN_64,
          "variant not exposed");
+    NEED16(A, lda); NEED16(B, ldb); NEED16(C, ldc);
     AtomicGuard ag(h, C);
     DISPATCH(dtype, gemm_raw_t<double>(h, variant, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, tri, klo, khi, stream),
              gemm_raw_t<float>(h, variant, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, tri, klo, khi, stream));

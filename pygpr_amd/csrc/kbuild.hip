@@ -364,6 +364,20 @@ __global__ __launch_bounds__(256) void pg_kbuild_kernel(pg_covspec spec, const d
 #undef KB_ARGS
 }
 
+// An empty operand (nr == 0 or nc == 0): the whole output is padding -- identity for a symmetric build (lower tiles only unless
+// mirrored), zeros for a cross build.  One KT x KT tile per workgroup; the point sets are never touched (the tile kernels load at
+// clamped addresses unconditionally, which on an empty operand is a read outside it).
+template <typename T>
+__global__ __launch_bounds__(256) void pg_kbuild_pad_kernel(T* __restrict__ K, long ldk, int c0, int W, int symmetric, int mirror, long eK) {
+    const int tr = blockIdx.x / W, tc = c0 + blockIdx.x % W;
+    if (symmetric && !mirror && tc > tr) return;
+    T* tile = K + (long)blockIdx.y * eK + (long)tr * KT * ldk + (long)tc * KT;
+    for (int idx = threadIdx.x; idx < KT * KT; idx += 256) {
+        const int r = idx / KT, c = idx % KT;
+        tile[(long)r * ldk + c] = (symmetric && tr == tc && r == c) ? (T)1 : (T)0;
+    }
+}
+
 template <typename T>
 int pg_kbuild(hipStream_t st, const pg_covspec& spec, const double* hp, const T* Xr, long ldr, int nr,
               const T* Xc, long ldc, int nc, int d, int symmetric, int lower_only, int accumulate, double jitter, T* K,
@@ -396,6 +410,13 @@ int pg_kbuild(hipStream_t st, const pg_covspec& spec, const double* hp, const T*
         return -2;
     }
     const int c0 = col0 / KT, c1 = col1 / KT, W = c1 - c0, TR = rows_pad / KT;
+    if (nr <= 0 || nc <= 0) {
+        if (accumulate || nexp < 1) return 0;      // a further pass leaves the padding alone
+        hipLaunchKernelGGL((pg_kbuild_pad_kernel<T>), dim3((unsigned)(TR * W), (unsigned)nexp), dim3(256), 0, st, K, ldk, c0, W, symmetric,
+                           mirror ? 1 : 0, eK);
+        PG_CHECK(hipGetLastError());
+        return 0;
+    }
     // strips of up to S tiles of one tile row per workgroup (PG_KB_STRIP; 1 = one tile per workgroup, round 2's granularity)
     // Re-swept with the fast body and the true prefetch (N = 16384, d = 8, lower-only / mirrored, ms): S = 1: 0.326 / 0.561, 2: 0.265 / 0.477,
     // 3: 0.236 / 0.411, 4: 0.224 / 0.406, 5: 0.214 / 0.394, 6: 0.213 / 0.397, 8: 0.233 / 0.424, 12: 0.224 / 0.425, 16: 0.239 / 0.429,

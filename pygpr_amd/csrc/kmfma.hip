@@ -416,7 +416,8 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void pg_grad_mfma_kern
                             base = e;
                             kv = rr * 1.7320508076f * e + e;
                         } else {
-                            sq = __builtin_elementwise_max(sq, (f2){0.0f, 0.0f});
+                            sq.x = sq.x < 0.0f ? 0.0f : sq.x;                          // (select, not max: a NaN stays a NaN)
+                            sq.y = sq.y < 0.0f ? 0.0f : sq.y;
                             const f2 rr = {__builtin_amdgcn_sqrtf(sq.x), __builtin_amdgcn_sqrtf(sq.y)};
                             const f2 t = rr * (-2.2360679775f * 1.44269504088896341f);
                             f2 e = {__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
