@@ -30,89 +30,54 @@ class CovSpec(C.Structure):
     ]
 
 
-_vp, _i, _l, _d = C.c_void_p, C.c_int, C.c_long, C.c_double
-_SIGS = {
-    "pg_version": (C.c_int, []),
-    "pg_last_error": (C.c_char_p, []),
-    "pg_create": (_i, [C.POINTER(_vp)]),
-    "pg_destroy": (_i, [_vp]),
-    "pg_kernel_build": (_i, [_vp, _i, C.POINTER(CovSpec), _vp, _vp, _l, _i, _vp, _l, _i, _i, _i, _i, _d, _vp, _l, _i, _i, _vp]),
-    "pg_kernel_build_batched": (_i, [_vp, _i, C.POINTER(CovSpec), _vp, _l, _vp, _l, _l, _i, _vp, _l, _l, _i, _i, _i, _d, _vp, _l, _l, _i, _i, _i, _vp]),
-    "pg_predict_mean_q_kt_batched": (_i, [_vp, _i, _i, _i, _vp, _l, _l, _vp, _l, _l, _vp, _l, _vp, _l, _vp, _l, C.POINTER(CovSpec), _vp, _l, _vp, _l,
-                                          _i, _vp]),
-    "pg_grbcm_local_terms_batched": (_i, [_vp, _i, _i, _vp, _l, _vp, _l, _vp, _i, _i, _i, _vp, _l, _vp, _vp, _l, _vp]),
-    "pg_kernel_grad_build": (_i, [_vp, _i, C.POINTER(CovSpec), _vp, _vp, _l, _i, _i, _vp, _vp]),
-    "pg_potrf_worksize": (_l, [_i, _i]),
-    "pg_potrf": (_i, [_vp, _i, _i, _vp, _l, _vp, _vp, _vp]),
-    "pg_potrf_trtri": (_i, [_vp, _i, _i, _vp, _l, _vp, _vp, _vp, _l, _vp]),
-    "pg_potrs_vec_worksize": (_l, [_i, _i]),
-    "pg_potrs_vec": (_i, [_vp, _i, _i, _vp, _l, _vp, _vp, _vp, _vp, _vp]),
-    "pg_trtri": (_i, [_vp, _i, _i, _vp, _l, _vp, _vp, _l, _vp]),
-    "pg_lauum": (_i, [_vp, _i, _i, _vp, _l, _vp, _l, _vp]),
-    "pg_potri": (_i, [_vp, _i, _i, _vp, _l, _vp, _vp, _l, _vp, _vp]),
-    "pg_logdet": (_i, [_vp, _i, _i, _vp, _l, _vp, _vp]),
-    "pg_trmv": (_i, [_vp, _i, _i, _vp, _l, _i, _vp, _vp, _vp, _vp]),
-    "pg_alpha_nlml_batched": (_i, [_vp, _i, _i, _i, _vp, _l, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _l, _i, _vp]),
-    "pg_lauum_batched": (_i, [_vp, _i, _i, _vp, _l, _l, _vp, _l, _l, _i, _vp]),
-    "pg_nlml_grad_batched": (_i, [_vp, _i, C.POINTER(CovSpec), _vp, _l, _vp, _l, _l, _i, _i, _vp, _l, _l, _vp, _l, _vp, _l, _i, _vp, _l, _i, _vp]),
-    "pg_alpha_nlml_async": (_i, [_vp, _i, _i, _i, _vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "pg_chol_append_worksize": (_l, [_i, _i, _i]),
-    "pg_chol_append": (_i, [_vp, _i, _i, _i, _i, _vp, _l, _vp, _vp, _l, _vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "pg_nlml_value": (_i, [_vp, _i, _i, _vp, _l, _vp, _vp, _vp, _vp]),
-    "pg_nlml_grad_worksize": (_l, [_i, _i]),
-    "pg_nlml_grad": (_i, [_vp, _i, C.POINTER(CovSpec), _vp, _vp, _l, _i, _i, _vp, _l, _vp, _vp, _i, _vp, _l, _vp]),
-    "pg_kernel_xgrad_worksize": (_l, [_vp, _i, _i, _i, _i]),
-    "pg_kernel_xgrad": (_i, [_vp, _i, C.POINTER(CovSpec), _vp, _l, _vp, _l, _l, _i, _vp, _l, _l, _i, _i, _vp, _l, _vp, _l, _l, _vp, _l, _l, _i,
-                             _vp, _l, _l, _i, _vp, _l, _i, _vp]),
-    "pg_predict_mean_q": (_i, [_vp, _i, _i, _i, _vp, _l, _vp, _l, _vp, _vp, _vp, _d, _vp, _vp]),
-    "pg_predict_mean_q_kt": (_i, [_vp, _i, _i, _i, _vp, _l, _vp, _l, _vp, _vp, _vp, _d, _vp, _vp]),
-    "pg_trmm_lower": (_i, [_vp, _i, _i, _i, _vp, _l, _vp, _l, _vp, _l, _vp]),
-    "pg_syrk_tn_sub": (_i, [_vp, _i, _i, _i, _vp, _l, _vp, _l, _i, _vp]),
-    "pg_trmm_lower_kt_batched": (_i, [_vp, _i, _i, _i, _vp, _l, _l, _vp, _l, _l, _vp, _l, _l, _i, _vp]),
-    "pg_syrk_nt_sub_batched": (_i, [_vp, _i, _i, _i, _vp, _l, _l, _vp, _l, _l, _i, _i, _vp]),
-    "pg_grbcm_local_terms": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _l, _vp, _vp, _vp]),
-    "pg_grbcm_finish": (_i, [_vp, _i, _i, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "pg_grbcm_weighted_prec": (_i, [_vp, _i, _i, _i, _vp, _l, _vp, _vp, _l, _i, _vp]),
-    "pg_symmetrize": (_i, [_vp, _i, _i, _vp, _l, _vp]),
-    "pg_grbcm_finish_full": (_i, [_vp, _i, _i, _vp, _l, _vp, _vp, _vp, _l, _vp, _vp]),
-    "pg_sqdist_argmin": (_i, [_vp, _i, _vp, _l, _i, _vp, _l, _i, _i, _vp, _l, _vp, _vp]),
-    "pg_tril": (_i, [_vp, _i, _i, _vp, _l, _vp]),
-    "pg_set_lookahead": (_i, [_vp, _i]),
-    "pg_set_outer_panel": (_i, [_vp, _i]),
-    "pg_set_recursive_split": (_i, [_vp, _i]),
-    "pg_profile": (_i, [_vp, _i]),
-    "pg_profile_read": (_i, [_vp, C.POINTER(_d), C.POINTER(_d), C.POINTER(_l)]),
-    "pg_build_potrf_trtri": (_i, [_vp, _i, C.POINTER(CovSpec), _vp, _vp, _l, _i, _i, _d, _vp, _l, _i, _vp, _vp, _vp, _l, _vp]),
-    "pg_build_potrf_trtri_checked": (_i, [_vp, _i, C.POINTER(CovSpec), _vp, _vp, _l, _i, _i, _d, _vp, _l, _i, _vp, _vp, _vp, _l, _vp,
-                                          C.POINTER(_i)]),
-    "pg_build_potrf_trtri_batched": (_i, [_vp, _i, C.POINTER(CovSpec), _vp, _l, _vp, _l, _l, _i, _i, _d, _vp, _l, _l, _i, _vp, _l, _vp, _vp,
-                                          _l, _l, _i, _vp]),
-    "pg_alpha_batched": (_i, [_vp, _i, _i, _vp, _l, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _l, _i, _vp]),
-    "pg_potrs_worksize": (_l, [_i, _i, _i, _i]),
-    "pg_potrs": (_i, [_vp, _i, _i, _i, _vp, _l, _vp, _vp, _l, _vp, _l, _vp, _l, _vp, _vp]),
-    "pg_trsm_lower": (_i, [_vp, _i, _i, _i, _vp, _l, _vp, _vp, _l, _vp, _l, _vp, _l, _vp, _vp]),
-    "pg_set_spin_budget": (_i, [_vp, _l]),
-    "pg_set_rearm_after": (_i, [_vp, _i]),
-    "pg_chain_rearms": (_i, [_vp]),
-    "pg_wait_budget_us": (_l, [_vp, _i]),
-    "pg_spin_probe": (_i, [_vp, _i, _vp, _vp]),
-    "pg_chain_timeouts": (_i, [_vp]),
-    "pg_last_coupled_panels": (_i, [_vp]),
-    "pg_set_coupled_chain": (_i, [_vp, _i]),
-    "pg_coupled_chain": (_i, [_vp]),
-    "pg_leaf_raw": (_i, [_vp, _i, _vp, _l, _vp, _l, _vp, _vp]),
-    "pg_rowstep_raw": (_i, [_vp, _i, _i, _vp, _l, _i, _i, _vp, _vp, _vp, _vp]),
-    "pg_gemm_raw": (_i, [_vp, _i, _i, _i, _i, _i, _d, _vp, _l, _vp, _l, _d, _vp, _l, _i, _i, _i, _vp]),
-}
+# The vocabulary of include/pygpr_hip.h.  Scalars keep their width; a pg_handle and every pointer travel as void* (c_void_p takes
+# None, an address and byref(...) alike), the covariance spec keeps its struct type.
+_RESTYPES = {"int": C.c_int, "long": C.c_long, "const char*": C.c_char_p}
+_ARGTYPES = {"int": C.c_int, "long": C.c_long, "double": C.c_double, "const pg_covspec*": C.POINTER(CovSpec)}
+_ARGTYPES.update((t, C.c_void_p) for t in ("pg_handle", "pg_handle*", "void*", "const void*", "double*", "const double*", "int*", "long*"))
 
-_lib = None
+
+def _strip_comments(text):
+    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
 
 
 def header_symbols():
     """Names of every function declared in include/pygpr_hip.h."""
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(pg_[a-z_0-9]+)\s*\(", text)))
+    return sorted(set(re.findall(r"\b(pg_[a-z_0-9]+)\s*\(", _strip_comments(open(HEADER).read()))))
+
+
+def parse_prototypes(text):
+    """name -> (return type, [parameter types]) of every `pg_*` prototype in the C text, the types as spelled there with the white
+    space normalised ("const void*")."""
+    def norm(t):
+        return re.sub(r"\s*\*", "*", " ".join(t.split()))
+
+    protos = {}
+    for ret, name, params in re.findall(r"([\w \t*]+?)\b(pg_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", _strip_comments(text)):
+        types = []
+        for p in [q.strip() for q in params.split(",")] if params.strip() != "void" else []:
+            m = re.fullmatch(r"(.*[\s*])[A-Za-z_]\w*", p, flags=re.S)      # a type, then the parameter's name
+            if not m:
+                raise ValueError("%s: cannot read parameter %r" % (name, p))
+            types.append(norm(m.group(1)))
+        protos[name] = (norm(ret), types)
+    return protos
+
+
+def signatures(protos):
+    """name -> (restype, argtypes) for ctypes.  A type outside the header's vocabulary is an error, never a guess."""
+    sigs = {}
+    for name, (ret, params) in protos.items():
+        for t, table in [(ret, _RESTYPES)] + [(p, _ARGTYPES) for p in params]:
+            if t not in table:
+                raise ValueError("%s: no ctypes mapping for the type %r" % (name, t))
+        sigs[name] = (_RESTYPES[ret], [_ARGTYPES[p] for p in params])
+    return sigs
+
+
+_SIGS = signatures(parse_prototypes(open(HEADER).read()))
+
+_lib = None
 
 
 def load(check_symbols=False):

@@ -59,6 +59,10 @@ class HipOps:
     def _st(self):
         return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
+    def _call(self, name, *args):
+        """lib.<name>(handle, *args); a non-zero status raises with the library's text under that name."""
+        _lib.check(getattr(self.lib, name)(self.h, *args), name)
+
     def _chk(self, *ts):
         for t in ts:
             if t is None:
@@ -86,11 +90,9 @@ class HipOps:
         for i, sp in enumerate(_passes(spec)):
             if i > 0 and xc is not None and sp.ncomp == 0:
                 continue                      # a noise-only pass adds nothing to a cross build (covar.py:243)
-            _lib.check(self.lib.pg_kernel_build(
-                self.h, _code(out.dtype), C.byref(sp), _p(hp), _p(xr), xr.stride(0), nr,
-                _p(xc), xc.stride(0) if xc is not None else 0, nc, d, int(lower_only), int(i > 0),
-                float(jitter) if i == 0 else 0.0, _p(out), out.stride(0), out.shape[0], out.shape[1], self._st()),
-                "pg_kernel_build")
+            self._call("pg_kernel_build", _code(out.dtype), C.byref(sp), _p(hp), _p(xr), xr.stride(0), nr, _p(xc),
+                       xc.stride(0) if xc is not None else 0, nc, d, int(lower_only), int(i > 0), float(jitter) if i == 0 else 0.0, _p(out),
+                       out.stride(0), out.shape[0], out.shape[1], self._st())
         return out
 
     def kernel_build_batched(self, spec, hp_all, xr, xc_all, out_all, lower_only=False, jitter=0.0):
@@ -110,10 +112,9 @@ class HipOps:
             ldc = xc_all.stride(-2)
         else:
             nc, xc_stride, ldc = nr, 0, 0
-        _lib.check(self.lib.pg_kernel_build_batched(
-            self.h, _code(out_all.dtype), C.byref(passes[0]), _p(hp_all), hp_all.stride(0) if hp_all.shape[0] > 1 else 0, _p(xr), xr.stride(-2),
-            xr_stride, nr, _p(xc_all), ldc, xc_stride, nc, d, int(lower_only), float(jitter), _p(out_all), out_all.stride(1),
-            out_all.stride(0), out_all.shape[1], out_all.shape[2], nexp, self._st()), "pg_kernel_build_batched")
+        self._call("pg_kernel_build_batched", _code(out_all.dtype), C.byref(passes[0]), _p(hp_all), hp_all.stride(0) if hp_all.shape[0] > 1 else 0,
+                   _p(xr), xr.stride(-2), xr_stride, nr, _p(xc_all), ldc, xc_stride, nc, d, int(lower_only), float(jitter), _p(out_all),
+                   out_all.stride(1), out_all.stride(0), out_all.shape[1], out_all.shape[2], nexp, self._st())
         return out_all
 
     def kernel_grad_build(self, spec, hp, x, out):
@@ -121,8 +122,7 @@ class HipOps:
         self._chk(hp, x, out)
         n, d = x.shape
         for sp in _passes(spec):              # passes write the slabs of different children
-            _lib.check(self.lib.pg_kernel_grad_build(self.h, _code(out.dtype), C.byref(sp), _p(hp), _p(x), x.stride(0),
-                                                     n, d, _p(out), self._st()), "pg_kernel_grad_build")
+            self._call("pg_kernel_grad_build", _code(out.dtype), C.byref(sp), _p(hp), _p(x), x.stride(0), n, d, _p(out), self._st())
         return out
 
     def sqdist(self, xr, xc, out):
@@ -142,8 +142,7 @@ class HipOps:
 
     def potrf(self, a, invd, info):
         self._chk(a, invd, info)
-        _lib.check(self.lib.pg_potrf(self.h, _code(a.dtype), a.shape[0], _p(a), a.stride(0), _p(invd), _p(info),
-                                     self._st()), "pg_potrf")
+        self._call("pg_potrf", _code(a.dtype), a.shape[0], _p(a), a.stride(0), _p(invd), _p(info), self._st())
 
     def build_factor(self, spec, hp, x, a, invd, info, minv=None, jitter=JITTER):
         """a <- k(x, x) + jitter I (lower tiles), then its Cholesky factor in place (and minv <- L^-1 if given): kernel_build
@@ -156,10 +155,8 @@ class HipOps:
         self._chk(hp, x, a, invd, info, minv)
         assert hp.dtype == torch.float64
         n, d = x.shape
-        _lib.check(self.lib.pg_build_potrf_trtri(
-            self.h, _code(a.dtype), C.byref(passes[0]), _p(hp), _p(x), x.stride(0), n, d, float(jitter), _p(a), a.stride(0),
-            a.shape[0], _p(invd), _p(info), _p(minv), minv.stride(0) if minv is not None else 0, self._st()),
-            "pg_build_potrf_trtri")
+        self._call("pg_build_potrf_trtri", _code(a.dtype), C.byref(passes[0]), _p(hp), _p(x), x.stride(0), n, d, float(jitter), _p(a), a.stride(0),
+                   a.shape[0], _p(invd), _p(info), _p(minv), minv.stride(0) if minv is not None else 0, self._st())
 
     def build_factor_batched(self, spec, hp_all, x_all, x_stride, a_all, invd_all, info_all, minv_all=None, jitter=JITTER):
         """The same for nexp experts of one size in ONE call (pg_build_potrf_trtri_batched): hp_all [nexp, nhp], x_all [nexp | 1, n, d]
@@ -172,11 +169,10 @@ class HipOps:
         assert hp_all.dtype == torch.float64 and info_all.dtype == torch.int32
         nexp, n_pad = a_all.shape[0], a_all.shape[1]
         n, d = x_all.shape[-2], x_all.shape[-1]
-        _lib.check(self.lib.pg_build_potrf_trtri_batched(
-            self.h, _code(a_all.dtype), C.byref(passes[0]), _p(hp_all), hp_all.stride(0), _p(x_all), x_all.stride(-2), int(x_stride),
-            n, d, float(jitter), _p(a_all), a_all.stride(1), a_all.stride(0), n_pad, _p(invd_all), invd_all.stride(0), _p(info_all),
-            _p(minv_all), minv_all.stride(1) if minv_all is not None else 0, minv_all.stride(0) if minv_all is not None else 0,
-            nexp, self._st()), "pg_build_potrf_trtri_batched")
+        self._call("pg_build_potrf_trtri_batched", _code(a_all.dtype), C.byref(passes[0]), _p(hp_all), hp_all.stride(0), _p(x_all), x_all.stride(-2),
+                   int(x_stride), n, d, float(jitter), _p(a_all), a_all.stride(1), a_all.stride(0), n_pad, _p(invd_all), invd_all.stride(0),
+                   _p(info_all), _p(minv_all), minv_all.stride(1) if minv_all is not None else 0, minv_all.stride(0) if minv_all is not None else 0,
+                   nexp, self._st())
 
     def potrf_trtri_batched(self, a_all, invd_all, info_all, minv_all=None):
         """Cholesky in place (+ minv_all <- L^-1) of nexp matrices that are already in a_all [nexp, n_pad, n_pad]: the batched call
@@ -184,34 +180,30 @@ class HipOps:
         self._chk(a_all, invd_all, info_all, minv_all)
         assert info_all.dtype == torch.int32
         nexp, n_pad = a_all.shape[0], a_all.shape[1]
-        _lib.check(self.lib.pg_build_potrf_trtri_batched(
-            self.h, _code(a_all.dtype), None, None, 0, None, 0, 0, n_pad, 0, 0.0, _p(a_all), a_all.stride(1), a_all.stride(0), n_pad,
-            _p(invd_all), invd_all.stride(0), _p(info_all), _p(minv_all), minv_all.stride(1) if minv_all is not None else 0,
-            minv_all.stride(0) if minv_all is not None else 0, nexp, self._st()), "pg_build_potrf_trtri_batched")
+        self._call("pg_build_potrf_trtri_batched", _code(a_all.dtype), None, None, 0, None, 0, 0, n_pad, 0, 0.0, _p(a_all), a_all.stride(1),
+                   a_all.stride(0), n_pad, _p(invd_all), invd_all.stride(0), _p(info_all), _p(minv_all),
+                   minv_all.stride(1) if minv_all is not None else 0, minv_all.stride(0) if minv_all is not None else 0, nexp, self._st())
 
     def alpha_batched(self, minv_all, y_all, u_all, alpha_all, work_all):
         """alpha_e = minv_e^T (minv_e y_e) for all experts in three launches; y_all [nexp | 1, n_pad] (one row: shared targets),
         u_all [nexp, n_pad], work_all [nexp, (n_pad/256) n_pad]."""
         self._chk(minv_all, y_all, u_all, alpha_all, work_all)
-        _lib.check(self.lib.pg_alpha_batched(self.h, _code(minv_all.dtype), minv_all.shape[1], _p(minv_all), minv_all.stride(1),
-                                             minv_all.stride(0), _p(y_all), y_all.stride(0) if y_all.shape[0] > 1 else 0, _p(u_all), u_all.stride(0), _p(alpha_all),
-                                             alpha_all.stride(0), _p(work_all), work_all.stride(0), minv_all.shape[0], self._st()),
-                   "pg_alpha_batched")
+        self._call("pg_alpha_batched", _code(minv_all.dtype), minv_all.shape[1], _p(minv_all), minv_all.stride(1), minv_all.stride(0), _p(y_all),
+                   y_all.stride(0) if y_all.shape[0] > 1 else 0, _p(u_all), u_all.stride(0), _p(alpha_all), alpha_all.stride(0), _p(work_all),
+                   work_all.stride(0), minv_all.shape[0], self._st())
 
     def alpha_nlml_batched(self, minv_all, y_all, u_all, alpha_all, work_all, n, out_all):
         """alpha_e and NLML_e for all experts (pg_alpha_nlml_batched): out_all [nexp, >= 1] float64 receives NLML_e in column 0."""
         self._chk(minv_all, y_all, u_all, alpha_all, work_all, None)
         assert out_all.dtype == torch.float64 and out_all.is_cuda
-        _lib.check(self.lib.pg_alpha_nlml_batched(
-            self.h, _code(minv_all.dtype), int(n), minv_all.shape[1], _p(minv_all), minv_all.stride(1), minv_all.stride(0), _p(y_all),
-            y_all.stride(0) if y_all.shape[0] > 1 else 0, _p(u_all), u_all.stride(0), _p(alpha_all), alpha_all.stride(0), _p(work_all),
-            work_all.stride(0), _p(out_all), out_all.stride(0), minv_all.shape[0], self._st()), "pg_alpha_nlml_batched")
+        self._call("pg_alpha_nlml_batched", _code(minv_all.dtype), int(n), minv_all.shape[1], _p(minv_all), minv_all.stride(1), minv_all.stride(0),
+                   _p(y_all), y_all.stride(0) if y_all.shape[0] > 1 else 0, _p(u_all), u_all.stride(0), _p(alpha_all), alpha_all.stride(0),
+                   _p(work_all), work_all.stride(0), _p(out_all), out_all.stride(0), minv_all.shape[0], self._st())
 
     def lauum_batched(self, minv_all, kinv_all):
         self._chk(minv_all, kinv_all)
-        _lib.check(self.lib.pg_lauum_batched(self.h, _code(minv_all.dtype), minv_all.shape[1], _p(minv_all), minv_all.stride(1),
-                                             minv_all.stride(0), _p(kinv_all), kinv_all.stride(1), kinv_all.stride(0), minv_all.shape[0],
-                                             self._st()), "pg_lauum_batched")
+        self._call("pg_lauum_batched", _code(minv_all.dtype), minv_all.shape[1], _p(minv_all), minv_all.stride(1), minv_all.stride(0), _p(kinv_all),
+                   kinv_all.stride(1), kinv_all.stride(0), minv_all.shape[0], self._st())
 
     def nlml_grad_batched(self, spec, hp_all, x_all, x_stride, n, kinv_all, alpha_all, grad_all, work):
         """grad_all [nexp, >= nhp] (a view with row stride: e.g. outs[:, 1:]) <- every expert's gradient in two launches."""
@@ -220,23 +212,20 @@ class HipOps:
         assert grad_all.dtype == torch.float64 and grad_all.is_cuda and grad_all.stride(-1) == 1
         nexp, nhp = kinv_all.shape[0], hp_all.shape[-1]
         for sp in passes:
-            _lib.check(self.lib.pg_nlml_grad_batched(
-                self.h, _code(kinv_all.dtype), C.byref(sp), _p(hp_all), hp_all.stride(0), _p(x_all), x_all.stride(-2), int(x_stride), int(n),
-                x_all.shape[-1], _p(kinv_all), kinv_all.stride(1), kinv_all.stride(0), _p(alpha_all), alpha_all.stride(0), _p(grad_all),
-                grad_all.stride(0), nhp, _p(work), work.numel(), nexp, self._st()), "pg_nlml_grad_batched")
+            self._call("pg_nlml_grad_batched", _code(kinv_all.dtype), C.byref(sp), _p(hp_all), hp_all.stride(0), _p(x_all), x_all.stride(-2),
+                       int(x_stride), int(n), x_all.shape[-1], _p(kinv_all), kinv_all.stride(1), kinv_all.stride(0), _p(alpha_all),
+                       alpha_all.stride(0), _p(grad_all), grad_all.stride(0), nhp, _p(work), work.numel(), nexp, self._st())
 
     def potrf_trtri(self, a, invd, info, minv):
         """Cholesky in place + minv = L^-1, fused so that part of the inverse overlaps the factorisation's tail."""
         self._chk(a, invd, info, minv)
-        _lib.check(self.lib.pg_potrf_trtri(self.h, _code(a.dtype), a.shape[0], _p(a), a.stride(0), _p(invd), _p(info),
-                                           _p(minv), minv.stride(0), self._st()), "pg_potrf_trtri")
+        self._call("pg_potrf_trtri", _code(a.dtype), a.shape[0], _p(a), a.stride(0), _p(invd), _p(info), _p(minv), minv.stride(0), self._st())
 
     def potrs_vec(self, chol, invd, y, x, work=None):
         if work is None:
             work = self.empty(self.lib.pg_potrs_vec_worksize(_code(chol.dtype), chol.shape[0]), dtype=chol.dtype)
         self._chk(chol, invd, y, x, work)
-        _lib.check(self.lib.pg_potrs_vec(self.h, _code(chol.dtype), chol.shape[0], _p(chol), chol.stride(0), _p(invd),
-                                         _p(y), _p(x), _p(work), self._st()), "pg_potrs_vec")
+        self._call("pg_potrs_vec", _code(chol.dtype), chol.shape[0], _p(chol), chol.stride(0), _p(invd), _p(y), _p(x), _p(work), self._st())
 
     def potrs(self, chol, invd, b, minv=None, triangular_only=False):
         """x = K^-1 b (or L^-1 b) for a matrix right-hand side b [n_pad, nrhs_pad] (nrhs_pad a multiple of 128): pg_potrs / pg_trsm_lower."""
@@ -244,10 +233,8 @@ class HipOps:
         x = self.empty(n, nrhs, dtype=b.dtype)
         work = self.empty(self.lib.pg_potrs_worksize(_code(b.dtype), n, nrhs, int(minv is not None)), dtype=b.dtype)
         self._chk(chol, invd, b, minv, x, work)
-        fn = self.lib.pg_trsm_lower if triangular_only else self.lib.pg_potrs
-        _lib.check(fn(self.h, _code(b.dtype), n, nrhs, _p(chol), chol.stride(0) if chol is not None else 0, _p(invd), _p(minv),
-                      minv.stride(0) if minv is not None else 0, _p(b), b.stride(0), _p(x), x.stride(0), _p(work), self._st()),
-                   "pg_trsm_lower" if triangular_only else "pg_potrs")
+        self._call("pg_trsm_lower" if triangular_only else "pg_potrs", _code(b.dtype), n, nrhs, _p(chol), chol.stride(0) if chol is not None else 0,
+                   _p(invd), _p(minv), minv.stride(0) if minv is not None else 0, _p(b), b.stride(0), _p(x), x.stride(0), _p(work), self._st())
         return x
 
     def potri(self, chol, invd, kinv, work=None):
@@ -256,27 +243,23 @@ class HipOps:
         if work is None:
             work = self.empty(n, n, dtype=chol.dtype)
         self._chk(chol, invd, kinv, work)
-        _lib.check(self.lib.pg_potri(self.h, _code(chol.dtype), n, _p(chol), chol.stride(0), _p(invd), _p(kinv), kinv.stride(0),
-                                     _p(work), self._st()), "pg_potri")
+        self._call("pg_potri", _code(chol.dtype), n, _p(chol), chol.stride(0), _p(invd), _p(kinv), kinv.stride(0), _p(work), self._st())
 
     def logdet(self, chol, n, out):
         self._chk(chol, out)
-        _lib.check(self.lib.pg_logdet(self.h, _code(chol.dtype), int(n), _p(chol), chol.stride(0), _p(out), self._st()), "pg_logdet")
+        self._call("pg_logdet", _code(chol.dtype), int(n), _p(chol), chol.stride(0), _p(out), self._st())
 
     def trtri(self, chol, invd, minv):
         self._chk(chol, invd, minv)
-        _lib.check(self.lib.pg_trtri(self.h, _code(chol.dtype), chol.shape[0], _p(chol), chol.stride(0), _p(invd),
-                                     _p(minv), minv.stride(0), self._st()), "pg_trtri")
+        self._call("pg_trtri", _code(chol.dtype), chol.shape[0], _p(chol), chol.stride(0), _p(invd), _p(minv), minv.stride(0), self._st())
 
     def lauum(self, minv, kinv):
         self._chk(minv, kinv)
-        _lib.check(self.lib.pg_lauum(self.h, _code(minv.dtype), minv.shape[0], _p(minv), minv.stride(0), _p(kinv),
-                                     kinv.stride(0), self._st()), "pg_lauum")
+        self._call("pg_lauum", _code(minv.dtype), minv.shape[0], _p(minv), minv.stride(0), _p(kinv), kinv.stride(0), self._st())
 
     def trmv(self, minv, x, y, trans, work=None):
         self._chk(minv, x, y, work)
-        _lib.check(self.lib.pg_trmv(self.h, _code(minv.dtype), minv.shape[0], _p(minv), minv.stride(0), int(trans),
-                                    _p(x), _p(y), _p(work), self._st()), "pg_trmv")
+        self._call("pg_trmv", _code(minv.dtype), minv.shape[0], _p(minv), minv.stride(0), int(trans), _p(x), _p(y), _p(work), self._st())
 
     def chol_append_worksize(self, n_pad, k, dtype):
         return int(self.lib.pg_chol_append_worksize(_code(dtype), int(n_pad), int(k)))
@@ -288,27 +271,24 @@ class HipOps:
         self._chk(chol, invd, minv, kt, knn, y_new, u, alpha, work, info)
         assert info.dtype == torch.int32
         n_pad = chol.shape[0]
-        _lib.check(self.lib.pg_chol_append(
-            self.h, _code(chol.dtype), int(n), int(k), n_pad, _p(chol), chol.stride(0), _p(invd), _p(minv), minv.stride(0), _p(kt),
-            kt.stride(0), _p(knn), knn.stride(0), _p(y_new), _p(u), _p(alpha), _p(work), _p(info), self._st()), "pg_chol_append")
+        self._call("pg_chol_append", _code(chol.dtype), int(n), int(k), n_pad, _p(chol), chol.stride(0), _p(invd), _p(minv), minv.stride(0), _p(kt),
+                   kt.stride(0), _p(knn), knn.stride(0), _p(y_new), _p(u), _p(alpha), _p(work), _p(info), self._st())
 
     def tril(self, a, n):
         self._chk(a)
-        _lib.check(self.lib.pg_tril(self.h, _code(a.dtype), n, _p(a), a.stride(0), self._st()), "pg_tril")
+        self._call("pg_tril", _code(a.dtype), n, _p(a), a.stride(0), self._st())
 
     # -- NLML ---------------------------------------------------------------------------------
     def nlml_value(self, chol, y, alpha, n, out):
         self._chk(chol, y, alpha, out)
-        _lib.check(self.lib.pg_nlml_value(self.h, _code(chol.dtype), n, _p(chol), chol.stride(0), _p(y), _p(alpha),
-                                          _p(out), self._st()), "pg_nlml_value")
+        self._call("pg_nlml_value", _code(chol.dtype), n, _p(chol), chol.stride(0), _p(y), _p(alpha), _p(out), self._st())
 
     def alpha_nlml_async(self, chol, minv, y, u, alpha, work, n, out):
         """alpha = minv^T (minv y) and out[0] = NLML (out[1]: log det, scratch), overlapped with the next pg_lauum."""
         self._chk(chol, minv, y, u, alpha, work, out)
         assert out.dtype == torch.float64 and out.numel() >= 2
-        _lib.check(self.lib.pg_alpha_nlml_async(self.h, _code(chol.dtype), int(n), chol.shape[0], _p(chol), chol.stride(0), _p(minv),
-                                                minv.stride(0), _p(y), _p(u), _p(alpha), _p(work), _p(out), self._st()),
-                   "pg_alpha_nlml_async")
+        self._call("pg_alpha_nlml_async", _code(chol.dtype), int(n), chol.shape[0], _p(chol), chol.stride(0), _p(minv), minv.stride(0), _p(y), _p(u),
+                   _p(alpha), _p(work), _p(out), self._st())
 
     def nlml_grad_worksize(self, n, nhp):
         return self.lib.pg_nlml_grad_worksize(n, nhp)
@@ -316,9 +296,8 @@ class HipOps:
     def nlml_grad(self, spec, hp, x, n, kinv, alpha, grad, work):
         self._chk(hp, x, kinv, alpha, grad, work)
         for sp in _passes(spec):              # each pass fills the gradient entries of its own children
-            _lib.check(self.lib.pg_nlml_grad(self.h, _code(kinv.dtype), C.byref(sp), _p(hp), _p(x), x.stride(0), n,
-                                             x.shape[1], _p(kinv), kinv.stride(0), _p(alpha), _p(grad), grad.numel(),
-                                             _p(work), work.numel(), self._st()), "pg_nlml_grad")
+            self._call("pg_nlml_grad", _code(kinv.dtype), C.byref(sp), _p(hp), _p(x), x.stride(0), n, x.shape[1], _p(kinv), kinv.stride(0), _p(alpha),
+                       _p(grad), grad.numel(), _p(work), work.numel(), self._st())
 
     # -- derivatives in the test points -------------------------------------------------------
     def kernel_xgrad(self, spec, hp, xq, z, u=None, b=None, out_u=None, out_b=None, trans_b=False, accumulate=False):
@@ -356,13 +335,12 @@ class HipOps:
 
         work = self.empty(max(1, int(self.lib.pg_kernel_xgrad_worksize(self.h, m, n, d, nexp))), dtype=torch.float64)
         for i, sp in enumerate(_passes(spec)):
-            _lib.check(self.lib.pg_kernel_xgrad(
-                self.h, _code(dt), C.byref(sp), _p(hp_all), hp_all.stride(0) if hp_all.shape[0] > 1 else 0, _p(xq), xq.stride(-2), es(xq), m,
-                _p(z_all), z_all.stride(-2), es(z_all), n, d, _p(u_all), u_all.stride(0) if (u_all is not None and u_all.shape[0] > 1) else 0,
-                _p(out_u), out_u.stride(1) if out_u is not None else 0, out_u.stride(0) if out_u is not None else 0,
-                _p(b_all), b_all.stride(-2) if b_all is not None else 0, es(b_all), int(bool(trans_b)),
-                _p(out_b), out_b.stride(1) if out_b is not None else 0, out_b.stride(0) if out_b is not None else 0,
-                int(bool(accumulate) or i > 0), _p(work), work.numel(), nexp, self._st()), "pg_kernel_xgrad")
+            self._call("pg_kernel_xgrad", _code(dt), C.byref(sp), _p(hp_all), hp_all.stride(0) if hp_all.shape[0] > 1 else 0, _p(xq), xq.stride(-2),
+                       es(xq), m, _p(z_all), z_all.stride(-2), es(z_all), n, d, _p(u_all),
+                       u_all.stride(0) if (u_all is not None and u_all.shape[0] > 1) else 0, _p(out_u), out_u.stride(1) if out_u is not None else 0,
+                       out_u.stride(0) if out_u is not None else 0, _p(b_all), b_all.stride(-2) if b_all is not None else 0, es(b_all),
+                       int(bool(trans_b)), _p(out_b), out_b.stride(1) if out_b is not None else 0, out_b.stride(0) if out_b is not None else 0,
+                       int(bool(accumulate) or i > 0), _p(work), work.numel(), nexp, self._st())
         return out_u, out_b
 
     # -- prediction ---------------------------------------------------------------------------
@@ -370,19 +348,15 @@ class HipOps:
         """mean = Ks^T alpha; var = kss - colsum((Minv Ks)^2) (var None: mean only)."""
         q = var
         self._chk(ks, minv, alpha, mean, q, work)
-        _lib.check(self.lib.pg_predict_mean_q(self.h, _code(ks.dtype), ks.shape[0], ks.shape[1], _p(ks), ks.stride(0),
-                                              _p(minv), minv.stride(0) if minv is not None else 0, _p(alpha),
-                                              _p(mean), _p(q), float(kss), _p(work), self._st()),
-                   "pg_predict_mean_q")
+        self._call("pg_predict_mean_q", _code(ks.dtype), ks.shape[0], ks.shape[1], _p(ks), ks.stride(0), _p(minv),
+                   minv.stride(0) if minv is not None else 0, _p(alpha), _p(mean), _p(q), float(kss), _p(work), self._st())
 
     def predict_mean_q_kt(self, kt, minv, alpha, mean, var, kss, work):
         """The same from kt [m_pad, n_pad] = k(xp, x) (test-point-major): mean = Kt alpha; var = kss - colsum((Minv Kt^T)^2)."""
         q = var
         self._chk(kt, minv, alpha, mean, q, work)
-        _lib.check(self.lib.pg_predict_mean_q_kt(self.h, _code(kt.dtype), kt.shape[1], kt.shape[0], _p(kt), kt.stride(0),
-                                                 _p(minv), minv.stride(0) if minv is not None else 0, _p(alpha),
-                                                 _p(mean), _p(q), float(kss), _p(work), self._st()),
-                   "pg_predict_mean_q_kt")
+        self._call("pg_predict_mean_q_kt", _code(kt.dtype), kt.shape[1], kt.shape[0], _p(kt), kt.stride(0), _p(minv),
+                   minv.stride(0) if minv is not None else 0, _p(alpha), _p(mean), _p(q), float(kss), _p(work), self._st())
 
     def predict_mean_q_kt_batched(self, kt_all, minv_all, alpha_all, mean_all, var_all, spec, hp_all, work_all):
         """All experts' means (and diagonal variances, var_all not None) in three launches (pg_predict_mean_q_kt_batched): kt_all
@@ -397,22 +371,19 @@ class HipOps:
             assert t is None or (t.is_cuda and t.dim() == 2 and t.stride(1) == 1 and t.shape[1] >= m_pad and (nexp == 1 or t.stride(0) >= m_pad))
         if want_var:
             assert minv_all.is_cuda and minv_all.stride(-1) == 1 and hp_all.dtype == torch.float64
-        _lib.check(self.lib.pg_predict_mean_q_kt_batched(
-            self.h, _code(kt_all.dtype), n_pad, m_pad, _p(kt_all), kt_all.stride(1), kt_all.stride(0),
-            _p(minv_all) if want_var else None, minv_all.stride(-2) if want_var else 0, minv_all.stride(0) if want_var else 0,
-            _p(alpha_all), alpha_all.stride(0), _p(mean_all), mean_all.stride(0), _p(var_all), var_all.stride(0) if want_var else 0,
-            C.byref(passes[0]), _p(hp_all), hp_all.stride(0) if hp_all.shape[0] > 1 else 0, _p(work_all), work_all.stride(0), nexp,
-            self._st()), "pg_predict_mean_q_kt_batched")
+        self._call("pg_predict_mean_q_kt_batched", _code(kt_all.dtype), n_pad, m_pad, _p(kt_all), kt_all.stride(1), kt_all.stride(0),
+                   _p(minv_all) if want_var else None, minv_all.stride(-2) if want_var else 0, minv_all.stride(0) if want_var else 0, _p(alpha_all),
+                   alpha_all.stride(0), _p(mean_all), mean_all.stride(0), _p(var_all), var_all.stride(0) if want_var else 0, C.byref(passes[0]),
+                   _p(hp_all), hp_all.stride(0) if hp_all.shape[0] > 1 else 0, _p(work_all), work_all.stride(0), nexp, self._st())
 
     def trmm_lower(self, minv, ks, v):
         self._chk(minv, ks, v)
-        _lib.check(self.lib.pg_trmm_lower(self.h, _code(ks.dtype), ks.shape[0], ks.shape[1], _p(minv), minv.stride(0),
-                                          _p(ks), ks.stride(0), _p(v), v.stride(0), self._st()), "pg_trmm_lower")
+        self._call("pg_trmm_lower", _code(ks.dtype), ks.shape[0], ks.shape[1], _p(minv), minv.stride(0), _p(ks), ks.stride(0), _p(v), v.stride(0),
+                   self._st())
 
     def syrk_tn_sub(self, v, c, lower_only=True):
         self._chk(v, c)
-        _lib.check(self.lib.pg_syrk_tn_sub(self.h, _code(v.dtype), c.shape[0], v.shape[0], _p(v), v.stride(0), _p(c),
-                                           c.stride(0), int(lower_only), self._st()), "pg_syrk_tn_sub")
+        self._call("pg_syrk_tn_sub", _code(v.dtype), c.shape[0], v.shape[0], _p(v), v.stride(0), _p(c), c.stride(0), int(lower_only), self._st())
 
     def trmm_lower_kt(self, minv, kt, vt):
         """vt = kt minv^T (= (minv ks)^T) from the test-point-major cross-covariance: kt, vt [m_pad, n_pad] or [nexp, m_pad, n_pad];
@@ -428,26 +399,22 @@ class HipOps:
             self._chk(minv, kt, vt)
             m0, ldm, step = minv, minv.stride(-2), (minv.stride(0) if minv.dim() == 3 else 0)
         nexp = kt.shape[0] if kt.dim() == 3 else 1
-        _lib.check(self.lib.pg_trmm_lower_kt_batched(
-            self.h, _code(kt.dtype), kt.shape[-1], kt.shape[-2], _p(m0), ldm, step, _p(kt), kt.stride(-2),
-            kt.stride(0) if kt.dim() == 3 else 0, _p(vt), vt.stride(-2), vt.stride(0) if vt.dim() == 3 else 0, nexp, self._st()),
-            "pg_trmm_lower_kt_batched")
+        self._call("pg_trmm_lower_kt_batched", _code(kt.dtype), kt.shape[-1], kt.shape[-2], _p(m0), ldm, step, _p(kt), kt.stride(-2),
+                   kt.stride(0) if kt.dim() == 3 else 0, _p(vt), vt.stride(-2), vt.stride(0) if vt.dim() == 3 else 0, nexp, self._st())
 
     def syrk_nt_sub_batched(self, vt_all, c_all, lower_only=True):
         """c_all[e] -= vt_all[e] vt_all[e]^T for all experts in one launch: vt_all [nexp, m_pad, n_pad], c_all [nexp, m_pad, m_pad]."""
         self._chk(vt_all, c_all)
         assert vt_all.dim() == 3 and c_all.dim() == 3 and vt_all.shape[0] == c_all.shape[0]
-        _lib.check(self.lib.pg_syrk_nt_sub_batched(self.h, _code(c_all.dtype), c_all.shape[1], vt_all.shape[2], _p(vt_all),
-                                                   vt_all.stride(1), vt_all.stride(0), _p(c_all), c_all.stride(1), c_all.stride(0),
-                                                   c_all.shape[0], int(lower_only), self._st()), "pg_syrk_nt_sub_batched")
+        self._call("pg_syrk_nt_sub_batched", _code(c_all.dtype), c_all.shape[1], vt_all.shape[2], _p(vt_all), vt_all.stride(1), vt_all.stride(0),
+                   _p(c_all), c_all.stride(1), c_all.stride(0), c_all.shape[0], int(lower_only), self._st())
 
     # -- grBCM --------------------------------------------------------------------------------
     def grbcm_local_terms(self, mean_c, var_c, var_g, is_first, accumulate, out, beta=None, prec=None):
         self._chk(mean_c, var_c, var_g, out, beta, prec)
         assert out.dtype == torch.float64 and out.shape[0] == 3
-        _lib.check(self.lib.pg_grbcm_local_terms(self.h, _code(mean_c.dtype), mean_c.numel(), _p(mean_c), _p(var_c),
-                                                 _p(var_g), int(is_first), int(accumulate), _p(out), out.stride(0),
-                                                 _p(beta), _p(prec), self._st()), "pg_grbcm_local_terms")
+        self._call("pg_grbcm_local_terms", _code(mean_c.dtype), mean_c.numel(), _p(mean_c), _p(var_c), _p(var_g), int(is_first), int(accumulate),
+                   _p(out), out.stride(0), _p(beta), _p(prec), self._st())
 
     def grbcm_local_terms_batched(self, mean_all, var_all, var_g, first, accumulate, out, beta=None, prec=None):
         """The terms of all owned experts in one launch: mean_all / var_all [nexp, >= m] (row stride arbitrary), out [3, m] float64,
@@ -458,30 +425,28 @@ class HipOps:
         nexp = mean_all.shape[0]
         if beta is not None:
             assert beta.stride(-1) == 1 and prec.stride(-1) == 1 and (nexp == 1 or beta.stride(0) == prec.stride(0))
-        _lib.check(self.lib.pg_grbcm_local_terms_batched(
-            self.h, _code(mean_all.dtype), m, _p(mean_all), mean_all.stride(0), _p(var_all), var_all.stride(0), _p(var_g), nexp, int(first),
-            int(accumulate), _p(out), out.stride(0), _p(beta), _p(prec), beta.stride(0) if beta is not None else 0, self._st()),
-            "pg_grbcm_local_terms_batched")
+        self._call("pg_grbcm_local_terms_batched", _code(mean_all.dtype), m, _p(mean_all), mean_all.stride(0), _p(var_all), var_all.stride(0),
+                   _p(var_g), nexp, int(first), int(accumulate), _p(out), out.stride(0), _p(beta), _p(prec),
+                   beta.stride(0) if beta is not None else 0, self._st())
 
     def grbcm_finish(self, sums, mean_g, var_g, mean, var, beta0=None, prec0=None):
         self._chk(sums, mean_g, var_g, mean, var, beta0, prec0)
-        _lib.check(self.lib.pg_grbcm_finish(self.h, _code(mean_g.dtype), mean_g.numel(), _p(sums), sums.stride(0),
-                                            _p(mean_g), _p(var_g), _p(mean), _p(var), _p(beta0), _p(prec0),
-                                            self._st()), "pg_grbcm_finish")
+        self._call("pg_grbcm_finish", _code(mean_g.dtype), mean_g.numel(), _p(sums), sums.stride(0), _p(mean_g), _p(var_g), _p(mean), _p(var),
+                   _p(beta0), _p(prec0), self._st())
 
     def grbcm_weighted_prec(self, prec, beta, acc, m, accumulate):
         self._chk(prec, beta, acc)
-        _lib.check(self.lib.pg_grbcm_weighted_prec(self.h, _code(acc.dtype), m, acc.shape[0], _p(prec), prec.stride(0), _p(beta),
-                                                   _p(acc), acc.stride(0), int(accumulate), self._st()), "pg_grbcm_weighted_prec")
+        self._call("pg_grbcm_weighted_prec", _code(acc.dtype), m, acc.shape[0], _p(prec), prec.stride(0), _p(beta), _p(acc), acc.stride(0),
+                   int(accumulate), self._st())
 
     def symmetrize(self, a, n):
         self._chk(a)
-        _lib.check(self.lib.pg_symmetrize(self.h, _code(a.dtype), n, _p(a), a.stride(0), self._st()), "pg_symmetrize")
+        self._call("pg_symmetrize", _code(a.dtype), n, _p(a), a.stride(0), self._st())
 
     def grbcm_finish_full(self, sums, mean_g, var_g, cov, mean):
         self._chk(sums, mean_g, var_g, cov, mean)
-        _lib.check(self.lib.pg_grbcm_finish_full(self.h, _code(mean_g.dtype), mean_g.numel(), _p(sums), sums.stride(0), _p(mean_g),
-                                                 _p(var_g), _p(cov), cov.stride(0), _p(mean), self._st()), "pg_grbcm_finish_full")
+        self._call("pg_grbcm_finish_full", _code(mean_g.dtype), mean_g.numel(), _p(sums), sums.stride(0), _p(mean_g), _p(var_g), _p(cov),
+                   cov.stride(0), _p(mean), self._st())
 
     def spd_inverse_lower(self, a_pad):
         """a_pad (padded SPD, lower triangle valid) -> its inverse's lower triangle in a new buffer; raises on a bad pivot."""
@@ -509,34 +474,32 @@ class HipOps:
     def sqdist_argmin(self, x, centres, dist=None, idx=None):
         """dist[n, m] = squared distances, idx[n] (int32) = nearest centre; either output may be None."""
         self._chk(x, centres, dist, idx)
-        _lib.check(self.lib.pg_sqdist_argmin(self.h, _code(x.dtype), _p(x), x.stride(0), x.shape[0], _p(centres),
-                                             centres.stride(0), centres.shape[0], x.shape[1], _p(dist),
-                                             dist.stride(0) if dist is not None else 0, _p(idx), self._st()), "pg_sqdist_argmin")
+        self._call("pg_sqdist_argmin", _code(x.dtype), _p(x), x.stride(0), x.shape[0], _p(centres), centres.stride(0), centres.shape[0], x.shape[1],
+                   _p(dist), dist.stride(0) if dist is not None else 0, _p(idx), self._st())
 
     # -- raw GEMM core (tests, roofline micro-benchmark) ---------------------------------------
     def gemm_raw(self, variant, m, n, k, alpha, a, b, beta, c, tri=0, klo=0, khi=0):
         self._chk(a, b, c)
-        _lib.check(self.lib.pg_gemm_raw(self.h, _code(c.dtype), variant, m, n, k, float(alpha), _p(a), a.stride(0),
-                                        _p(b), b.stride(0), float(beta), _p(c), c.stride(0), tri, klo, khi,
-                                        self._st()), "pg_gemm_raw")
+        self._call("pg_gemm_raw", _code(c.dtype), variant, m, n, k, float(alpha), _p(a), a.stride(0), _p(b), b.stride(0), float(beta), _p(c),
+                   c.stride(0), tri, klo, khi, self._st())
 
     def set_lookahead(self, on):
-        _lib.check(self.lib.pg_set_lookahead(self.h, int(on)), "pg_set_lookahead")
+        self._call("pg_set_lookahead", int(on))
 
     def set_outer_panel(self, columns):
-        _lib.check(self.lib.pg_set_outer_panel(self.h, int(columns)), "pg_set_outer_panel")
+        self._call("pg_set_outer_panel", int(columns))
 
     def set_recursive_split(self, min_n):
         """From min_n points on the fused factor-and-invert call splits the matrix recursively (0: never; default 16384)."""
-        _lib.check(self.lib.pg_set_recursive_split(self.h, int(min_n)), "pg_set_recursive_split")
+        self._call("pg_set_recursive_split", int(min_n))
 
     def set_coupled_chain(self, on):
-        _lib.check(self.lib.pg_set_coupled_chain(self.h, int(on)), "pg_set_coupled_chain")
+        self._call("pg_set_coupled_chain", int(on))
 
     def set_spin_budget(self, microseconds):
         """Wall-time bound of one wait of the coupled chain; 0: scaled to the call (default); < 0: every wait expires at once
         (test hook of the fall-back)."""
-        _lib.check(self.lib.pg_set_spin_budget(self.h, int(microseconds)), "pg_set_spin_budget")
+        self._call("pg_set_spin_budget", int(microseconds))
 
     def chain_timeouts(self):
         return int(self.lib.pg_chain_timeouts(self.h))
@@ -544,7 +507,7 @@ class HipOps:
     def set_rearm_after(self, calls):
         """After a time-out the handle takes the coupled chain back by itself once this many further factorisations have been
         enqueued (default 8; 0: never)."""
-        _lib.check(self.lib.pg_set_rearm_after(self.h, int(calls)), "pg_set_rearm_after")
+        self._call("pg_set_rearm_after", int(calls))
 
     def chain_rearms(self):
         return int(self.lib.pg_chain_rearms(self.h))
@@ -555,7 +518,7 @@ class HipOps:
     def spin_probe(self, n):
         """One bounded wait on a flag nobody sets, with the budget of an n x n factorisation: (milliseconds waited, flag came)."""
         scratch = torch.zeros(4, dtype=torch.int64, device=self.device)
-        _lib.check(self.lib.pg_spin_probe(self.h, int(n), _p(scratch), self._st()), "pg_spin_probe")
+        self._call("pg_spin_probe", int(n), _p(scratch), self._st())
         torch.cuda.synchronize()
         v = scratch.tolist()
         return v[2] * 1e-5, bool(v[3])
@@ -567,7 +530,7 @@ class HipOps:
         torch.cuda.synchronize()
         self.chain_timeouts()                      # polls the pinned word
         if self.coupled_chain():                   # (-1: off as after a time-out -- the rows stream stays, the handle re-arms itself)
-            _lib.check(self.lib.pg_set_coupled_chain(self.h, -1), "pg_set_coupled_chain")
+            self._call("pg_set_coupled_chain", -1)
         self.fallbacks = getattr(self, "fallbacks", 0) + 1
 
     def build_factor_checked(self, spec, hp, x, a, invd, info, minv=None, jitter=JITTER):
@@ -577,10 +540,8 @@ class HipOps:
         self._chk(hp, x, a, invd, info, minv)
         n, d = x.shape
         out = C.c_int(0)
-        _lib.check(self.lib.pg_build_potrf_trtri_checked(
-            self.h, _code(a.dtype), C.byref(passes[0]), _p(hp), _p(x), x.stride(0), n, d, float(jitter), _p(a), a.stride(0),
-            a.shape[0], _p(invd), _p(info), _p(minv), minv.stride(0) if minv is not None else 0, self._st(), C.byref(out)),
-            "pg_build_potrf_trtri_checked")
+        self._call("pg_build_potrf_trtri_checked", _code(a.dtype), C.byref(passes[0]), _p(hp), _p(x), x.stride(0), n, d, float(jitter), _p(a),
+                   a.stride(0), a.shape[0], _p(invd), _p(info), _p(minv), minv.stride(0) if minv is not None else 0, self._st(), C.byref(out))
         return out.value
 
     def coupled_chain(self):
@@ -591,15 +552,14 @@ class HipOps:
 
     def leaf_raw(self, a, inv, info):
         self._chk(a, inv, info)
-        _lib.check(self.lib.pg_leaf_raw(self.h, _code(a.dtype), _p(a), a.stride(0), _p(inv), inv.stride(0) if inv is not None else 0,
-                                        _p(info), self._st()), "pg_leaf_raw")
+        self._call("pg_leaf_raw", _code(a.dtype), _p(a), a.stride(0), _p(inv), inv.stride(0) if inv is not None else 0, _p(info), self._st())
 
     def profile(self, on):
-        _lib.check(self.lib.pg_profile(self.h, int(on)), "pg_profile")
+        self._call("pg_profile", int(on))
 
     def profile_read(self):
         f, ms, n = C.c_double(), C.c_double(), C.c_long()
-        _lib.check(self.lib.pg_profile_read(self.h, C.byref(f), C.byref(ms), C.byref(n)), "pg_profile_read")
+        self._call("pg_profile_read", C.byref(f), C.byref(ms), C.byref(n))
         return f.value, ms.value, n.value
 
 

@@ -69,13 +69,15 @@ static bool rows16(int dtype, const void* p, long ld) {
 }
 #define NEED16(p, ld) NEED(rows16(dtype, (p), (ld)), #p ": base and rows (" #ld ") must be 16-byte aligned")
 #define NEEDS16(p, stride) NEED(!(p) || ((stride) * (dtype == PG_F32 ? 4 : 8)) % 16 == 0, #p ": expert stride " #stride " must keep every expert 16-byte aligned")
-#define DISPATCH(dtype, CALL_D, CALL_F)                                      \
-    do {                                                                     \
-        if ((dtype) == PG_F64) return CALL_D;                                \
-        if ((dtype) == PG_F32) return CALL_F;                                \
-        pg_set_error("%s: unknown dtype %d", __func__, (int)(dtype));        \
-        return -1;                                                           \
-    } while (0)
+// dtype dispatch: `call` is a generic lambda that receives a double or a float and names its type T.  `fn` is the entry point's name,
+// passed in by the caller (__func__ inside the lambda would name the lambda).
+template <typename F>
+static int dispatch(int dtype, const char* fn, F&& call) {
+    if (dtype == PG_F64) return call(double());
+    if (dtype == PG_F32) return call(float());
+    pg_set_error("%s: unknown dtype %d", fn, dtype);
+    return -1;
+}
 
 // A timed-out wait of the coupled chain (chainstep.h) sets the handle's pinned host word: from the next entry point on the handle
 // factorises on the classic chain (no flags, no resident kernels), so that repeating the failed call -- which is what
@@ -365,11 +367,10 @@ int pg_kernel_build(pg_handle h, int dtype, const pg_covspec* spec, const double
     NEED(!sym || rows_pad == cols_pad, "symmetric build needs a square padded shape");
     NEED(ldk % (dtype == PG_F64 ? 2 : 4) == 0, "ldk must keep rows 16-byte aligned");
     NEED16(K, ldk);
-    DISPATCH(dtype,
-             pg_kbuild<double>(ST(stream), *spec, hp, (const double*)Xr, ldr, nr, (const double*)Xc, ldc, nc, d, sym,
-                               lower_only, accumulate, jitter, (double*)K, ldk, rows_pad, cols_pad),
-             pg_kbuild<float>(ST(stream), *spec, hp, (const float*)Xr, ldr, nr, (const float*)Xc, ldc, nc, d, sym,
-                              lower_only, accumulate, jitter, (float*)K, ldk, rows_pad, cols_pad));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_kbuild<T>(ST(stream), *spec, hp, (const T*)Xr, ldr, nr, (const T*)Xc, ldc, nc, d, sym, lower_only, accumulate, jitter,
+                            (T*)K, ldk, rows_pad, cols_pad);
+    });
 }
 
 int pg_kernel_build_batched(pg_handle h, int dtype, const pg_covspec* spec, const double* hp, long hp_stride, const void* Xr, long ldr,
@@ -386,11 +387,10 @@ int pg_kernel_build_batched(pg_handle h, int dtype, const pg_covspec* spec, cons
     NEED(nexp == 1 || k_stride >= (long)rows_pad * ldk, "experts' matrices overlap");
     NEED(ldk % (dtype == PG_F64 ? 2 : 4) == 0, "ldk must keep rows 16-byte aligned");
     NEED16(K, ldk); NEEDS16(K, k_stride);
-    DISPATCH(dtype,
-             pg_kbuild<double>(ST(stream), *spec, hp, (const double*)Xr, ldr, nr, (const double*)Xc, ldc, nc, d, sym, lower_only, 0, jitter,
-                               (double*)K, ldk, rows_pad, cols_pad, 0, 0, nexp, xc_stride, hp_stride, k_stride, xr_stride),
-             pg_kbuild<float>(ST(stream), *spec, hp, (const float*)Xr, ldr, nr, (const float*)Xc, ldc, nc, d, sym, lower_only, 0, jitter,
-                              (float*)K, ldk, rows_pad, cols_pad, 0, 0, nexp, xc_stride, hp_stride, k_stride, xr_stride));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_kbuild<T>(ST(stream), *spec, hp, (const T*)Xr, ldr, nr, (const T*)Xc, ldc, nc, d, sym, lower_only, 0, jitter, (T*)K, ldk,
+                            rows_pad, cols_pad, 0, 0, nexp, xc_stride, hp_stride, k_stride, xr_stride);
+    });
 }
 
 int pg_kernel_grad_build(pg_handle h, int dtype, const pg_covspec* spec, const double* hp, const void* X, long ldx,
@@ -398,8 +398,9 @@ int pg_kernel_grad_build(pg_handle h, int dtype, const pg_covspec* spec, const d
     JOIN(h, stream);
     NEED(h && hp && X && dK, "null pointer");
     if (check_spec(spec, __func__)) return -1;
-    DISPATCH(dtype, pg_kgrad<double>(ST(stream), *spec, hp, (const double*)X, ldx, n, d, (double*)dK),
-             pg_kgrad<float>(ST(stream), *spec, hp, (const float*)X, ldx, n, d, (float*)dK));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_kgrad<T>(ST(stream), *spec, hp, (const T*)X, ldx, n, d, (T*)dK);
+    });
 }
 
 int pg_build_potrf_trtri(pg_handle h, int dtype, const pg_covspec* spec, const double* hp, const void* X, long ldx, int n, int d,
@@ -413,8 +414,9 @@ int pg_build_potrf_trtri(pg_handle h, int dtype, const pg_covspec* spec, const d
     NEED(lda % (dtype == PG_F64 ? 2 : 4) == 0, "lda must keep rows 16-byte aligned");
     NEED16(A, lda); NEED16(inv_diag, 0); NEED16(Minv, ldm);
     AtomicGuard ag(h, A);
-    DISPATCH(dtype, build_potrf_t<double>(h, ST(stream), spec, hp, X, ldx, n, d, jitter, A, lda, n_pad, inv_diag, info, Minv, ldm),
-             build_potrf_t<float>(h, ST(stream), spec, hp, X, ldx, n, d, jitter, A, lda, n_pad, inv_diag, info, Minv, ldm));
+    return dispatch(dtype, __func__, [&](auto t) {
+        return build_potrf_t<decltype(t)>(h, ST(stream), spec, hp, X, ldx, n, d, jitter, A, lda, n_pad, inv_diag, info, Minv, ldm);
+    });
 }
 
 int pg_build_potrf_trtri_batched(pg_handle h, int dtype, const pg_covspec* spec, const double* hp, long hp_stride, const void* X, long ldx,
@@ -433,11 +435,10 @@ int pg_build_potrf_trtri_batched(pg_handle h, int dtype, const pg_covspec* spec,
     NEED16(A, lda); NEEDS16(A, a_stride); NEED16(inv_diag, inv_stride); NEED16(Minv, ldm); NEEDS16(Minv, m_stride);
     maybe_rearm(h);      // a batched-only workload counts towards the re-arm like the single-matrix calls (one per call)
     AtomicGuard ag(h, A);
-    DISPATCH(dtype,
-             potrf_batched_t<double>(h, ST(stream), spec, hp, hp_stride, X, ldx, x_stride, n, d, jitter, A, lda, a_stride, n_pad, inv_diag,
-                                     inv_stride, info, Minv, ldm, m_stride, nexp),
-             potrf_batched_t<float>(h, ST(stream), spec, hp, hp_stride, X, ldx, x_stride, n, d, jitter, A, lda, a_stride, n_pad, inv_diag,
-                                    inv_stride, info, Minv, ldm, m_stride, nexp));
+    return dispatch(dtype, __func__, [&](auto t) {
+        return potrf_batched_t<decltype(t)>(h, ST(stream), spec, hp, hp_stride, X, ldx, x_stride, n, d, jitter, A, lda, a_stride, n_pad, inv_diag,
+                                            inv_stride, info, Minv, ldm, m_stride, nexp);
+    });
 }
 
 long pg_potrf_worksize(int dtype, int n) { (void)dtype; return pg_potrf_worksize_impl(n); }
@@ -449,8 +450,9 @@ int pg_potrf(pg_handle h, int dtype, int n, void* A, long lda, void* inv_diag, i
     AtomicGuard ag(h, A);
     NEED(lda >= n, "lda < n");
     NEED16(A, lda); NEED16(inv_diag, 0);
-    DISPATCH(dtype, pg_potrf_t<double>(h, ST(stream), n, (double*)A, lda, (double*)inv_diag, info, nullptr, 0),
-             pg_potrf_t<float>(h, ST(stream), n, (float*)A, lda, (float*)inv_diag, info, nullptr, 0));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_potrf_t<T>(h, ST(stream), n, (T*)A, lda, (T*)inv_diag, info, nullptr, 0);
+    });
 }
 
 int pg_potrf_trtri(pg_handle h, int dtype, int n, void* A, long lda, void* inv_diag, int* info, void* Minv, long ldm,
@@ -461,8 +463,9 @@ int pg_potrf_trtri(pg_handle h, int dtype, int n, void* A, long lda, void* inv_d
     NEED(lda >= n && ldm >= n && A != Minv, "bad leading dimension / aliasing");
     NEED16(A, lda); NEED16(inv_diag, 0); NEED16(Minv, ldm);
     AtomicGuard ag(h, A);
-    DISPATCH(dtype, pg_potrf_t<double>(h, ST(stream), n, (double*)A, lda, (double*)inv_diag, info, (double*)Minv, ldm),
-             pg_potrf_t<float>(h, ST(stream), n, (float*)A, lda, (float*)inv_diag, info, (float*)Minv, ldm));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_potrf_t<T>(h, ST(stream), n, (T*)A, lda, (T*)inv_diag, info, (T*)Minv, ldm);
+    });
 }
 
 long pg_potrs_vec_worksize(int dtype, int n) { (void)dtype; return pg_potrs_vec_worksize_impl(n); }
@@ -473,11 +476,9 @@ int pg_potrs_vec(pg_handle h, int dtype, int n, const void* L, long ldl, const v
     NEED(h && L && inv_diag && y && x && work, "null pointer");
     NEED(ldl >= n, "ldl < n");
     NEED16(L, ldl); NEED16(inv_diag, 0); NEED16(y, 0); NEED16(x, 0); NEED16(work, 0);
-    DISPATCH(dtype,
-             pg_potrs_vec_t<double>(h, ST(stream), n, (const double*)L, ldl, (const double*)inv_diag, (const double*)y,
-                                    (double*)x, (double*)work),
-             pg_potrs_vec_t<float>(h, ST(stream), n, (const float*)L, ldl, (const float*)inv_diag, (const float*)y,
-                                   (float*)x, (float*)work));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_potrs_vec_t<T>(h, ST(stream), n, (const T*)L, ldl, (const T*)inv_diag, (const T*)y, (T*)x, (T*)work);
+    });
 }
 
 int pg_trtri(pg_handle h, int dtype, int n, const void* L, long ldl, const void* inv_diag, void* Minv, long ldm,
@@ -487,9 +488,9 @@ int pg_trtri(pg_handle h, int dtype, int n, const void* L, long ldl, const void*
     NEED(L != Minv, "pg_trtri is out of place");
     NEED(ldl >= n && ldm >= n, "leading dimension < n");
     NEED16(L, ldl); NEED16(inv_diag, 0); NEED16(Minv, ldm);
-    DISPATCH(dtype,
-             pg_trtri_t<double>(h, ST(stream), n, (const double*)L, ldl, (const double*)inv_diag, (double*)Minv, ldm),
-             pg_trtri_t<float>(h, ST(stream), n, (const float*)L, ldl, (const float*)inv_diag, (float*)Minv, ldm));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_trtri_t<T>(h, ST(stream), n, (const T*)L, ldl, (const T*)inv_diag, (T*)Minv, ldm);
+    });
 }
 
 long pg_potrs_worksize(int dtype, int n, int nrhs, int have_minv) {
@@ -504,11 +505,10 @@ static int potrs_any(pg_handle h, int dtype, int n, int nrhs, const void* L, lon
     NEED(ldb >= nrhs && ldx >= nrhs && (Minv ? ldm >= n : ldl >= n), "leading dimension too small");
     NEED(B != X, "out of place: X must not alias B");
     NEED16(L, ldl); NEED16(inv_diag, 0); NEED16(Minv, ldm); NEED16(B, ldb); NEED16(X, ldx); NEED16(work, 0);
-    DISPATCH(dtype,
-             pg_potrs_t<double>(h, ST(stream), n, nrhs, (const double*)L, ldl, (const double*)inv_diag, (const double*)Minv, ldm,
-                                (const double*)B, ldb, (double*)X, ldx, (double*)work, both),
-             pg_potrs_t<float>(h, ST(stream), n, nrhs, (const float*)L, ldl, (const float*)inv_diag, (const float*)Minv, ldm, (const float*)B,
-                               ldb, (float*)X, ldx, (float*)work, both));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_potrs_t<T>(h, ST(stream), n, nrhs, (const T*)L, ldl, (const T*)inv_diag, (const T*)Minv, ldm, (const T*)B, ldb, (T*)X, ldx,
+                             (T*)work, both);
+    });
 }
 int pg_potrs(pg_handle h, int dtype, int n, int nrhs, const void* L, long ldl, const void* inv_diag, const void* Minv, long ldm, const void* B,
              long ldb, void* X, long ldx, void* work, void* stream) {
@@ -524,8 +524,9 @@ int pg_lauum(pg_handle h, int dtype, int n, const void* Minv, long ldm, void* Ki
     NEED(Minv != Kinv, "pg_lauum is out of place");
     NEED(ldm >= n && ldk >= n, "leading dimension < n");
     NEED16(Minv, ldm); NEED16(Kinv, ldk);
-    DISPATCH(dtype, pg_lauum_t<double>(h, ST(stream), n, (const double*)Minv, ldm, (double*)Kinv, ldk),
-             pg_lauum_t<float>(h, ST(stream), n, (const float*)Minv, ldm, (float*)Kinv, ldk));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_lauum_t<T>(h, ST(stream), n, (const T*)Minv, ldm, (T*)Kinv, ldk);
+    });
 }
 
 int pg_potri(pg_handle h, int dtype, int n, const void* L, long ldl, const void* inv_diag, void* Kinv, long ldk, void* work,
@@ -544,8 +545,9 @@ int pg_logdet(pg_handle h, int dtype, int n, const void* L, long ldl, double* ou
     JOIN(h, stream);
     NEED(h && L && out, "null pointer");
     NEED(n > 0 && ldl >= n, "bad size");
-    DISPATCH(dtype, pg_logdet_t<double>(ST(stream), n, (const double*)L, ldl, out),
-             pg_logdet_t<float>(ST(stream), n, (const float*)L, ldl, out));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_logdet_t<T>(ST(stream), n, (const T*)L, ldl, out);
+    });
 }
 
 int pg_trmv(pg_handle h, int dtype, int n, const void* Minv, long ldm, int trans, const void* x, void* y, void* work,
@@ -556,9 +558,9 @@ int pg_trmv(pg_handle h, int dtype, int n, const void* Minv, long ldm, int trans
     NEED(x != y, "pg_trmv is out of place");
     NEED(ldm >= n, "ldm < n");
     NEED16(Minv, ldm); NEED16(x, 0); NEED16(y, 0); NEED16(work, 0);
-    DISPATCH(dtype,
-             pg_trmv_t<double>(h, ST(stream), n, (const double*)Minv, ldm, trans, (const double*)x, (double*)y, (double*)work),
-             pg_trmv_t<float>(h, ST(stream), n, (const float*)Minv, ldm, trans, (const float*)x, (float*)y, (float*)work));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_trmv_t<T>(h, ST(stream), n, (const T*)Minv, ldm, trans, (const T*)x, (T*)y, (T*)work);
+    });
 }
 
 long pg_chol_append_worksize(int dtype, int n_pad, int k) {
@@ -576,11 +578,10 @@ int pg_chol_append(pg_handle h, int dtype, int n, int k, int n_pad, void* L, lon
     NEED(ldl >= n_pad && ldm >= n_pad, "ldl, ldm >= n_pad");
     NEED(ldkt >= n && ldknn >= k, "ldkt >= n, ldknn >= k");
     NEED(L != Minv && u != alpha, "L / Minv and u / alpha must not alias");
-    DISPATCH(dtype,
-             pg_chol_append_t<double>(h, ST(stream), n, k, n_pad, (double*)L, ldl, (double*)inv_diag, (double*)Minv, ldm, (const double*)Kt,
-                                      ldkt, (const double*)Knn, ldknn, (const double*)y_new, (double*)u, (double*)alpha, work, info),
-             pg_chol_append_t<float>(h, ST(stream), n, k, n_pad, (float*)L, ldl, (float*)inv_diag, (float*)Minv, ldm, (const float*)Kt,
-                                     ldkt, (const float*)Knn, ldknn, (const float*)y_new, (float*)u, (float*)alpha, work, info));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_chol_append_t<T>(h, ST(stream), n, k, n_pad, (T*)L, ldl, (T*)inv_diag, (T*)Minv, ldm, (const T*)Kt, ldkt, (const T*)Knn, ldknn,
+                                   (const T*)y_new, (T*)u, (T*)alpha, work, info);
+    });
 }
 
 int pg_alpha_batched(pg_handle h, int dtype, int n, const void* Minv, long ldm, long m_stride, const void* y, long y_stride, void* u,
@@ -589,11 +590,10 @@ int pg_alpha_batched(pg_handle h, int dtype, int n, const void* Minv, long ldm, 
     NEED(h && Minv && y && u && alpha && work, "null pointer");
     NEED(ldm >= n && nexp >= 1 && nexp <= 65535, "bad size");
     NEED16(Minv, ldm); NEEDS16(Minv, m_stride); NEED16(y, y_stride); NEED16(u, u_stride); NEED16(alpha, alpha_stride); NEED16(work, work_stride);
-    DISPATCH(dtype,
-             pg_alpha_batched_t<double>(ST(stream), n, (const double*)Minv, ldm, m_stride, (const double*)y, y_stride, (double*)u, u_stride,
-                                        (double*)alpha, alpha_stride, (double*)work, work_stride, nexp),
-             pg_alpha_batched_t<float>(ST(stream), n, (const float*)Minv, ldm, m_stride, (const float*)y, y_stride, (float*)u, u_stride,
-                                       (float*)alpha, alpha_stride, (float*)work, work_stride, nexp));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_alpha_batched_t<T>(ST(stream), n, (const T*)Minv, ldm, m_stride, (const T*)y, y_stride, (T*)u, u_stride, (T*)alpha, alpha_stride,
+                                     (T*)work, work_stride, nexp);
+    });
 }
 
 int pg_alpha_nlml_batched(pg_handle h, int dtype, int n_real, int n, const void* Minv, long ldm, long m_stride, const void* y, long y_stride,
@@ -603,11 +603,10 @@ int pg_alpha_nlml_batched(pg_handle h, int dtype, int n_real, int n, const void*
     NEED(h && Minv && y && u && alpha && work && out, "null pointer");
     NEED(n_real > 0 && n_real <= n && ldm >= n && nexp >= 1 && nexp <= 65535, "bad size");
     NEED16(Minv, ldm); NEEDS16(Minv, m_stride); NEED16(y, y_stride); NEED16(u, u_stride); NEED16(alpha, alpha_stride); NEED16(work, work_stride);
-    DISPATCH(dtype,
-             pg_alpha_batched_t<double>(ST(stream), n, (const double*)Minv, ldm, m_stride, (const double*)y, y_stride, (double*)u, u_stride,
-                                        (double*)alpha, alpha_stride, (double*)work, work_stride, nexp, n_real, out, out_stride),
-             pg_alpha_batched_t<float>(ST(stream), n, (const float*)Minv, ldm, m_stride, (const float*)y, y_stride, (float*)u, u_stride,
-                                       (float*)alpha, alpha_stride, (float*)work, work_stride, nexp, n_real, out, out_stride));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_alpha_batched_t<T>(ST(stream), n, (const T*)Minv, ldm, m_stride, (const T*)y, y_stride, (T*)u, u_stride, (T*)alpha, alpha_stride,
+                                     (T*)work, work_stride, nexp, n_real, out, out_stride);
+    });
 }
 
 int pg_lauum_batched(pg_handle h, int dtype, int n, const void* Minv, long ldm, long m_stride, void* Kinv, long ldk, long k_stride, int nexp,
@@ -620,8 +619,9 @@ int pg_lauum_batched(pg_handle h, int dtype, int n, const void* Minv, long ldm, 
     NEED16(Minv, ldm); NEEDS16(Minv, m_stride); NEED16(Kinv, ldk); NEEDS16(Kinv, k_stride);
     ExpBatch eb;
     eb.nexp = nexp; eb.eA = k_stride; eb.eInv = 0; eb.eM = m_stride; eb.eX = 0; eb.ehp = 0;
-    DISPATCH(dtype, pg_lauum_t<double>(h, ST(stream), n, (const double*)Minv, ldm, (double*)Kinv, ldk, &eb),
-             pg_lauum_t<float>(h, ST(stream), n, (const float*)Minv, ldm, (float*)Kinv, ldk, &eb));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_lauum_t<T>(h, ST(stream), n, (const T*)Minv, ldm, (T*)Kinv, ldk, &eb);
+    });
 }
 
 int pg_nlml_grad_batched(pg_handle h, int dtype, const pg_covspec* spec, const double* hp, long hp_stride, const void* X, long ldx, long x_stride,
@@ -632,11 +632,10 @@ int pg_nlml_grad_batched(pg_handle h, int dtype, const pg_covspec* spec, const d
     NEED(ldk >= n && ldx >= d, "leading dimension too small");
     NEED16(Kinv, ldk); NEEDS16(Kinv, k_stride);
     if (check_spec(spec, __func__)) return -1;
-    DISPATCH(dtype,
-             pg_nlml_grad_t<double>(ST(stream), *spec, hp, (const double*)X, ldx, n, d, (const double*)Kinv, ldk, (const double*)alpha, grad,
-                                    nhp, work, lwork, nexp, hp_stride, x_stride, k_stride, alpha_stride, grad_stride),
-             pg_nlml_grad_t<float>(ST(stream), *spec, hp, (const float*)X, ldx, n, d, (const float*)Kinv, ldk, (const float*)alpha, grad, nhp,
-                                   work, lwork, nexp, hp_stride, x_stride, k_stride, alpha_stride, grad_stride));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_nlml_grad_t<T>(ST(stream), *spec, hp, (const T*)X, ldx, n, d, (const T*)Kinv, ldk, (const T*)alpha, grad, nhp, work, lwork, nexp,
+                                 hp_stride, x_stride, k_stride, alpha_stride, grad_stride);
+    });
 }
 
 int pg_alpha_nlml_async(pg_handle h, int dtype, int n_real, int n, const void* L, long ldl, const void* Minv, long ldm, const void* y,
@@ -645,20 +644,18 @@ int pg_alpha_nlml_async(pg_handle h, int dtype, int n_real, int n, const void* L
     NEED(h && L && Minv && y && u && alpha && work && out, "null pointer");
     NEED(n_real > 0 && n_real <= n && ldl >= n && ldm >= n, "bad size");
     NEED16(L, ldl); NEED16(Minv, ldm); NEED16(y, 0); NEED16(u, 0); NEED16(alpha, 0); NEED16(work, 0);
-    DISPATCH(dtype,
-             pg_alpha_nlml_async_t<double>(h, ST(stream), n_real, n, (const double*)L, ldl, (const double*)Minv, ldm, (const double*)y,
-                                           (double*)u, (double*)alpha, (double*)work, out),
-             pg_alpha_nlml_async_t<float>(h, ST(stream), n_real, n, (const float*)L, ldl, (const float*)Minv, ldm, (const float*)y,
-                                          (float*)u, (float*)alpha, (float*)work, out));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_alpha_nlml_async_t<T>(h, ST(stream), n_real, n, (const T*)L, ldl, (const T*)Minv, ldm, (const T*)y, (T*)u, (T*)alpha, (T*)work, out);
+    });
 }
 
 int pg_nlml_value(pg_handle h, int dtype, int n, const void* L, long ldl, const void* y, const void* alpha, double* out,
                   void* stream) {
     JOIN(h, stream);
     NEED(h && L && y && alpha && out, "null pointer");
-    DISPATCH(dtype,
-             pg_nlml_value_t<double>(ST(stream), n, (const double*)L, ldl, (const double*)y, (const double*)alpha, out),
-             pg_nlml_value_t<float>(ST(stream), n, (const float*)L, ldl, (const float*)y, (const float*)alpha, out));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_nlml_value_t<T>(ST(stream), n, (const T*)L, ldl, (const T*)y, (const T*)alpha, out);
+    });
 }
 
 long pg_nlml_grad_worksize(int n, int nhp) { return pg_nlml_grad_worksize_impl(n, nhp); }
@@ -679,13 +676,11 @@ int pg_kernel_xgrad(pg_handle h, int dtype, const pg_covspec* spec, const double
     NEED(ldq >= d && ldz >= d, "ldq, ldz >= d");
     NEED(!B || ldb >= (trans_b ? m : n), "ldb too small");
     NEED((!u || ldou >= d) && (!B || ldob >= d), "ldou, ldob >= d");
-    DISPATCH(dtype,
-             pg_xgrad_t<double>(ST(stream), h->ncu, *spec, hp, hp_stride, (const double*)Xq, ldq, xq_stride, m, (const double*)Z, ldz, z_stride, n,
-                                d, (const double*)u, u_stride, (double*)out_u, ldou, ou_stride, (const double*)B, ldb, b_stride, trans_b,
-                                (double*)out_b, ldob, ob_stride, accumulate, work, lwork, nexp),
-             pg_xgrad_t<float>(ST(stream), h->ncu, *spec, hp, hp_stride, (const float*)Xq, ldq, xq_stride, m, (const float*)Z, ldz, z_stride, n,
-                               d, (const float*)u, u_stride, (float*)out_u, ldou, ou_stride, (const float*)B, ldb, b_stride, trans_b,
-                               (float*)out_b, ldob, ob_stride, accumulate, work, lwork, nexp));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_xgrad_t<T>(ST(stream), h->ncu, *spec, hp, hp_stride, (const T*)Xq, ldq, xq_stride, m, (const T*)Z, ldz, z_stride, n, d, (const T*)u,
+                             u_stride, (T*)out_u, ldou, ou_stride, (const T*)B, ldb, b_stride, trans_b, (T*)out_b, ldob, ob_stride, accumulate, work,
+                             lwork, nexp);
+    });
 }
 
 int pg_nlml_grad(pg_handle h, int dtype, const pg_covspec* spec, const double* hp, const void* X, long ldx, int n, int d,
@@ -696,11 +691,9 @@ int pg_nlml_grad(pg_handle h, int dtype, const pg_covspec* spec, const double* h
     NEED(ldk >= n && ldx >= d, "leading dimension too small");
     NEED16(Kinv, ldk);
     if (check_spec(spec, __func__)) return -1;
-    DISPATCH(dtype,
-             pg_nlml_grad_t<double>(ST(stream), *spec, hp, (const double*)X, ldx, n, d, (const double*)Kinv, ldk,
-                                    (const double*)alpha, grad, nhp, work, lwork),
-             pg_nlml_grad_t<float>(ST(stream), *spec, hp, (const float*)X, ldx, n, d, (const float*)Kinv, ldk,
-                                   (const float*)alpha, grad, nhp, work, lwork));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_nlml_grad_t<T>(ST(stream), *spec, hp, (const T*)X, ldx, n, d, (const T*)Kinv, ldk, (const T*)alpha, grad, nhp, work, lwork);
+    });
 }
 
 int pg_predict_mean_q(pg_handle h, int dtype, int n_pad, int m_pad, const void* Ks, long ldks, const void* Minv, long ldm,
@@ -710,11 +703,10 @@ int pg_predict_mean_q(pg_handle h, int dtype, int n_pad, int m_pad, const void* 
     NEED(!q || Minv, "variance needs Minv");
     NEED(ldks >= m_pad && (!Minv || ldm >= n_pad), "bad leading dimension");
     NEED16(Ks, ldks); NEED16(Minv, ldm); NEED16(alpha, 0); NEED16(work, 0);
-    DISPATCH(dtype,
-             pg_predict_mean_q_t<double>(h, ST(stream), n_pad, m_pad, (const double*)Ks, ldks, (const double*)Minv, ldm,
-                                         (const double*)alpha, (double*)mean, (double*)q, kss, (double*)work),
-             pg_predict_mean_q_t<float>(h, ST(stream), n_pad, m_pad, (const float*)Ks, ldks, (const float*)Minv, ldm,
-                                        (const float*)alpha, (float*)mean, (float*)q, kss, (float*)work));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_predict_mean_q_t<T>(h, ST(stream), n_pad, m_pad, (const T*)Ks, ldks, (const T*)Minv, ldm, (const T*)alpha, (T*)mean, (T*)q, kss,
+                                      (T*)work);
+    });
 }
 
 int pg_predict_mean_q_kt(pg_handle h, int dtype, int n_pad, int m_pad, const void* Kt, long ldkt, const void* Minv, long ldm,
@@ -724,11 +716,10 @@ int pg_predict_mean_q_kt(pg_handle h, int dtype, int n_pad, int m_pad, const voi
     NEED(!q || Minv, "variance needs Minv");
     NEED(ldkt >= n_pad && (!Minv || ldm >= n_pad), "bad leading dimension");
     NEED16(Kt, ldkt); NEED16(Minv, ldm); NEED16(alpha, 0); NEED16(work, 0);
-    DISPATCH(dtype,
-             pg_predict_mean_q_kt_t<double>(h, ST(stream), n_pad, m_pad, (const double*)Kt, ldkt, (const double*)Minv, ldm,
-                                            (const double*)alpha, (double*)mean, (double*)q, kss, (double*)work),
-             pg_predict_mean_q_kt_t<float>(h, ST(stream), n_pad, m_pad, (const float*)Kt, ldkt, (const float*)Minv, ldm,
-                                           (const float*)alpha, (float*)mean, (float*)q, kss, (float*)work));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_predict_mean_q_kt_t<T>(h, ST(stream), n_pad, m_pad, (const T*)Kt, ldkt, (const T*)Minv, ldm, (const T*)alpha, (T*)mean, (T*)q, kss,
+                                         (T*)work);
+    });
 }
 
 int pg_predict_mean_q_kt_batched(pg_handle h, int dtype, int n_pad, int m_pad, const void* Kt, long ldkt, long kt_stride, const void* Minv,
@@ -745,13 +736,11 @@ int pg_predict_mean_q_kt_batched(pg_handle h, int dtype, int n_pad, int m_pad, c
     NEED(nexp == 1 || (mean_stride >= m_pad && (!var || (var_stride >= m_pad && work_stride >= (long)(n_pad / 64) * m_pad))),
          "experts' outputs / workspaces overlap");
     static const pg_covspec none = {};
-    DISPATCH(dtype,
-             pg_predict_mean_q_kt_batched_t<double>(h, ST(stream), n_pad, m_pad, (const double*)Kt, ldkt, kt_stride, (const double*)Minv, ldm,
-                                                    m_stride, (const double*)alpha, alpha_stride, (double*)mean, mean_stride, (double*)var,
-                                                    var_stride, spec ? *spec : none, hp, hp_stride, (double*)work, work_stride, nexp),
-             pg_predict_mean_q_kt_batched_t<float>(h, ST(stream), n_pad, m_pad, (const float*)Kt, ldkt, kt_stride, (const float*)Minv, ldm,
-                                                   m_stride, (const float*)alpha, alpha_stride, (float*)mean, mean_stride, (float*)var,
-                                                   var_stride, spec ? *spec : none, hp, hp_stride, (float*)work, work_stride, nexp));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_predict_mean_q_kt_batched_t<T>(h, ST(stream), n_pad, m_pad, (const T*)Kt, ldkt, kt_stride, (const T*)Minv, ldm, m_stride,
+                                                 (const T*)alpha, alpha_stride, (T*)mean, mean_stride, (T*)var, var_stride, spec ? *spec : none, hp,
+                                                 hp_stride, (T*)work, work_stride, nexp);
+    });
 }
 
 int pg_trmm_lower(pg_handle h, int dtype, int n_pad, int m_pad, const void* Minv, long ldm, const void* Ks, long ldks,
@@ -760,11 +749,9 @@ int pg_trmm_lower(pg_handle h, int dtype, int n_pad, int m_pad, const void* Minv
     NEED(h && Minv && Ks && V, "null pointer");
     NEED(ldm >= n_pad && ldks >= m_pad && ldv >= m_pad, "bad leading dimension");
     NEED16(Minv, ldm); NEED16(Ks, ldks); NEED16(V, ldv);
-    DISPATCH(dtype,
-             pg_trmm_lower_t<double>(h, ST(stream), n_pad, m_pad, (const double*)Minv, ldm, (const double*)Ks, ldks,
-                                     (double*)V, ldv),
-             pg_trmm_lower_t<float>(h, ST(stream), n_pad, m_pad, (const float*)Minv, ldm, (const float*)Ks, ldks,
-                                    (float*)V, ldv));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_trmm_lower_t<T>(h, ST(stream), n_pad, m_pad, (const T*)Minv, ldm, (const T*)Ks, ldks, (T*)V, ldv);
+    });
 }
 
 int pg_syrk_tn_sub(pg_handle h, int dtype, int m_pad, int n_pad, const void* V, long ldv, void* C, long ldc, int lower_only,
@@ -774,8 +761,9 @@ int pg_syrk_tn_sub(pg_handle h, int dtype, int m_pad, int n_pad, const void* V, 
     NEED(ldv >= m_pad && ldc >= m_pad, "bad leading dimension");
     NEED16(V, ldv); NEED16(C, ldc);
     AtomicGuard ag(h, C);
-    DISPATCH(dtype, pg_syrk_tn_sub_t<double>(h, ST(stream), m_pad, n_pad, (const double*)V, ldv, (double*)C, ldc, lower_only),
-             pg_syrk_tn_sub_t<float>(h, ST(stream), m_pad, n_pad, (const float*)V, ldv, (float*)C, ldc, lower_only));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_syrk_tn_sub_t<T>(h, ST(stream), m_pad, n_pad, (const T*)V, ldv, (T*)C, ldc, lower_only);
+    });
 }
 
 int pg_trmm_lower_kt_batched(pg_handle h, int dtype, int n_pad, int m_pad, const void* Minv, long ldm, long m_stride, const void* Kt, long ldkt,
@@ -786,11 +774,10 @@ int pg_trmm_lower_kt_batched(pg_handle h, int dtype, int n_pad, int m_pad, const
     NEED(ldm >= n_pad && ldkt >= n_pad && ldvt >= n_pad && Kt != Vt, "bad leading dimension / aliasing");
     NEED(nexp == 1 || vt_stride >= (long)m_pad * ldvt, "experts' outputs overlap");
     NEED16(Minv, ldm); NEEDS16(Minv, m_stride); NEED16(Kt, ldkt); NEEDS16(Kt, kt_stride); NEED16(Vt, ldvt); NEEDS16(Vt, vt_stride);
-    DISPATCH(dtype,
-             pg_trmm_lower_kt_t<double>(h, ST(stream), n_pad, m_pad, (const double*)Minv, ldm, m_stride, (const double*)Kt, ldkt, kt_stride,
-                                        (double*)Vt, ldvt, vt_stride, nexp),
-             pg_trmm_lower_kt_t<float>(h, ST(stream), n_pad, m_pad, (const float*)Minv, ldm, m_stride, (const float*)Kt, ldkt, kt_stride,
-                                       (float*)Vt, ldvt, vt_stride, nexp));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_trmm_lower_kt_t<T>(h, ST(stream), n_pad, m_pad, (const T*)Minv, ldm, m_stride, (const T*)Kt, ldkt, kt_stride, (T*)Vt, ldvt, vt_stride,
+                                     nexp);
+    });
 }
 
 int pg_syrk_nt_sub_batched(pg_handle h, int dtype, int m_pad, int n_pad, const void* Vt, long ldvt, long vt_stride, void* C, long ldc,
@@ -802,9 +789,9 @@ int pg_syrk_nt_sub_batched(pg_handle h, int dtype, int m_pad, int n_pad, const v
     NEED(nexp == 1 || (vt_stride >= (long)m_pad * ldvt && c_stride >= (long)m_pad * ldc), "experts' matrices overlap");
     NEED16(Vt, ldvt); NEEDS16(Vt, vt_stride); NEED16(C, ldc); NEEDS16(C, c_stride);
     AtomicGuard ag(h, C);
-    DISPATCH(dtype,
-             pg_syrk_nt_sub_t<double>(h, ST(stream), m_pad, n_pad, (const double*)Vt, ldvt, vt_stride, (double*)C, ldc, c_stride, nexp, lower_only),
-             pg_syrk_nt_sub_t<float>(h, ST(stream), m_pad, n_pad, (const float*)Vt, ldvt, vt_stride, (float*)C, ldc, c_stride, nexp, lower_only));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_syrk_nt_sub_t<T>(h, ST(stream), m_pad, n_pad, (const T*)Vt, ldvt, vt_stride, (T*)C, ldc, c_stride, nexp, lower_only);
+    });
 }
 
 int pg_grbcm_local_terms(pg_handle h, int dtype, int m, const void* mean_c, const void* var_c, const void* var_g,
@@ -813,11 +800,9 @@ int pg_grbcm_local_terms(pg_handle h, int dtype, int m, const void* mean_c, cons
     JOIN(h, stream);
     NEED(h && mean_c && var_c && var_g && out, "null pointer");
     NEED(ldo >= m, "ldo < m");
-    DISPATCH(dtype,
-             pg_grbcm_terms_t<double>(ST(stream), m, (const double*)mean_c, (const double*)var_c, (const double*)var_g,
-                                      is_first, accumulate, out, ldo, beta_out, prec_out),
-             pg_grbcm_terms_t<float>(ST(stream), m, (const float*)mean_c, (const float*)var_c, (const float*)var_g,
-                                     is_first, accumulate, out, ldo, beta_out, prec_out));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_grbcm_terms_t<T>(ST(stream), m, (const T*)mean_c, (const T*)var_c, (const T*)var_g, is_first, accumulate, out, ldo, beta_out, prec_out);
+    });
 }
 
 int pg_grbcm_local_terms_batched(pg_handle h, int dtype, int m, const void* mean_l, long mean_stride, const void* var_l, long var_stride,
@@ -826,22 +811,19 @@ int pg_grbcm_local_terms_batched(pg_handle h, int dtype, int m, const void* mean
     JOIN(h, stream);
     NEED(h && mean_l && var_l && var_g && out, "null pointer");
     NEED(ldo >= m && nexp >= 1 && (nexp == 1 || (!beta_out && !prec_out) || ldb >= m), "bad size");
-    DISPATCH(dtype,
-             pg_grbcm_terms_batched_t<double>(ST(stream), m, (const double*)mean_l, mean_stride, (const double*)var_l, var_stride,
-                                              (const double*)var_g, nexp, first, accumulate, out, ldo, beta_out, prec_out, ldb),
-             pg_grbcm_terms_batched_t<float>(ST(stream), m, (const float*)mean_l, mean_stride, (const float*)var_l, var_stride,
-                                             (const float*)var_g, nexp, first, accumulate, out, ldo, beta_out, prec_out, ldb));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_grbcm_terms_batched_t<T>(ST(stream), m, (const T*)mean_l, mean_stride, (const T*)var_l, var_stride, (const T*)var_g, nexp, first,
+                                           accumulate, out, ldo, beta_out, prec_out, ldb);
+    });
 }
 
 int pg_grbcm_finish(pg_handle h, int dtype, int m, const double* sums, long lds, const void* mean_g, const void* var_g,
                     void* mean, void* var, double* beta0, double* prec0, void* stream) {
     JOIN(h, stream);
     NEED(h && sums && mean_g && var_g && mean && var, "null pointer");
-    DISPATCH(dtype,
-             pg_grbcm_finish_t<double>(ST(stream), m, sums, lds, (const double*)mean_g, (const double*)var_g, (double*)mean,
-                                       (double*)var, beta0, prec0),
-             pg_grbcm_finish_t<float>(ST(stream), m, sums, lds, (const float*)mean_g, (const float*)var_g, (float*)mean,
-                                      (float*)var, beta0, prec0));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_grbcm_finish_t<T>(ST(stream), m, sums, lds, (const T*)mean_g, (const T*)var_g, (T*)mean, (T*)var, beta0, prec0);
+    });
 }
 
 int pg_grbcm_weighted_prec(pg_handle h, int dtype, int m, int m_pad, const void* P, long ldp, const double* beta, void* acc,
@@ -849,40 +831,43 @@ int pg_grbcm_weighted_prec(pg_handle h, int dtype, int m, int m_pad, const void*
     JOIN(h, stream);
     NEED(h && P && beta && acc, "null pointer");
     NEED(m_pad >= m && ldp >= m && lda >= m_pad, "inconsistent sizes");
-    DISPATCH(dtype, pg_weighted_prec_t<double>(ST(stream), m, m_pad, (const double*)P, ldp, beta, (double*)acc, lda, accumulate),
-             pg_weighted_prec_t<float>(ST(stream), m, m_pad, (const float*)P, ldp, beta, (float*)acc, lda, accumulate));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_weighted_prec_t<T>(ST(stream), m, m_pad, (const T*)P, ldp, beta, (T*)acc, lda, accumulate);
+    });
 }
 
 int pg_symmetrize(pg_handle h, int dtype, int n, void* A, long lda, void* stream) {
     JOIN(h, stream);
     NEED(h && A, "null pointer");
-    DISPATCH(dtype, pg_symmetrize_t<double>(ST(stream), n, (double*)A, lda), pg_symmetrize_t<float>(ST(stream), n, (float*)A, lda));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_symmetrize_t<T>(ST(stream), n, (T*)A, lda);
+    });
 }
 
 int pg_grbcm_finish_full(pg_handle h, int dtype, int m, const double* sums, long lds, const void* mean_g, const void* var_g,
                          const void* cov, long ldc, void* mean, void* stream) {
     JOIN(h, stream);
     NEED(h && sums && mean_g && var_g && cov && mean, "null pointer");
-    DISPATCH(dtype,
-             pg_grbcm_finish_full_t<double>(ST(stream), m, sums, lds, (const double*)mean_g, (const double*)var_g,
-                                            (const double*)cov, ldc, (double*)mean),
-             pg_grbcm_finish_full_t<float>(ST(stream), m, sums, lds, (const float*)mean_g, (const float*)var_g, (const float*)cov,
-                                           ldc, (float*)mean));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_grbcm_finish_full_t<T>(ST(stream), m, sums, lds, (const T*)mean_g, (const T*)var_g, (const T*)cov, ldc, (T*)mean);
+    });
 }
 
 int pg_sqdist_argmin(pg_handle h, int dtype, const void* X, long ldx, int n, const void* C, long ldc, int m, int d, void* D,
                      long ldd, int* idx, void* stream) {
     JOIN(h, stream);
     NEED(h && X && C && (D || idx), "null pointer");
-    DISPATCH(dtype,
-             pg_centres<double>(ST(stream), (const double*)X, ldx, n, (const double*)C, ldc, m, d, (double*)D, ldd, idx),
-             pg_centres<float>(ST(stream), (const float*)X, ldx, n, (const float*)C, ldc, m, d, (float*)D, ldd, idx));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_centres<T>(ST(stream), (const T*)X, ldx, n, (const T*)C, ldc, m, d, (T*)D, ldd, idx);
+    });
 }
 
 int pg_tril(pg_handle h, int dtype, int n, void* A, long lda, void* stream) {
     JOIN(h, stream);
     NEED(h && A, "null pointer");
-    DISPATCH(dtype, pg_tril_t<double>(ST(stream), n, (double*)A, lda), pg_tril_t<float>(ST(stream), n, (float*)A, lda));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_tril_t<T>(ST(stream), n, (T*)A, lda);
+    });
 }
 
 int pg_set_lookahead(pg_handle h, int on) {
@@ -1013,8 +998,9 @@ int pg_build_potrf_trtri_checked(pg_handle h, int dtype, const pg_covspec* spec,
 int pg_leaf_raw(pg_handle h, int dtype, void* A, long lda, void* inv, long ldi, int* info, void* stream) {
     JOIN(h, stream);
     NEED(h && A && info, "null pointer");
-    DISPATCH(dtype, pg_leaf<double>(ST(stream), (double*)A, lda, (double*)inv, ldi, info, 0),
-             pg_leaf<float>(ST(stream), (float*)A, lda, (float*)inv, ldi, info, 0));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_leaf<T>(ST(stream), (T*)A, lda, (T*)inv, ldi, info, 0);
+    });
 }
 
 int pg_rowstep_raw(pg_handle h, int dtype, int n, void* A, long lda, int o0, int k0, const void* inv, int* flags, int* info, void* stream) {
@@ -1025,8 +1011,9 @@ int pg_rowstep_raw(pg_handle h, int dtype, int n, void* A, long lda, int o0, int
     PG_CHECK(hipMemsetAsync(flags, 0x40, 8 * sizeof(int), ST(stream)));
     PG_CHECK(hipMemsetAsync(flags + 6, 0, 2 * sizeof(int), ST(stream)));   // [6]: time-out word, [7]: spare
     const CsWait cw = {flags + 6, nullptr, 200000000LL, 1};
-    DISPATCH(dtype, pg_rowstep<double>(ST(stream), (double*)A, lda, n, o0, k0, 1, (const double*)inv, flags, flags + 1, flags + 2, cw, info, flags + 3, flags + 4, 0),
-             pg_rowstep<float>(ST(stream), (float*)A, lda, n, o0, k0, 1, (const float*)inv, flags, flags + 1, flags + 2, cw, info, flags + 3, flags + 4, 0));
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_rowstep<T>(ST(stream), (T*)A, lda, n, o0, k0, 1, (const T*)inv, flags, flags + 1, flags + 2, cw, info, flags + 3, flags + 4, 0);
+    });
 }
 
 int pg_gemm_raw(pg_handle h, int dtype, int variant, int M, int N, int K, double alpha, const void* A, long lda,
@@ -1039,8 +1026,9 @@ int pg_gemm_raw(pg_handle h, int dtype, int variant, int M, int N, int K, double
          "variant not exposed");
     NEED16(A, lda); NEED16(B, ldb); NEED16(C, ldc);
     AtomicGuard ag(h, C);
-    DISPATCH(dtype, gemm_raw_t<double>(h, variant, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, tri, klo, khi, stream),
-             gemm_raw_t<float>(h, variant, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, tri, klo, khi, stream));
+    return dispatch(dtype, __func__, [&](auto t) {
+        return gemm_raw_t<decltype(t)>(h, variant, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, tri, klo, khi, stream);
+    });
 }
 
 }  // extern "C"

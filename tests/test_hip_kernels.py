@@ -615,6 +615,37 @@ def test_bad_arguments_are_refused_with_a_message(ops):
     assert b"null" in _lib.load().pg_last_error()
 
 
+def test_unknown_dtype_is_refused_under_the_entry_points_own_name(ops):
+    """A dtype code that is neither PG_F64 nor PG_F32, with operands that pass every other check (256 x 256 fp64, aligned): -1, the
+    text names the entry point that was called (not the dispatcher or a closure inside it), and no operand changes -- the call
+    returns before anything is enqueued."""
+    import ctypes as C
+    from pygpr_amd import _lib, _ops
+
+    lib, h, st, n, d, bad = _lib.load(), ops.h, ops._st(), 256, 2, 7
+    sentinel = -1234.5678
+    buf = {name: torch.full(shape, sentinel, dtype=torch.float64, device="cuda")
+           for name, shape in dict(a=(n, n), b=(n, n), invd=(lib.pg_potrf_worksize(_lib.PG_F64, n),), x=(n, d), vec=(n,), vec2=(n,), out=(n,), out2=(n,),
+                                   sums=(3, n), hp=(d + 2,), grad=(d + 2,), work=(max(1, lib.pg_nlml_grad_worksize(n, d + 2)),)).items()}
+    buf["info"] = torch.full((1,), 77, dtype=torch.int32, device="cuda")
+    before = {k: v.clone() for k, v in buf.items()}
+    p = {k: v.data_ptr() for k, v in buf.items()}
+    spec = C.byref(_ops.make_spec([_lib.PG_KIND_RBF], [0], [d + 1]))
+    calls = {
+        "pg_potrf": (n, p["a"], n, p["invd"], p["info"], st),
+        "pg_trtri": (n, p["a"], n, p["invd"], p["b"], n, st),
+        "pg_kernel_build": (spec, p["hp"], p["x"], d, n, None, 0, n, d, 0, 0, 0.0, p["a"], n, n, n, st),
+        "pg_nlml_grad": (spec, p["hp"], p["x"], d, n, d, p["a"], n, p["vec"], p["grad"], d + 2, p["work"], buf["work"].numel(), st),
+        "pg_grbcm_finish": (n, p["sums"], n, p["vec"], p["vec2"], p["out"], p["out2"], None, None, st),
+    }
+    for name, args in calls.items():
+        assert getattr(lib, name)(h, bad, *args) == -1, name
+        assert _lib.last_error() == "%s: unknown dtype %d" % (name, bad)
+    torch.cuda.synchronize()
+    for k, v in buf.items():
+        assert torch.equal(v.view(torch.int32), before[k].view(torch.int32)), k      # bit for bit
+
+
 def test_potri_and_logdet(ops):
     """pg_potri = K^-1 from the factor in one call (may overwrite the factor); pg_logdet = 2 sum log L_ii over the real rows."""
     rng = np.random.default_rng(71)

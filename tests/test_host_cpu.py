@@ -40,6 +40,53 @@ def test_library_loads_and_exports_every_header_symbol():
     assert lib.pg_potrf_worksize(0, 16384) == 16384 * 128 + 16384 + 2048
 
 
+def test_ctypes_signatures_are_derived_from_the_header():
+    """_lib._SIGS is parsed from include/pygpr_hip.h: one signature per declared name, types mapped by a closed vocabulary."""
+    protos = _lib.parse_prototypes(open(_lib.HEADER).read())
+    assert sorted(protos) == _lib.header_symbols() and sorted(_lib._SIGS) == _lib.header_symbols()
+    assert _lib._SIGS == _lib.signatures(protos)
+    # shapes a regular expression could plausibly get wrong: a pointer to the handle, a non-int return, three kinds of out-pointer
+    assert protos["pg_create"] == ("int", ["pg_handle*"])
+    assert protos["pg_potrs_worksize"] == ("long", ["int", "int", "int", "int"])
+    assert protos["pg_profile_read"] == ("int", ["pg_handle", "double*", "double*", "long*"])
+    vp, i = ctypes.c_void_p, ctypes.c_int
+    assert _lib._SIGS["pg_create"] == (i, [vp])
+    assert _lib._SIGS["pg_potrs_worksize"] == (ctypes.c_long, [i, i, i, i])
+    assert _lib._SIGS["pg_profile_read"] == (i, [vp, vp, vp, vp])
+    assert _lib._SIGS["pg_last_error"] == (ctypes.c_char_p, []) and _lib._SIGS["pg_version"] == (i, [])
+    assert _lib._SIGS["pg_set_spin_budget"] == (i, [vp, ctypes.c_long])
+    assert _lib._SIGS["pg_kernel_grad_build"][1][2:5] == [ctypes.POINTER(_lib.CovSpec), vp, vp]
+    assert _lib._SIGS["pg_gemm_raw"][1][6] is ctypes.c_double
+    # a prototype split over three lines with a comment between two parameters
+    split = "long pg_split(pg_handle h, int n, /* rows */\n              const double* hp,\n              void *out);\nint pg_none(void);"
+    assert _lib.parse_prototypes(split) == {"pg_split": ("long", ["pg_handle", "int", "const double*", "void*"]), "pg_none": ("int", [])}
+    assert _lib.signatures(_lib.parse_prototypes(split))["pg_split"] == (ctypes.c_long, [vp, i, vp, vp])
+    # a type outside the vocabulary is refused with the prototype's name, never guessed
+    for bad in ("int pg_bad_float(pg_handle h, float x);", "int pg_bad_size(pg_handle h, size_t n);", "float pg_bad_ret(int n);",
+                "int pg_bad_unnamed(pg_handle, int);"):
+        with pytest.raises(ValueError, match=bad.split("(")[0].split()[-1]):
+            _lib.signatures(_lib.parse_prototypes("int pg_good(int n);\n" + bad))
+
+
+def test_derived_bindings_are_callable_without_a_gpu():
+    """The bindings work on the CPU: the two entry points that need no device, and byref(...) / None through void* parameters (the
+    three byref call sites of _ops.py) on entry points that refuse a null handle before they touch anything."""
+    lib = _lib.load()
+    assert lib.pg_version() == 100
+    assert isinstance(lib.pg_last_error(), bytes)
+    f, ms, n = ctypes.c_double(1.5), ctypes.c_double(2.5), ctypes.c_long(3)
+    assert lib.pg_profile_read(None, ctypes.byref(f), ctypes.byref(ms), ctypes.byref(n)) == -1
+    assert _lib.last_error() == "pg_profile_read: null handle" and (f.value, ms.value, n.value) == (1.5, 2.5, 3)
+    assert lib.pg_create(None) == -1 and _lib.last_error() == "pg_create: null handle pointer"
+    out = ctypes.c_int(7)
+    sp = _ops.make_spec([_lib.PG_KIND_RBF], [0], [])
+    assert lib.pg_build_potrf_trtri_checked(None, 0, ctypes.byref(sp), None, None, 0, 0, 1, 0.0, None, 0, 0, None, None, None, 0, None, None) == -1
+    assert _lib.last_error() == "pg_build_potrf_trtri_checked: null pointer"
+    assert lib.pg_potrf_worksize(0, 512) == 512 * 128 + 512 + 2048 and lib.pg_potrs_worksize(0, 256, 128, 1) == 256 * 128
+    for arg in (ctypes.byref(out), ctypes.byref(ctypes.c_void_p()), None, ctypes.c_void_p(64), 64):
+        ctypes.c_void_p.from_param(arg)
+
+
 def test_no_cpu_fallback_without_a_gpu():
     if torch.cuda.is_available():
         pytest.skip("this box has a GPU")
