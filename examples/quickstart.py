@@ -32,6 +32,9 @@ print("NLML after %d evaluations: %.4f" % (opt.res.nfev, float(opt.res.fun)))
 mean, var = gp.predict(xs, var="diag")
 print("test RMSE %.4f, mean predictive std %.4f" % (float((mean - torch.sin(-xs.sum(-1))).pow(2).mean().sqrt()),
                                                     float(var.sqrt().mean())))
+loo_mean, loo_var = gp.loo_predict()   # leave-one-out check of the fit on its own data; PyGPR.LOO(gp) trains on that criterion
+print("LOO standardised residuals: std %.3f (1 = calibrated), worst %.1f sigma" % (
+    float(((y - loo_mean) / loo_var.sqrt()).std()), float(((y - loo_mean) / loo_var.sqrt()).abs().max())))
 
 # ---- grBCM committee: 4 local experts + a global communication set, shared hyper-parameters
 nc, nls, ng = 4, 400, 200

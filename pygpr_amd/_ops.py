@@ -299,6 +299,28 @@ class HipOps:
             self._call("pg_nlml_grad", _code(kinv.dtype), C.byref(sp), _p(hp), _p(x), x.stride(0), n, x.shape[1], _p(kinv), kinv.stride(0), _p(alpha),
                        _p(grad), grad.numel(), _p(work), work.numel(), self._st())
 
+    # -- leave-one-out (include/pygpr_hip_loo.h) ----------------------------------------------
+    def loo_terms_worksize(self, n_pad):
+        return int(self.lib.pg_loo_terms_worksize(int(n_pad)))
+
+    def loo_terms(self, minv, alpha, y, n, c, mu, var, out, work):
+        """c = diag(K^-1) from the column sums of squares of minv = L^-1, mu / var = the leave-one-out mean and variance of the n real
+        points, out[0] = the LOO loss (fp64); work: loo_terms_worksize(n_pad) doubles."""
+        self._chk(minv, alpha, y, c, mu, var, out, work)
+        assert out.dtype == torch.float64 and work.dtype == torch.float64 and work.numel() >= self.loo_terms_worksize(minv.shape[0])
+        self._call("pg_loo_terms", _code(minv.dtype), int(n), minv.shape[0], _p(minv), minv.stride(0), _p(alpha), _p(y), _p(c), _p(mu), _p(var),
+                   _p(out), _p(work), self._st())
+
+    def loo_weights(self, c, alpha, kinv, n, p, q):
+        """kinv (full symmetric K^-1) -> S = K^-1 diag(sqrt(2 w)) in place, p / q = (alpha +- K^-1 v) / sqrt2 (pg_loo_weights)."""
+        self._chk(c, alpha, kinv, p, q)
+        self._call("pg_loo_weights", _code(kinv.dtype), int(n), _p(c), _p(alpha), _p(kinv), kinv.stride(0), _p(p), _p(q), self._st())
+
+    def loo_fold(self, m, q, n):
+        """m (lower triangle) += q q^T on the n real points (pg_loo_fold)."""
+        self._chk(m, q)
+        self._call("pg_loo_fold", _code(m.dtype), int(n), _p(m), m.stride(0), _p(q), self._st())
+
     # -- derivatives in the test points -------------------------------------------------------
     def kernel_xgrad(self, spec, hp, xq, z, u=None, b=None, out_u=None, out_b=None, trans_b=False, accumulate=False):
         """out_u[p][k] = sum_i u_i dk(xq_p, z_i)/dxq_pk and / or out_b[p][k] = sum_i B_pi dk(xq_p, z_i)/dxq_pk (pg_kernel_xgrad, one pass

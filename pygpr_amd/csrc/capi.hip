@@ -4,6 +4,7 @@
 #include "leaf.h"
 #include "chainstep.h"
 #include "linalg.h"
+#include "pygpr_hip_loo.h"
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -581,6 +582,40 @@ int pg_chol_append(pg_handle h, int dtype, int n, int k, int n_pad, void* L, lon
     return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
         return pg_chol_append_t<T>(h, ST(stream), n, k, n_pad, (T*)L, ldl, (T*)inv_diag, (T*)Minv, ldm, (const T*)Kt, ldkt, (const T*)Knn, ldknn,
                                    (const T*)y_new, (T*)u, (T*)alpha, work, info);
+    });
+}
+
+long pg_loo_terms_worksize(int n_pad) { return (n_pad > 0 && n_pad % PG_PAD == 0) ? pg_loo_terms_worksize_impl(n_pad) : -1; }
+
+int pg_loo_terms(pg_handle h, int dtype, int n, int n_pad, const void* Minv, long ldm, const void* alpha, const void* y, void* c, void* mu,
+                 void* var, double* out, double* work, void* stream) {
+    JOIN(h, stream);
+    NEED(h && Minv && alpha && y && c && mu && var && out && work, "null pointer");
+    NEED(n_pad > 0 && n_pad % PG_PAD == 0, "n_pad must be a positive multiple of 256");
+    NEED(n >= 1 && n <= n_pad && ldm >= n_pad, "1 <= n <= n_pad <= ldm");
+    NEED16(Minv, ldm);
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_loo_terms_t<T>(ST(stream), n, n_pad, (const T*)Minv, ldm, (const T*)alpha, (const T*)y, (T*)c, (T*)mu, (T*)var, out, work);
+    });
+}
+
+int pg_loo_weights(pg_handle h, int dtype, int n, const void* c, const void* alpha, void* Kinv, long ldk, void* p, void* q, void* stream) {
+    JOIN(h, stream);
+    NEED(h && c && alpha && Kinv && p && q, "null pointer");
+    NEED(n >= 1 && ldk >= n, "1 <= n <= ldk");
+    NEED(p != q && p != c && p != alpha && q != c && q != alpha, "p and q must not alias each other, c or alpha");
+    NEED16(Kinv, ldk);
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_loo_weights_t<T>(ST(stream), n, (const T*)c, (const T*)alpha, (T*)Kinv, ldk, (T*)p, (T*)q);
+    });
+}
+
+int pg_loo_fold(pg_handle h, int dtype, int n, void* M, long ldm, const void* q, void* stream) {
+    JOIN(h, stream);
+    NEED(h && M && q, "null pointer");
+    NEED(n >= 1 && ldm >= n, "1 <= n <= ldm");
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_loo_fold_t<T>(ST(stream), n, (T*)M, ldm, (const T*)q);
     });
 }
 

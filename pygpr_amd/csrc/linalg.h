@@ -80,3 +80,10 @@ long pg_chol_append_worksize_impl(int tsize, int n_pad, int k);
 template <typename T>
 int pg_chol_append_t(pg_ctx*, hipStream_t, int n, int k, int n_pad, T* L, long ldl, T* invd, T* Minv, long ldm, const T* Kt, long ldkt,
                      const T* Knn, long ldknn, const T* yn, T* u, T* alpha, void* work, int* info);
+// loo.hip: leave-one-out terms from L^-1 and alpha, and the operands of the LOO gradient (include/pygpr_hip_loo.h)
+long pg_loo_terms_worksize_impl(int n_pad);
+template <typename T>
+int pg_loo_terms_t(hipStream_t, int n, int n_pad, const T* Minv, long ldm, const T* alpha, const T* y, T* c, T* mu, T* var, double* out,
+                   double* work);
+template <typename T> int pg_loo_weights_t(hipStream_t, int n, const T* c, const T* alpha, T* Kinv, long ldk, T* p, T* q);
+template <typename T> int pg_loo_fold_t(hipStream_t, int n, T* M, long ldm, const T* q);

@@ -14,6 +14,7 @@ Differences a caller can observe:
   * K** is never built for var="diag": its diagonal is sum sigma_c^2 + sum sigma_n^2 analytically
   * assigning `model.x` / `model.y` marks the model dirty (the reference keeps a stale factor there)
   * `krn`, `krnchd`, `wt` are read-only views materialised on access
+  * `append` and `loo_predict` are new: conditioning on further points, and leave-one-out predictions from the cached L^-1
 """
 import os
 from typing import Sequence
@@ -169,6 +170,9 @@ class GPR:
 
     def predict(self, xp: Tensor, var: str) -> Sequence[Tensor]:
         raise NotImplementedError
+
+    def loo_predict(self) -> Sequence[Tensor]:
+        raise NotImplementedError("%s has no leave-one-out prediction; fit an Exact_GP on the data" % type(self).__name__)
 
     def predict_var(self, xp: Tensor, **kwrgs: Tensor) -> Tensor:
         raise NotImplementedError
@@ -487,6 +491,27 @@ class Exact_GP(GPR):
         self._data = [dta]
         self._data_key = (id(self._x), self._x._version, id(self._y), self._y._version)
         self._upd_count += 1
+
+    # ---- leave-one-out cross-validation -----------------------------------------------------------
+    def loo_predict(self) -> Sequence[Tensor]:
+        """[mean, var] of the leave-one-out predictive distributions p(y_i | x, y_-i) (Rasmussen & Williams 5.4.2), each [n] in the
+        model's dtype on x's device: mean_i = y_i - alpha_i / c_i and var_i = 1 / c_i with c = diag(K^-1) -- predictive for y_i, the noise
+        and the 1e-7 jitter included (K is the matrix update() factors).  Calls update(); c comes from one pass over the cached L^-1
+        (pg_loo_terms), which is formed once if it is not held and kept from then on, as `append` does.  Batched models (more than one
+        expert) raise NotImplementedError, and so does GRBCM."""
+        x_old, y_old = self._x, self._y
+        nb_params = self.params.reshape(-1, self.params.shape[-1]).shape[0] if isinstance(self.params, Tensor) else 1
+        if (x_old.dim() == 3 and x_old.shape[0] > 1) or (y_old.dim() > 1 and y_old.reshape(-1, y_old.shape[-1]).shape[0] > 1) or nb_params > 1:
+            raise NotImplementedError("Exact_GP.loo_predict: batched models (more than one expert) are not supported")
+        self.update()
+        ops = get_ops()
+        e = self._experts[0]
+        dt = self.dtype
+        c, mu, var = (ops.empty(e.n, dtype=dt) for _ in range(3))
+        out = ops.zeros(1, dtype=torch.float64)
+        work = ops.empty(ops.loo_terms_worksize(e.n_pad), dtype=torch.float64)
+        ops.loo_terms(self._minv(e), e.alpha, e.y, e.n, c, mu, var, out, work)
+        return [mu.to(self._x.device), var.to(self._x.device)]
 
     def _kss_diag(self, b: int) -> float:
         """diag of cov.kernel(params, xp): sum sigma_c^2 + sum sigma_n^2 (White_noise sees xp=None,

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 from numpy import ndarray
 
+from . import _lib
 from ._ops import get_ops
 from .covar import layout, spec_of
 from .gpr import _BATCH_EAGER_N, _BATCH_MAX_N, GPR, _checked, _lin_alg_error
@@ -40,17 +41,58 @@ class Loss():
         raise NotImplementedError
 
 
-class MLE(Loss):
-    """Negative log marginal likelihood of the hyper-parameters (PyGPR/loss.py:31-128)."""
+class _MemoLoss(Loss):
+    """A loss whose device evaluation (`_evaluate_device`) is memoised on parameters, data and covariance: what MLE and LOO share."""
 
     def __init__(self, model: GPR) -> None:
         super().__init__(model)
         self._buf = {}
-        self._bbuf = {}
-        self.last_batched = False   # the last device evaluation took the experts-together path (tests / diagnostics)
         self.memoize = True     # re-use the last evaluation when asked again at identical parameters (off in benchmarks)
         self._memo = None
         self._factor_key = None   # memo key of the loss-only evaluation whose factor is still in the work buffers
+
+    def _evaluate(self, params: ndarray, want_grad: bool):
+        """One evaluation, memoised on (parameters, data identity and version, covariance): the reference re-factorises on
+        every call (loss.py:39,64,97); CG_Quad / BFGS_Quad / hessian ask for grad(par) at the same point again and again,
+        and get_learn_rate / Nelder_Mead callers ask for loss(p) and then grad(p).  Two levels (SURVEY 8f-4):
+          * the last RESULT is returned as is when it already holds what is asked for;
+          * after a loss-only evaluation of a single model the FACTOR stays in the work buffers: a following grad(p) at
+            the same p only adds L^-1, K^-1 and the contraction (no second covariance build / Cholesky)."""
+        m = self.model      # the reference re-reads model.x / .y / .cov on every call: all three are part of the key
+        key = (np.asarray(params, dtype=np.float64).tobytes(), np.shape(params), id(m._x), m._x._version, id(m._y), m._y._version,
+               id(m.cov), tuple(map(tuple, layout(m.cov, m._x.shape[-1])[:3])))
+        hit = self._memo if (self.memoize and self._memo is not None and self._memo[0] == key) else None
+        if hit is not None and (hit[2] is not None or not want_grad):
+            return hit[1].copy(), (hit[2].copy() if hit[2] is not None else None)
+        reuse = hit is not None and want_grad and self._factor_key == key
+        loss, grad = self._evaluate_device(params, want_grad, key if self.memoize else None, reuse)
+        self._memo = (key, loss.copy(), grad.copy() if want_grad else None)
+        return loss, grad
+
+    def loss(self, params: ndarray) -> float:
+        llhd, _ = self._evaluate(params, False)
+        self.loss_value = llhd
+        return llhd
+
+    def grad(self, params: ndarray) -> ndarray:
+        _, jac = self._evaluate(params, True)
+        self.grad_value = jac
+        return jac
+
+    def loss_and_grad(self, params: ndarray) -> Tuple[float, ndarray]:
+        llhd, jac = self._evaluate(params, True)
+        self.loss_value = llhd
+        self.grad_value = jac
+        return (llhd, jac)
+
+
+class MLE(_MemoLoss):
+    """Negative log marginal likelihood of the hyper-parameters (PyGPR/loss.py:31-128)."""
+
+    def __init__(self, model: GPR) -> None:
+        super().__init__(model)
+        self._bbuf = {}
+        self.last_batched = False   # the last device evaluation took the experts-together path (tests / diagnostics)
 
     def _buffers(self, n_pad, dtype, nhp, n):
         key = (n_pad, dtype, nhp, n)
@@ -70,24 +112,6 @@ class MLE(Loss):
                 "val": ops.zeros(2, dtype=torch.float64),
             }
         return self._buf
-
-    def _evaluate(self, params: ndarray, want_grad: bool):
-        """One evaluation, memoised on (parameters, data identity and version, covariance): the reference re-factorises on
-        every call (loss.py:39,64,97); CG_Quad / BFGS_Quad / hessian ask for grad(par) at the same point again and again,
-        and get_learn_rate / Nelder_Mead callers ask for loss(p) and then grad(p).  Two levels (SURVEY 8f-4):
-          * the last RESULT is returned as is when it already holds what is asked for;
-          * after a loss-only evaluation of a single model the FACTOR stays in the work buffers: a following grad(p) at
-            the same p only adds L^-1, K^-1 and the contraction (no second covariance build / Cholesky)."""
-        m = self.model      # the reference re-reads model.x / .y / .cov on every call: all three are part of the key
-        key = (np.asarray(params, dtype=np.float64).tobytes(), np.shape(params), id(m._x), m._x._version, id(m._y), m._y._version,
-               id(m.cov), tuple(map(tuple, layout(m.cov, m._x.shape[-1])[:3])))
-        hit = self._memo if (self.memoize and self._memo is not None and self._memo[0] == key) else None
-        if hit is not None and (hit[2] is not None or not want_grad):
-            return hit[1].copy(), (hit[2].copy() if hit[2] is not None else None)
-        reuse = hit is not None and want_grad and self._factor_key == key
-        loss, grad = self._evaluate_device(params, want_grad, key if self.memoize else None, reuse)
-        self._memo = (key, loss.copy(), grad.copy() if want_grad else None)
-        return loss, grad
 
     def _evaluate_device(self, params: ndarray, want_grad: bool, key=None, reuse_factor=False):
         ops = get_ops()
@@ -190,18 +214,79 @@ class MLE(Loss):
         grad = grads.copy() if batched else grads[0].copy()
         return loss, grad
 
-    def loss(self, params: ndarray) -> float:
-        llhd, _ = self._evaluate(params, False)
-        self.loss_value = llhd
-        return llhd
 
-    def grad(self, params: ndarray) -> ndarray:
-        _, jac = self._evaluate(params, True)
-        self.grad_value = jac
-        return jac
+class LOO(_MemoLoss):
+    """Leave-one-out negative log predictive density of the hyper-parameters (Rasmussen & Williams 5.4.2; new, not in the reference):
 
-    def loss_and_grad(self, params: ndarray) -> Tuple[float, ndarray]:
-        llhd, jac = self._evaluate(params, True)
-        self.loss_value = llhd
-        self.grad_value = jac
-        return (llhd, jac)
+        L_loo = sum_i [ -1/2 log c_i + alpha_i^2 / (2 c_i) ] + n/2 log 2pi,   c = diag(K^-1), alpha = K^-1 y
+        dL_loo/dtheta_k = 1/2 sum (S S^T + q q^T - p p^T) o dK_k,   S = K^-1 diag(sqrt(2 w)), w = 1/(2c) + alpha^2/(2c^2),
+                                                                    p, q = (alpha +- K^-1 (alpha / c)) / sqrt2
+
+    A second training objective with MLE's protocol (`CG(LOO(model))`), more robust than the marginal likelihood when the kernel family
+    is misspecified.  One evaluation = MLE's (build, Cholesky, L^-1, alpha, K^-1) + one pass over L^-1 for c (pg_loo_terms), the
+    mirror of K^-1, one pass that scales it to S and takes p, q (pg_loo_weights), the n^3-flop product S S^T on the GEMM core (lower
+    tiles), the rank-one fold (pg_loo_fold) and MLE's own contraction, pg_nlml_grad(S S^T + q q^T, p).  No third n x n buffer: c is
+    taken from `m` = L^-1 first, S overwrites `a` = K^-1 in place, S S^T goes over `m`.  Single models only."""
+
+    def _buffers(self, n_pad, dtype, nhp, n):
+        key = (n_pad, dtype, nhp, n)
+        if self._buf.get("key") != key:
+            ops = get_ops()
+            self._buf = {
+                "key": key,
+                "a": ops.empty(n_pad, n_pad, dtype=dtype),       # K -> L -> K^-1 -> S
+                "m": ops.empty(n_pad, n_pad, dtype=dtype),       # L^-1 -> S S^T + q q^T (a loss-only evaluation needs L^-1 too)
+                "invd": ops.potrf_workspace(n_pad, dtype),
+                "info": torch.zeros(1, dtype=torch.int32, device=ops.device),
+                "alpha": ops.zeros(n_pad, dtype=dtype),
+                "u": ops.empty(n_pad, dtype=dtype),
+                "vwork": ops.empty((n_pad // 256) * n_pad, dtype=dtype),
+                "c": ops.empty(n_pad, dtype=dtype), "mu": ops.empty(n_pad, dtype=dtype), "var": ops.empty(n_pad, dtype=dtype),
+                "p": ops.zeros(n_pad, dtype=dtype), "q": ops.zeros(n_pad, dtype=dtype),
+                "lwork": ops.empty(ops.loo_terms_worksize(n_pad), dtype=torch.float64),
+                "gwork": ops.empty(ops.nlml_grad_worksize(n, nhp), dtype=torch.float64),
+                "out": ops.zeros(1 + nhp, dtype=torch.float64),
+            }
+        return self._buf
+
+    def _evaluate_device(self, params: ndarray, want_grad: bool, key=None, reuse_factor=False):
+        ops = get_ops()
+        model = self.model
+        d = model.x.shape[-1]
+        spec, nhp = spec_of(model.cov, d)
+        p = np.asarray(params, dtype=np.float64)
+        assert p.shape[-1] == nhp
+        experts = model._device_data()
+        if p.reshape(-1, nhp).shape[0] != 1 or len(experts) != 1:
+            raise NotImplementedError("LOO: batched models (more than one expert) are not supported")
+        self._factor_key = None             # whatever the buffers held is overwritten below
+        e = experts[0]
+        buf = self._buffers(e.n_pad, model.dtype, nhp, e.n)
+        hp = ops.to_device(torch.from_numpy(p.reshape(nhp).copy()), torch.float64)
+        a, m, out, info = buf["a"], buf["m"], buf["out"], buf["info"]
+        res = [None]
+
+        def enqueue():
+            if not reuse_factor:
+                ops.build_factor(spec, hp, e.x, a, buf["invd"], info, m)       # covariance build + Cholesky + L^-1 in one call
+                ops.trmv(m, e.y, buf["u"], 0)
+                ops.trmv(m, buf["u"], buf["alpha"], 1, buf["vwork"])           # alpha = L^-T (L^-1 y)
+            # (reuse_factor: `m` still holds L^-1 and buf["alpha"] the weights of the loss-only evaluation at these parameters)
+            ops.loo_terms(m, buf["alpha"], e.y, e.n, buf["c"], buf["mu"], buf["var"], out, buf["lwork"])
+            if want_grad:
+                ops.lauum(m, a)                                                # K^-1 (lower) over the factor ...
+                ops.symmetrize(a, e.n_pad)                                     # ... mirrored: S = K^-1 diag(.) is not symmetric
+                ops.loo_weights(buf["c"], buf["alpha"], a, e.n, buf["p"], buf["q"])
+                ops.gemm_raw(_lib.GEMM_NT, e.n_pad, e.n_pad, e.n_pad, 1.0, a, a, 0.0, m, tri=1)     # S S^T (lower tiles) over L^-1
+                ops.loo_fold(m, buf["q"], e.n)
+                ops.nlml_grad(spec, hp, e.x, e.n, m, buf["p"], out[1:], buf["gwork"])
+            res[0] = out.cpu().numpy()                                         # the one sync + transfer
+
+        # (a timed-out coupled chain -- info = -1 -- repeats the evaluation on the classic chain; a re-used factor was checked when
+        # it was made and its status word still reads 0)
+        for st in _checked(enqueue, lambda: info.tolist()):
+            if st:
+                raise _lin_alg_error(st)
+        if not want_grad and key is not None:
+            self._factor_key = key
+        return np.array(res[0][0]), res[0][1:].copy()
