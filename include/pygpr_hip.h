@@ -399,7 +399,9 @@ int pg_rowstep_raw(pg_handle h, int dtype, int n, void* A, long lda, int o0, int
 
 /* raw MFMA GEMM core, exposed for tests and the roofline micro-benchmark:
  * variant 0: C = a A B^T + b C (128x128 tiles; tri != 0 -> lower tiles only), 2: C = a A B + b C,
- * 3: C = a A^T B + b C.  klo/khi as in csrc/gemm.h. */
+ * 3: C = a A^T B + b C.  klo/khi as in csrc/gemm.h.  A K range that follows the tile rows (klo or khi == 1) needs a row tile that is a
+ * multiple of the variant's K tile, one that follows the tile columns (== 2) such a column tile: every variant but the 32 x 32 tiling
+ * (K tile 64), which refuses klo/khi with -2 and a text before anything is enqueued.  tests/gemm_ref.py states the whole call in NumPy. */
 int pg_gemm_raw(pg_handle h, int dtype, int variant, int M, int N, int K, double alpha, const void* A, long lda,
                 const void* B, long ldb, double beta, void* C, long ldc, int tri, int klo, int khi, void* stream);
 

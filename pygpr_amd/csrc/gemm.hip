@@ -376,6 +376,13 @@ static int launch(hipStream_t st, const GemmP<T>& p) {
         pg_set_error("pg_gemm: shape %d x %d x %d not tile aligned (%d x %d)", p.M, p.N, p.K, BM, BN);
         return -2;
     }
+    // A K range that follows the tile rows (columns) starts and ends at multiples of BM (BN), and gemm_tile walks it in whole K tiles:
+    // a tiling whose tile is not a multiple of its K tile (32 x 32 with BKT = 64) would drop the rest of every range without a word.
+    if (((p.klo == 1 || p.khi == 1) && BM % BKT) || ((p.klo == 2 || p.khi == 2) && BN % BKT)) {
+        pg_set_error("pg_gemm: variant GEMM_%c%c_%dx%d takes no klo = %d / khi = %d: its %d x %d tile is not a multiple of its K tile (%d)",
+                     TA ? 'T' : 'N', TB ? 'T' : 'N', BM, BN, p.klo, p.khi, BM, BN, BKT);
+        return -2;
+    }
     const int tm = p.M / BM, tn = p.N / BN;
     if (p.tri && tn > tm) { pg_set_error("pg_gemm: tri with N = %d > M = %d", p.N, p.M); return -2; }
     const long tiles = p.tri ? (long)tn * (tn + 1) / 2 + (long)(tm - tn) * tn : (long)tm * tn;   // (tn < tm: a trapezoid)
