@@ -1,24 +1,29 @@
-// Covariance assembly (HBM-bound, O(n^2 d)) and the fused NLML-gradient contraction.
+// Covariance assembly (HBM-bound, O(n^2 d)) and the fused NLML-gradient contraction: entry points, routing and the VALU bodies.
 //
-// pg_kbuild: K[i][j] = sum_c k_c(r_i, c_j) (+ (sum sigma_n^2 + jitter) on the diagonal of a symmetric
-// build); k_c is the ARD squared exponential of PyGPR/covar.py:129-167 (hp = [sigma, l_1..l_d], l are
-// INVERSE length scales, no 1/2 in the exponent) or Matern-5/2, -3/2, -1/2 with the same hp layout.  Distances are
-// direct sums of squared differences (exactly symmetric, never negative) instead of the reference's
-// GEMM expansion (covar.py:102-127).  One 64x64 output tile per 256-thread workgroup; both point tiles
-// are staged in LDS k-major ([d][64]); each thread owns a 4x4 micro-tile whose columns are two 16-byte
-// vectors, so every store instruction writes 256 contiguous bytes per row.  Rows/columns >= the real
-// point count are padding: identity for a symmetric build (keeps the padded Cholesky trivial), zero
-// for a cross build.
+// pg_kbuild: K[i][j] = sum_c k_c(r_i, c_j) (+ (sum sigma_n^2 + jitter) on the diagonal of a symmetric build); k_c is the ARD squared
+// exponential of PyGPR/covar.py:129-167 (hp = [sigma, l_1..l_d], l are INVERSE length scales, no 1/2 in the exponent) or Matern-5/2,
+// -3/2, -1/2 with the same hp layout.  Rows/columns >= the real point count are padding: identity for a symmetric build (keeps the
+// padded Cholesky trivial), zero for a cross build.  Which body serves which input:
+//   * one child of kind SE / Matern-5/2 / Matern-3/2, d <= 16, no accumulate pass: the matrix-pipe kernel of kmfma.hip -- except the
+//     fp64 squared exponential at d <= 8, which the FAST body here serves at 0.63-0.66 of the HBM peak;
+//   * one fp64 SE child, no accumulate pass, d <= 8 or d > 16: kb_body<FAST>, the expansion |x|^2 + |x'|^2 - 2 x.x' on the VALU;
+//   * any other single child (Matern-1/2, d > 16, an accumulate pass): kb_body<PRESC>, direct differences of coordinates
+//     pre-multiplied by the inverse length scales;  several children: the general kb_body, l^2 applied per coordinate.
+// Direct differences are exactly symmetric and never negative (the reference expands into a GEMM, covar.py:102-127).  One 64x64
+// output tile per 256-thread workgroup at a time; both point tiles are staged in LDS k-major ([d][64]); each thread owns a 4x4
+// micro-tile whose columns are two 16-byte vectors, so every store instruction writes 256 contiguous bytes per row.
 //
-// pg_nlml_grad: g_k = 1/2 sum_ij (K^-1 - a a^T)_ij dK_ij/dtheta_k over the lower triangle, with dK
-// recomputed from the point tiles on the fly: dK/dsigma = 2K/sigma, dK/dl_k = -2 l_k D_k^2 K
-// (covar.py:169-206), dK/dsigma_n = 2 sigma_n I (covar.py:247-269); the Matern kinds as dK/dl_k = coef base l_k D_k^2
-// (kind_hcoef: coef / 2).  The reference materialises
-// dK[nhp,n,n] and solves against it (loss.py:116-121); this is the same number by the K^-1 route.
+// pg_nlml_grad: g_k = 1/2 sum_ij (K^-1 - a a^T)_ij dK_ij/dtheta_k over the lower triangle, with dK recomputed from the point tiles
+// on the fly: dK/dsigma = 2K/sigma, dK/dl_k = -2 l_k D_k^2 K (covar.py:169-206), dK/dsigma_n = 2 sigma_n I (covar.py:247-269); the
+// Matern kinds as dK/dl_k = coef base l_k D_k^2 (kind_hcoef: coef / 2).  The reference materialises dK[nhp,n,n] and solves against
+// it (loss.py:116-121); this is the same number by the K^-1 route.  One child of kind SE / Matern-5/2 / Matern-3/2 at d <= 16 takes
+// the matrix-pipe contraction of kmfma.hip; everything else (Matern-1/2, d > 16, several children, PG_GRAD_MFMA=0) takes
+// pg_grad_kernel here: direct differences on the VALU.
 #include "kbuild.h"
 #include "kfun.h"
 #include "kmfma.h"
 #include <cstdlib>
+#include <type_traits>
 
 #define KT 64
 #define TLD 65     // odd leading dimension of the LDS transpose tile: column writes are at worst 2-way conflicted
@@ -26,19 +31,6 @@
 template <typename T> struct VecOf;
 template <> struct VecOf<double> { typedef double type __attribute__((ext_vector_type(2))); static constexpr int N = 2; };
 template <> struct VecOf<float> { typedef float type __attribute__((ext_vector_type(4))); static constexpr int N = 4; };
-
-template <typename T> __device__ __forceinline__ T comp_value(int kind, T sig2, T sqd) {
-    if (kind == PG_KIND_RBF) return sig2 * pg_exp(-sqd);
-    if (kind == PG_KIND_SQDIST) return sqd;    // Squared_exponential.distance (covar.py:102-127): the scaled squared distance itself
-    const T r = sqrt(sqd);
-    if (kind == PG_KIND_MATERN12) return sig2 * pg_exp(-r);
-    if (kind == PG_KIND_MATERN32) {
-        const T s3 = (T)1.73205080756887729353;
-        return sig2 * ((T)1 + s3 * r) * pg_exp(-s3 * r);
-    }
-    const T s5 = (T)2.23606797749978969641;
-    return sig2 * ((T)1 + s5 * r + (T)(5.0 / 3.0) * sqd) * pg_exp(-s5 * r);
-}
 
 template <typename T>
 __device__ __forceinline__ void stage_points(T* dst, const T* __restrict__ X, long ldx, int npts, int p0, int d, int tid,
@@ -74,58 +66,22 @@ __device__ __forceinline__ void kb_body(const pg_covspec& spec, const T* xr, con
     for (int r = 0; r < 4; ++r)
 #pragma unroll
         for (int c = 0; c < 4; ++c) out[r][c] = (T)0;
-    if (FAST) {
-        T arg[4][4];
+    for (int cp = 0; cp < (FAST ? 1 : spec.ncomp); ++cp) {
+        const T* lc = l2 + cp * d;
+        T sq[4][4];      // the scaled squared distance; FAST: MINUS it, started at -|x|^2 - |x'|^2
         {
             T na[4], nb[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) na[r] = nrm_r[ty * 4 + r];
+            for (int r = 0; r < 4; ++r) na[r] = FAST ? nrm_r[ty * 4 + r] : (T)0;
 #pragma unroll
             for (int v = 0; v < NVC; ++v)
 #pragma unroll
-                for (int e = 0; e < VE; ++e) nb[v * VE + e] = nrm_c[v * (16 * VE) + tx * VE + e];
+                for (int e = 0; e < VE; ++e) nb[v * VE + e] = FAST ? nrm_c[v * (16 * VE) + tx * VE + e] : (T)0;
 #pragma unroll
             for (int r = 0; r < 4; ++r)
 #pragma unroll
-                for (int c = 0; c < 4; ++c) arg[r][c] = na[r] + nb[c];
+                for (int c = 0; c < 4; ++c) sq[r][c] = na[r] + nb[c];
         }
-#pragma unroll 2
-        for (int k = 0; k < d; ++k) {
-            T a[4], b[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) a[r] = xr[k * KT + ty * 4 + r];
-#pragma unroll
-            for (int v = 0; v < NVC; ++v) {
-                const vec_t bv = *reinterpret_cast<const vec_t*>(xc + k * KT + v * (16 * VE) + tx * VE);
-#pragma unroll
-                for (int e = 0; e < VE; ++e) b[v * VE + e] = bv[e];
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) arg[r][c] += a[r] * b[c];
-        }
-        // The expansion's absolute error is eps |x l|^2, not relative to the distance: near-duplicate points can come out with a slightly
-        // POSITIVE argument (K_ij > sigma^2) and, in a symmetric build, the diagonal off sigma^2 by that error.  One v_min per element
-        // keeps K_ij <= sigma^2; tiles on the diagonal take the exact 0 where a point meets itself (a NaN argument stays NaN).
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                T a = arg[r][c] > (T)0 ? (T)0 : arg[r][c];
-                if (CHECKED) {
-                    if (symmetric && tr == tc && ty * 4 + r == (c / VE) * (16 * VE) + tx * VE + (c % VE) && a == a) a = (T)0;
-                }
-                out[r][c] = (T)pg_exp_tab((double)a, tab);
-            }
-    }
-    for (int cp = 0; cp < (FAST ? 0 : spec.ncomp); ++cp) {
-        const T* lc = l2 + cp * d;
-        T sq[4][4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) sq[r][c] = (T)0;
 #pragma unroll 2
         for (int k = 0; k < d; ++k) {      // (two coordinates' LDS reads in flight per trip)
             T a[4], b[4];
@@ -137,54 +93,46 @@ __device__ __forceinline__ void kb_body(const pg_covspec& spec, const T* xr, con
 #pragma unroll
                 for (int e = 0; e < VE; ++e) b[v * VE + e] = bv[e];
             }
-            if (PRESC) {
+            const T w = (FAST || PRESC) ? (T)1 : lc[k];
 #pragma unroll
-                for (int r = 0; r < 4; ++r)
+            for (int r = 0; r < 4; ++r)
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        const T df = a[r] - b[c];
-                        sq[r][c] += df * df;
-                    }
-            } else {
-                const T w = lc[k];
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        const T df = a[r] - b[c];
-                        sq[r][c] += w * df * df;
-                    }
-            }
+                for (int c = 0; c < 4; ++c) {
+                    if (FAST) sq[r][c] += a[r] * b[c];
+                    else if (PRESC) { const T df = a[r] - b[c]; sq[r][c] += df * df; }
+                    else { const T df = a[r] - b[c]; sq[r][c] += w * df * df; }
+                }
         }
-        // the kind is decided ONCE for the sixteen elements: with the dispatch inside the element loop every covariance value sat
-        // behind its own branch and the sixteen exponentials ran one after the other, each a chain of dependent operations
-        const int kind = spec.kind[cp];
-        const T s2 = sg2[cp];
-        if (kind == PG_KIND_RBF) {
+        if (FAST) {
+            // The expansion's absolute error is eps |x l|^2, not relative to the distance: near-duplicate points can come out with a slightly
+            // POSITIVE argument (K_ij > sigma^2) and, in a symmetric build, the diagonal off sigma^2 by that error.  One v_min per element
+            // keeps K_ij <= sigma^2; tiles on the diagonal take the exact 0 where a point meets itself (a NaN argument stays NaN).
 #pragma unroll
             for (int r = 0; r < 4; ++r)
 #pragma unroll
-                for (int c = 0; c < 4; ++c) out[r][c] += s2 * pg_exp(-sq[r][c]);
-        } else if (kind == PG_KIND_SQDIST) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) out[r][c] += sq[r][c];
-        } else if (kind == PG_KIND_MATERN52) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) out[r][c] += comp_value<T>(PG_KIND_MATERN52, s2, sq[r][c]);
-        } else if (kind == PG_KIND_MATERN32) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) out[r][c] += comp_value<T>(PG_KIND_MATERN32, s2, sq[r][c]);
+                for (int c = 0; c < 4; ++c) {
+                    T a = sq[r][c] > (T)0 ? (T)0 : sq[r][c];
+                    if (CHECKED) {
+                        if (symmetric && tr == tc && ty * 4 + r == (c / VE) * (16 * VE) + tx * VE + (c % VE) && a == a) a = (T)0;
+                    }
+                    out[r][c] = (T)pg_exp_tab((double)a, tab);
+                }
         } else {
+            // the kind is decided ONCE for the sixteen elements: with the dispatch inside the element loop every covariance value sat
+            // behind its own branch and the sixteen exponentials ran one after the other, each a chain of dependent operations
+            const int kind = spec.kind[cp];
+            const T s2 = sg2[cp];
+            auto add = [&](auto kind_c) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
+                for (int r = 0; r < 4; ++r)
 #pragma unroll
-                for (int c = 0; c < 4; ++c) out[r][c] += comp_value<T>(PG_KIND_MATERN12, s2, sq[r][c]);
+                    for (int c = 0; c < 4; ++c) out[r][c] += kind_value<T, decltype(kind_c)::value>(s2, sq[r][c]);
+            };
+            if (kind == PG_KIND_RBF) add(std::integral_constant<int, PG_KIND_RBF>{});
+            else if (kind == PG_KIND_SQDIST) add(std::integral_constant<int, PG_KIND_SQDIST>{});
+            else if (kind == PG_KIND_MATERN52) add(std::integral_constant<int, PG_KIND_MATERN52>{});
+            else if (kind == PG_KIND_MATERN32) add(std::integral_constant<int, PG_KIND_MATERN32>{});
+            else add(std::integral_constant<int, PG_KIND_MATERN12>{});
         }
     }
     const T dg = sg2[PG_MAX_COMP];
@@ -255,7 +203,7 @@ __global__ __launch_bounds__(256) void pg_kbuild_kernel(pg_covspec spec, const d
     T* tt = sg2 + PG_MAX_COMP + 2;  // MIRROR: [64][TLD] transposed tile
     T* nrm = tt + (MIRROR ? KT * TLD : 0);                      // fast path: -|x|^2 of the row points [64], of the column points [2][64]
     double* tab = reinterpret_cast<double*>(nrm + 3 * KT);      // fast path: sigma^2 2^(j/32) [32] (fp64 builds only)
-    constexpr bool fast = FASTK;                                // host: one squared-exponential component, fp64, PG_KB_FAST (presc = 2)
+    constexpr bool fast = FASTK;                                // host: one squared-exponential component, fp64, no accumulate pass (presc = 2)
     const int tid = threadIdx.x;
     const double* scale = presc ? hp + spec.off[0] + 1 : nullptr;
     // this thread's share of a point tile: elements idx = tid + 256 u < 64 d  ->  point idx / d, coordinate idx % d
@@ -308,21 +256,17 @@ __global__ __launch_bounds__(256) void pg_kbuild_kernel(pg_covspec spec, const d
         tab[tid] = sg * sg * pg_exp2_32[tid];
     }
     __syncthreads();
-    // -|x|^2 per staged point, one thread per point (rows: staged times two, hence the quarter)
-    auto col_norms = [&](const T* pts, T* dst) {
-        if (tid < KT) {
+    // dst[p] = mul |x_p|^2 per staged point, thread t0 + p for point p (columns: mul = -1; rows: staged times two, hence -1/4)
+    auto norms = [&](const T* pts, T* dst, int t0, T mul) {
+        if (tid >= t0 && tid < t0 + KT) {
             T sacc = (T)0;
-            for (int k = 0; k < d; ++k) { const T v = pts[k * KT + tid]; sacc += v * v; }
-            dst[tid] = -sacc;
+            for (int k = 0; k < d; ++k) { const T v = pts[k * KT + tid - t0]; sacc += v * v; }
+            dst[tid - t0] = mul * sacc;
         }
     };
     if (fast) {
-        if (tid >= KT && tid < 2 * KT) {
-            T sacc = (T)0;
-            for (int k = 0; k < d; ++k) { const T v = xr[k * KT + tid - KT]; sacc += v * v; }
-            nrm[tid - KT] = (T)-0.25 * sacc;
-        }
-        col_norms(xc, nrm + KT);
+        norms(xr, nrm, KT, (T)-0.25);
+        norms(xc, nrm + KT, 0, (T)-1);
         __syncthreads();
     }
     // workgroup-uniform: every tile of the strip lies strictly below the diagonal (or the build is a cross build) and inside the
@@ -330,38 +274,24 @@ __global__ __launch_bounds__(256) void pg_kbuild_kernel(pg_covspec spec, const d
     // in the tile loop the kernel needed 160 VGPRs (three workgroups per CU instead of four).
     const int tcl = tcs + ntile - 1;
     const bool interior = !accumulate && (!symmetric || tcl < tr) && (tr + 1) * KT <= nr && (tcl + 1) * KT <= nc;
-    auto walk = [&](auto body) {
+    auto walk = [&](auto presc_c, auto checked_c) {      // the strip through kb_body<T, PRESC, CHECKED, MIRROR, FASTK>
         for (int t = 0; t < ntile; ++t) {
-            const int tc = tcs + t;
-            const T* cur = xc + (t & 1) * KT * d;
+            const int tc = tcs + t, cur = t & 1, nxt = cur ^ 1;
             if (t + 1 < ntile) load_cols(tc + 1);           // in flight while this tile is computed
-            body(cur, tc);
+            kb_body<T, decltype(presc_c)::value, decltype(checked_c)::value, MIRROR, FASTK>(
+                spec, xr, xc + cur * KT * d, l2, sg2, tt, d, tr, tc, nr, nc, symmetric, accumulate, K, ldk, tid, nrm, nrm + KT + cur * KT, tab);
             if (t + 1 < ntile) {
-                store_cols(xc + ((t + 1) & 1) * KT * d);
+                store_cols(xc + nxt * KT * d);
                 __syncthreads();   // publishes the next tile's points; also orders this tile's reads of `tt` before the next one's writes
                 if (fast) {
-                    col_norms(xc + ((t + 1) & 1) * KT * d, nrm + KT + ((t + 1) & 1) * KT);
+                    norms(xc + nxt * KT * d, nrm + KT + nxt * KT, 0, (T)-1);
                     __syncthreads();
                 }
             }
         }
     };
-#define KB_ARGS(cur, tc) spec, xr, cur, l2, sg2, tt, d, tr, tc, nr, nc, symmetric, accumulate, K, ldk, tid
-    if constexpr (FASTK) {
-#define KB_FARGS(cur, tc) KB_ARGS(cur, tc), nrm, nrm + KT + (int)((cur - xc) / (KT * d)) * KT, tab
-        if (interior) walk([&](const T* cur, int tc) { kb_body<T, true, false, MIRROR, true>(KB_FARGS(cur, tc)); });
-        else walk([&](const T* cur, int tc) { kb_body<T, true, true, MIRROR, true>(KB_FARGS(cur, tc)); });
-#undef KB_FARGS
-    } else {
-        if (presc) {
-            if (interior) walk([&](const T* cur, int tc) { kb_body<T, true, false, MIRROR>(KB_ARGS(cur, tc)); });
-            else walk([&](const T* cur, int tc) { kb_body<T, true, true, MIRROR>(KB_ARGS(cur, tc)); });
-        } else {
-            if (interior) walk([&](const T* cur, int tc) { kb_body<T, false, false, MIRROR>(KB_ARGS(cur, tc)); });
-            else walk([&](const T* cur, int tc) { kb_body<T, false, true, MIRROR>(KB_ARGS(cur, tc)); });
-        }
-    }
-#undef KB_ARGS
+    if (FASTK || presc) { if (interior) walk(std::true_type{}, std::false_type{}); else walk(std::true_type{}, std::true_type{}); }
+    else if constexpr (!FASTK) { if (interior) walk(std::false_type{}, std::false_type{}); else walk(std::false_type{}, std::true_type{}); }
 }
 
 // An empty operand (nr == 0 or nc == 0): the whole output is padding -- identity for a symmetric build (lower tiles only unless
@@ -378,6 +308,25 @@ __global__ __launch_bounds__(256) void pg_kbuild_pad_kernel(T* __restrict__ K, l
     }
 }
 
+// LDS of pg_kbuild_kernel in bytes at dimension d (the fast body's norms and table are always counted)
+template <typename T> static constexpr size_t kb_lds_bytes(int d, bool mirror) {
+    return (size_t)(3 * KT * d + PG_MAX_COMP * d + PG_MAX_COMP + 2 + (mirror ? KT * TLD : 0) + 3 * KT) * sizeof(T) + 32 * sizeof(double);
+}
+
+// One instantiation of pg_kbuild_kernel: its dynamic-LDS limit once, then the launch.
+template <typename T, bool MIRROR, int NPF, bool FAST, typename... Args>
+static int kb_launch(dim3 grid, size_t lds, hipStream_t st, Args... args) {
+    static bool attr_done = false;
+    if (!attr_done) {   // large d passes the 64 KB a kernel gets without opting in (134 KB for the mirrored fp64 build at d = 64)
+        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_kbuild_kernel<T, MIRROR, NPF, FAST>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kb_lds_bytes<T>(PG_MAX_DIM, true)));
+        attr_done = true;
+    }
+    hipLaunchKernelGGL((pg_kbuild_kernel<T, MIRROR, NPF, FAST>), grid, dim3(256), lds, st, args...);
+    PG_CHECK(hipGetLastError());
+    return 0;
+}
+
 template <typename T>
 int pg_kbuild(hipStream_t st, const pg_covspec& spec, const double* hp, const T* Xr, long ldr, int nr,
               const T* Xc, long ldc, int nc, int d, int symmetric, int lower_only, int accumulate, double jitter, T* K,
@@ -388,16 +337,7 @@ int pg_kbuild(hipStream_t st, const pg_covspec& spec, const double* hp, const T*
         return -2;
     }
     const bool mirror = symmetric && !lower_only;
-    const size_t lds = (size_t)(3 * KT * d + PG_MAX_COMP * d + PG_MAX_COMP + 2 + (mirror ? KT * TLD : 0) + 3 * KT) * sizeof(T) + 32 * sizeof(double);
-    static bool attr_done = false;
-    if (!attr_done) {   // large d passes the 64 KB a kernel gets without opting in (134 KB for the mirrored fp64 build at d = 64)
-        const size_t lds_max = (size_t)(3 * KT * PG_MAX_DIM + PG_MAX_COMP * PG_MAX_DIM + PG_MAX_COMP + 2 + KT * TLD + 3 * KT) * sizeof(T) + 32 * sizeof(double);
-        const void* fns[6] = {reinterpret_cast<const void*>(pg_kbuild_kernel<T, true, 2>), reinterpret_cast<const void*>(pg_kbuild_kernel<T, true, 4>),
-                              reinterpret_cast<const void*>(pg_kbuild_kernel<T, true, 16>), reinterpret_cast<const void*>(pg_kbuild_kernel<T, false, 2>),
-                              reinterpret_cast<const void*>(pg_kbuild_kernel<T, false, 4>), reinterpret_cast<const void*>(pg_kbuild_kernel<T, false, 16>)};
-        for (const void* f : fns) PG_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-        attr_done = true;
-    }
+    const size_t lds = kb_lds_bytes<T>(d, mirror);
     // columns [col0, col1) only (col1 <= 0: all): a lower-only symmetric build in two column windows lets the factorisation
     // start on the first panel while the rest is still being written (pg_potrf_t, BuildReq)
     if (col1 <= 0) { col0 = 0; col1 = cols_pad; }
@@ -427,12 +367,10 @@ int pg_kbuild(hipStream_t st, const pg_covspec& spec, const double* hp, const T*
     // symmetric: the triangle of the window's own tile rows plus the rectangle below it; cross build: every tile of the window
     const long strips = symmetric ? kb_strips_before(W, S) + (long)(TR - c1) * SW : (long)TR * SW;
     if (strips <= 0) return 0;
-    // one stationary component (the common Compose([SE, WN])): its inverse length scales go into the staged coordinates.  In fp64
-    // (x l) - (x' l) rounds differently from l^2 (x - x')^2 in the last bit; PG_KB_PRESC=0 keeps the unscaled form
-    static const int presc_env = getenv("PG_KB_PRESC") ? atoi(getenv("PG_KB_PRESC")) : 1;
-    // ... and when that component is the squared exponential, fp64 builds take the fast body (kb_body, FAST): presc = 2
-    static const int fast_env = getenv("PG_KB_FAST") ? atoi(getenv("PG_KB_FAST")) : 1;
-    const int presc = (presc_env && spec.ncomp == 1) ? ((fast_env && sizeof(T) == 8 && spec.kind[0] == PG_KIND_RBF && !accumulate) ? 2 : 1) : 0;
+    // one stationary component (the common Compose([SE, WN])): its inverse length scales go into the staged coordinates (presc = 1; in
+    // fp64 (x l) - (x' l) rounds differently from l^2 (x - x')^2 in the last bit) ... and when that component is the squared
+    // exponential, fp64 builds take the fast body (kb_body, FAST): presc = 2.  Several components: presc = 0
+    const int presc = spec.ncomp != 1 ? 0 : ((sizeof(T) == 8 && spec.kind[0] == PG_KIND_RBF && !accumulate) ? 2 : 1);
     // One stationary component, d <= 16, no accumulate pass: the distance on the matrix pipe (kmfma.hip).  PG_KB_MFMA = 0: never;
     // 1 (default): wherever the VALU bodies have no fast form -- d > 8, Matern-5/2 and -3/2, fp32; 2: also for the fp64 squared exponential at
     // d <= 8, which the fast body of round 3 serves at 0.63-0.66 of the HBM peak.
@@ -445,33 +383,22 @@ int pg_kbuild(hipStream_t st, const pg_covspec& spec, const double* hp, const T*
         return pg_kbuild_mfma<T>(st, spec, hp, Xr, ldr, nr, Xc, ldc, nc, d, symmetric, mirror ? 1 : 0, jitter, K, ldk, c0, c1, S, strips, nexp, eX,
                                  ehp, eK, eXr);
     const int npf = d <= 8 ? 2 : (d <= 16 ? 4 : 16);
-#define KB_LAUNCH(M, P, F)                                                                                                           \
-    hipLaunchKernelGGL((pg_kbuild_kernel<T, M, P, F>), dim3((unsigned)strips, (unsigned)nexp), dim3(256), lds, st, spec, hp, Xr, ldr, nr, Xc, \
-                       ldc, nc, d, symmetric, accumulate, jitter, K, ldk, c0, c1, presc, S, eX, ehp, eK, eXr)
-    bool launched = false;
+    // (mirror, npf, fast) -> kb_launch<T, MIRROR, NPF, FAST>; the fast body exists in fp64 only
+    auto go = [&](auto mirror_c, auto npf_c, auto fast_c) {
+        return kb_launch<T, decltype(mirror_c)::value, decltype(npf_c)::value, decltype(fast_c)::value>(
+            dim3((unsigned)strips, (unsigned)nexp), lds, st, spec, hp, Xr, ldr, nr, Xc, ldc, nc, d, symmetric, accumulate, jitter, K, ldk, c0, c1,
+            presc, S, eX, ehp, eK, eXr);
+    };
+    auto with_npf = [&](auto mirror_c, auto fast_c) {
+        if (npf == 2) return go(mirror_c, std::integral_constant<int, 2>{}, fast_c);
+        if (npf == 4) return go(mirror_c, std::integral_constant<int, 4>{}, fast_c);
+        return go(mirror_c, std::integral_constant<int, 16>{}, fast_c);
+    };
+    auto with_mirror = [&](auto fast_c) { return mirror ? with_npf(std::true_type{}, fast_c) : with_npf(std::false_type{}, fast_c); };
     if constexpr (sizeof(T) == 8) {
-        if (presc == 2) {
-            static bool fattr = false;
-            if (!fattr) {
-                const size_t lds_max = (size_t)(3 * KT * PG_MAX_DIM + PG_MAX_COMP * PG_MAX_DIM + PG_MAX_COMP + 2 + KT * TLD + 3 * KT) * sizeof(T) + 32 * sizeof(double);
-                const void* fns[6] = {reinterpret_cast<const void*>(pg_kbuild_kernel<T, true, 2, true>), reinterpret_cast<const void*>(pg_kbuild_kernel<T, true, 4, true>),
-                                      reinterpret_cast<const void*>(pg_kbuild_kernel<T, true, 16, true>), reinterpret_cast<const void*>(pg_kbuild_kernel<T, false, 2, true>),
-                                      reinterpret_cast<const void*>(pg_kbuild_kernel<T, false, 4, true>), reinterpret_cast<const void*>(pg_kbuild_kernel<T, false, 16, true>)};
-                for (const void* f : fns) PG_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-                fattr = true;
-            }
-            if (mirror) { if (npf == 2) KB_LAUNCH(true, 2, true); else if (npf == 4) KB_LAUNCH(true, 4, true); else KB_LAUNCH(true, 16, true); }
-            else { if (npf == 2) KB_LAUNCH(false, 2, true); else if (npf == 4) KB_LAUNCH(false, 4, true); else KB_LAUNCH(false, 16, true); }
-            launched = true;
-        }
+        if (presc == 2) return with_mirror(std::true_type{});
     }
-    if (!launched) {
-        if (mirror) { if (npf == 2) KB_LAUNCH(true, 2, false); else if (npf == 4) KB_LAUNCH(true, 4, false); else KB_LAUNCH(true, 16, false); }
-        else { if (npf == 2) KB_LAUNCH(false, 2, false); else if (npf == 4) KB_LAUNCH(false, 4, false); else KB_LAUNCH(false, 16, false); }
-    }
-#undef KB_LAUNCH
-    PG_CHECK(hipGetLastError());
-    return 0;
+    return with_mirror(std::false_type{});
 }
 template int pg_kbuild<double>(hipStream_t, const pg_covspec&, const double*, const double*, long, int,
                                const double*, long, int, int, int, int, int, double, double*, long, int, int, int, int, int, long, long, long, long);
@@ -501,15 +428,10 @@ __global__ __launch_bounds__(256) void pg_kgrad_kernel(pg_covspec spec, const do
             const T df = xi[k] - xj[k];
             sq += (T)(l * l) * df * df;
         }
-        T kv, base, coef;
-        if (spec.kind[cp] == PG_KIND_RBF) {
-            kv = (T)(sg * sg) * pg_exp(-sq);
-            base = kv;
-            coef = (T)-2;
-        } else {
-            matern_val<T>(spec.kind[cp], (T)(sg * sg), sq, kv, base);
-            coef = (T)(2.0 * kind_hcoef(spec.kind[cp]));
-        }
+        T kv, base;
+        if (spec.kind[cp] == PG_KIND_RBF) kind_eval<T, PG_KIND_RBF>((T)(sg * sg), sq, kv, base);
+        else matern_val<T>(spec.kind[cp], (T)(sg * sg), sq, kv, base);
+        const T coef = (T)(2.0 * kind_hcoef(spec.kind[cp]));
         dK[(long)o * slab + e] = kv * (T)(2.0 / sg);
         for (int k = 0; k < d; ++k) {
             const T df = xi[k] - xj[k];
@@ -661,7 +583,7 @@ __global__ __launch_bounds__(256) void pg_grad_kernel(pg_covspec spec, const dou
                 }
                 double kv, base;   // dK/dl_k = base * l_k * D_k^2 (sign and constants applied in the reduce)
                 if (kind == PG_KIND_RBF) {
-                    kv = (double)(sig2 * pg_exp(-sq));
+                    kv = (double)kind_value<T, PG_KIND_RBF>(sig2, sq);
                     base = kv;
                 } else {
                     T kt, bt;
@@ -701,135 +623,8 @@ __global__ __launch_bounds__(256) void pg_grad_kernel(pg_covspec spec, const dou
     }
 }
 
-// The contraction's fast body (round 4): fp64, ONE squared-exponential child (the common Compose([SE, WN])) and d <= 8 -- what round 3
-// did for the covariance build (kb_body<FAST>).  The general kernel above walks a thread's sixteen elements two at a time, each behind
-// its own degree-13 exponential chain: 0.82 ms at N = 16384, D = 8 for 1.07 GB of K^-1 (1.3 TB/s), a third of the fp64 issue rate.  Here
-//   * a thread owns a 4 x 4 micro-tile (rows ty*4 + r, columns v*32 + tx*2 + e: 16-byte loads of K^-1, 256-byte runs per row) whose
-//     sixteen elements are INDEPENDENT chains: distances, exponentials and weights interleave;
-//   * the inverse length scales are folded into the staged coordinates (one subtract + one FMA per coordinate; the partial sums of the
-//     length-scale entries then hold l_k^2 D_k^2 and the reduce divides by l_k: `presc`), differences stay DIRECT -- the per-coordinate
-//     squares are needed anyway, and they keep the weights of near-duplicate points exact;
-//   * the exponential is pg_exp_tab with sigma^2 folded into its table;
-//   * tiles strictly below the diagonal and inside the real points take a body without per-element tests (weight 2 everywhere).
-template <int DMAX>
-__global__ __launch_bounds__(256, 3) void pg_grad_fast_kernel(pg_covspec spec, const double* __restrict__ hp, const double* __restrict__ X,
-                                                           long ldx, int n, int d, const double* __restrict__ Kinv, long ldk,
-                                                           const double* __restrict__ alpha, double* __restrict__ part, int nhp, GradBatch gb) {
-    typedef double vec_t __attribute__((ext_vector_type(2)));
-    X += blockIdx.z * gb.eX; hp += blockIdx.z * gb.ehp; Kinv += blockIdx.z * gb.eK; alpha += blockIdx.z * gb.ea; part += blockIdx.z * gb.epart;
-    const int tr = blockIdx.y;
-    const int c0 = blockIdx.x * GCH, c1 = min(c0 + GCH, tr + 1);
-    const int blk = tr * gridDim.x + blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int idx = tid; idx < nhp; idx += 256) part[(long)blk * nhp + idx] = 0.0;
-    if (c0 > tr) return;
-    __shared__ double red[4][DMAX + 2];
-    __shared__ double xr[DMAX * KT], xc[2][DMAX * KT], ar[KT], ac[2][KT], tab[32];
-    const int o = spec.off[0];
-    const double* scale = hp + o + 1;
-    auto stage = [&](double* dst, double* adst, int t0) {
-        for (int idx = tid; idx < KT * DMAX; idx += 256) {
-            const int p = idx / DMAX, k = idx % DMAX;
-            const int g = t0 * KT + p;
-            dst[k * KT + p] = (k < d && g < n) ? X[(long)g * ldx + k] * scale[k] : 0.0;
-        }
-        if (tid < KT) adst[tid] = (t0 * KT + tid < n) ? alpha[t0 * KT + tid] : 0.0;
-    };
-    stage(xr, ar, tr);
-    if (tid < 32) { const double sg = hp[o]; tab[tid] = sg * sg * pg_exp2_32[tid]; }
-    const int tx = tid & 15, ty = tid >> 4;
-    double acc[DMAX + 1];
-#pragma unroll
-    for (int k = 0; k <= DMAX; ++k) acc[k] = 0.0;
-    double tr_w = 0.0;
-    for (int tc = c0, it = 0; tc < c1; ++tc, ++it) {
-        double* xb = xc[it & 1];
-        double* ab = ac[it & 1];
-        stage(xb, ab, tc);
-        const bool interior = tc < tr && (tr + 1) * KT <= n;
-        __syncthreads();   // publishes the staged tile; also orders this buffer's previous readers (two tiles ago) before the writes above
-        // The micro-tile in two halves of 4 rows x 2 columns (eight independent chains each).  All sixteen elements at once, or halves
-        // whose coordinates the compiler keeps in registers across both passes, need 170-270 VGPRs (one wave per SIMD): the column
-        // points of a half are held on purpose (2 DMAX doubles), the row points are re-read from LDS in the second pass.
-#pragma unroll 1
-        for (int v = 0; v < 2; ++v) {
-            const int cb = v * 32 + tx * 2;
-            const int gj0 = tc * KT + cb;
-            vec_t kin[4];     // this half's eight K^-1 values: in flight while the distances are summed (the row's stride ldk is even and covers the padding)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                kin[r] = *reinterpret_cast<const vec_t*>(Kinv + (long)min(tr * KT + ty * 4 + r, n - 1) * ldk + min(gj0, (int)ldk - 2));
-            vec_t b[DMAX];
-#pragma unroll
-            for (int k = 0; k < DMAX; ++k) b[k] = *reinterpret_cast<const vec_t*>(xb + k * KT + cb);
-            const vec_t aj = *reinterpret_cast<const vec_t*>(ab + cb);
-            double sq[4][2];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) sq[r][0] = sq[r][1] = 0.0;
-#pragma unroll
-            for (int k = 0; k < DMAX; ++k) {
-                const vec_t a01 = *reinterpret_cast<const vec_t*>(xr + k * KT + ty * 4), a23 = *reinterpret_cast<const vec_t*>(xr + k * KT + ty * 4 + 2);
-                const double a[4] = {a01[0], a01[1], a23[0], a23[1]};
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-#pragma unroll
-                    for (int c = 0; c < 2; ++c) {
-                        const double df = a[r] - b[k][c];
-                        sq[r][c] = __builtin_fma(df, df, sq[r][c]);
-                    }
-            }
-            // W = weight * (K^-1 - a a^T), times the covariance value
-            double wb[4][2];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const double ai = ar[ty * 4 + r];
-#pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                    double w = __builtin_fma(-ai, aj[c], kin[r][c]);
-                    if (interior) w *= 2.0;
-                    else {
-                        const int gi = tr * KT + ty * 4 + r, gj = gj0 + c;
-                        if (gi >= n || gj > gi) w = 0.0;
-                        else if (gj < gi) w *= 2.0;
-                        else tr_w += w;
-                    }
-                    wb[r][c] = w * pg_exp_tab(-sq[r][c], tab);
-                    acc[0] += wb[r][c];
-                }
-            }
-            asm volatile("" ::: "memory");    // second pass: re-read the row points instead of keeping 4 DMAX doubles alive
-#pragma unroll
-            for (int k = 0; k < DMAX; ++k) {
-                const vec_t a01 = *reinterpret_cast<const vec_t*>(xr + k * KT + ty * 4), a23 = *reinterpret_cast<const vec_t*>(xr + k * KT + ty * 4 + 2);
-                const double a[4] = {a01[0], a01[1], a23[0], a23[1]};
-                double s = 0.0;
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-#pragma unroll
-                    for (int c = 0; c < 2; ++c) {
-                        const double df = a[r] - b[k][c];
-                        s = __builtin_fma(wb[r][c], df * df, s);
-                    }
-                acc[1 + k] += s;
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k <= DMAX; ++k) {
-        const double s = wave_sum(acc[k]);
-        if (lane == 0) red[wave][k] = s;
-    }
-    {
-        const double s = wave_sum(tr_w);
-        if (lane == 0) red[wave][DMAX + 1] = s;
-    }
-    __syncthreads();
-    if (tid <= d) part[(long)blk * nhp + o + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
-    if (tid < spec.nnoise)
-        part[(long)blk * nhp + spec.noise_off[tid]] = red[0][DMAX + 1] + red[1][DMAX + 1] + red[2][DMAX + 1] + red[3][DMAX + 1];
-}
-
-// grad[p] = scale_p * sum_blocks part[b][p]
+// grad[p] = scale_p * sum_blocks part[b][p].  presc: the partial sums came from pg_grad_mfma (kmfma.hip), whose length-scale entries
+// hold sums of (l_k D_k)^2 -- the inverse length scales are folded into its staged coordinates; pg_grad_kernel sums D_k^2 (presc = 0).
 __global__ __launch_bounds__(256) void pg_grad_reduce_kernel(pg_covspec spec, const double* __restrict__ hp,
                                                              const double* __restrict__ part, int nblk, int nhp,
                                                              int d, double* __restrict__ grad, int presc, GradBatch gb) {
@@ -851,7 +646,7 @@ __global__ __launch_bounds__(256) void pg_grad_reduce_kernel(pg_covspec spec, co
             else if (p > o && p <= o + d) {
                 const double hc = kind_hcoef(spec.kind[c]);      // SE: -2 l_k D_k^2 K, Matern: coef base l_k D_k^2
                 scale = hc * hp[p];
-                // the fast contraction summed (l_k D_k)^2: -l_k S = -S' / l_k (l_k = 0: S' = 0 and the derivative is 0)
+                // the matrix-pipe contraction summed (l_k D_k)^2: -l_k S = -S' / l_k (l_k = 0: S' = 0 and the derivative is 0)
                 if (presc) scale = hp[p] != 0.0 ? hc / hp[p] : 0.0;
                 mine = true;
             }
@@ -888,8 +683,8 @@ int pg_nlml_grad_t(hipStream_t st, const pg_covspec& spec, const double* hp, con
     if (lwork < need * nexp) { pg_set_error("pg_nlml_grad: workspace %ld < %ld doubles", lwork, need * nexp); return -3; }
     const GradBatch gb = {eX, ehp, eK, ea, need, egrad};
     int rc;
-    static const int fast_env = getenv("PG_GRAD_FAST") ? atoi(getenv("PG_GRAD_FAST")) : 1;
-    // One stationary component, d <= 16: the contraction on the matrix pipe (kmfma.hip; PG_GRAD_MFMA=0 restores the VALU kernels)
+    // One stationary component, d <= 16: the contraction on the matrix pipe (kmfma.hip; PG_GRAD_MFMA=0: pg_grad_kernel for every input,
+    // the independent direct-difference yardstick of the tests)
     const int mfma_env = getenv("PG_GRAD_MFMA") ? atoi(getenv("PG_GRAD_MFMA")) : 1;   // (read per call: tests compare the bodies in one process)
     // (not Matern-1/2: its factor e^-r / r is unbounded near r = 0, and the expansion's cancellation error is u |x|^2 sum |G| -- DESIGN.md)
     if (mfma_env && spec.ncomp == 1 && d <= 16 && n >= 1 &&
@@ -900,19 +695,7 @@ int pg_nlml_grad_t(hipStream_t st, const pg_covspec& spec, const double* hp, con
         PG_CHECK(hipGetLastError());
         return 0;
     }
-    int presc = 0;
-    if constexpr (sizeof(T) == 8) {
-        // (d <= 8: with sixteen coordinates the held column points alone are 64 VGPRs and the kernel spills)
-        if (fast_env && spec.ncomp == 1 && spec.kind[0] == PG_KIND_RBF && d <= 8 && n >= 2 && ldk % 2 == 0) {
-            const dim3 grid((tiles + GCH - 1) / GCH, tiles, nexp);
-            if (d <= 4) hipLaunchKernelGGL(pg_grad_fast_kernel<4>, grid, dim3(256), 0, st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, gb);
-            else hipLaunchKernelGGL(pg_grad_fast_kernel<8>, grid, dim3(256), 0, st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, gb);
-            PG_CHECK(hipGetLastError());
-            presc = 1;
-        }
-    }
-    if (presc) rc = 0;
-    else if (d <= 4) rc = launch_grad<T, 4>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
+    if (d <= 4) rc = launch_grad<T, 4>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
     else if (d <= 8) rc = launch_grad<T, 8>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
     else if (d <= 16) rc = launch_grad<T, 16>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
     else if (d <= 32) rc = launch_grad<T, 32>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
@@ -920,7 +703,7 @@ int pg_nlml_grad_t(hipStream_t st, const pg_covspec& spec, const double* hp, con
     else { pg_set_error("pg_nlml_grad: d=%d > %d", d, PG_MAX_DIM); return -2; }
     if (rc) return rc;
     hipLaunchKernelGGL(pg_grad_reduce_kernel, dim3(nhp, 1, nexp), dim3(256), 0, st, spec, hp, work, tiles * ((tiles + GCH - 1) / GCH), nhp,
-                       d, grad, presc, gb);
+                       d, grad, 0, gb);
     PG_CHECK(hipGetLastError());
     return 0;
 }

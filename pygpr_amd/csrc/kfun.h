@@ -1,4 +1,6 @@
 // Device helpers shared by the covariance / gradient tile kernels (kbuild.hip: VALU bodies; kmfma.hip: matrix-pipe bodies).
+// pg_exp: the direct-difference VALU bodies (kind_eval below; xgrad.hip).  pg_exp_tab: the VALU build's fast body (fp64 squared exponential)
+// and every fp64 matrix-pipe body, whose Matern forms take their root from pg_sqrt_pos (the fp32 ones use the hardware's own, kmfma.hip).
 #pragma once
 #include "common.h"
 
@@ -74,7 +76,7 @@ __device__ __forceinline__ double pg_sqrt_pos(double x) {
     return r;
 }
 
-// Half the factor `coef` of the length-scale derivative dK/dl_k = coef base l_k D_k^2, per stationary kind (base: see pg_grad_kernel)
+// Half the factor `coef` of the length-scale derivative dK/dl_k = coef base l_k D_k^2, per stationary kind (base: see kind_eval)
 __device__ __forceinline__ double kind_hcoef(int kind) {
     if (kind == PG_KIND_RBF) return -1.0;
     if (kind == PG_KIND_MATERN52) return 0.5 * -(5.0 / 3.0);
@@ -82,26 +84,47 @@ __device__ __forceinline__ double kind_hcoef(int kind) {
     return -0.5;                               // PG_KIND_MATERN12
 }
 
-// Covariance value kv and the factor `base` of dK/dl_k for a Matern kind from the scaled squared distance (direct differences: the
-// Matern-1/2 factor 1/r is only formed from an exact sq, so it is bounded by |D_k| after the multiplication by l_k D_k^2; 0 at sq = 0,
-// the derivative's limit there).
-template <typename T> __device__ __forceinline__ void matern_val(int kind, T sig2, T sq, T& kv, T& base) {
-    const T rr = sqrt(sq);
-    if (kind == PG_KIND_MATERN12) {
+// THE definition of every kind for the VALU bodies: covariance value kv and the factor `base` of dK/dl_k from the scaled squared
+// distance sq of direct differences (the Matern-1/2 factor 1/r is only formed from an exact sq, so it is bounded by |D_k| after the
+// multiplication by l_k D_k^2; 0 at sq = 0, the derivative's limit there).  The kind is a template parameter: callers dispatch on it
+// OUTSIDE their element loops.  The matrix-pipe bodies have forms of their own (KmVal in kmfma.hip: other primitives, other bits).
+template <typename T, int KIND> __device__ __forceinline__ void kind_eval(T sig2, T sq, T& kv, T& base) {
+    if constexpr (KIND == PG_KIND_RBF) {
+        kv = base = sig2 * pg_exp(-sq);
+    } else if constexpr (KIND == PG_KIND_SQDIST) {       // Squared_exponential.distance (covar.py:102-127): the scaled squared distance itself
+        kv = sq;
+        base = (T)0;
+    } else if constexpr (KIND == PG_KIND_MATERN12) {
+        const T rr = sqrt(sq);
         const T ex = sig2 * pg_exp(-rr);
         kv = ex;
         base = sq == (T)0 ? (T)0 : ex / rr;
-    } else if (kind == PG_KIND_MATERN32) {
+    } else if constexpr (KIND == PG_KIND_MATERN32) {
         const T s3 = (T)1.73205080756887729353;
+        const T rr = sqrt(sq);
         const T ex = pg_exp(-s3 * rr);
         kv = sig2 * ((T)1 + s3 * rr) * ex;
         base = sig2 * ex;
-    } else {                                   // PG_KIND_MATERN52
+    } else {
+        static_assert(KIND == PG_KIND_MATERN52, "unknown kernel kind");
         const T s5 = (T)2.23606797749978969641;
+        const T rr = sqrt(sq);
         const T ex = pg_exp(-s5 * rr);
         kv = sig2 * ((T)1 + s5 * rr + (T)(5.0 / 3.0) * sq) * ex;
         base = sig2 * ((T)1 + s5 * rr) * ex;
     }
+}
+// the value alone (the covariance build): `base` is dead code there
+template <typename T, int KIND> __device__ __forceinline__ T kind_value(T sig2, T sq) {
+    T kv, base;
+    kind_eval<T, KIND>(sig2, sq, kv, base);
+    return kv;
+}
+// kv and base of a Matern kind chosen at run time (the direct-difference gradient kernels)
+template <typename T> __device__ __forceinline__ void matern_val(int kind, T sig2, T sq, T& kv, T& base) {
+    if (kind == PG_KIND_MATERN12) kind_eval<T, PG_KIND_MATERN12>(sig2, sq, kv, base);
+    else if (kind == PG_KIND_MATERN32) kind_eval<T, PG_KIND_MATERN32>(sig2, sq, kv, base);
+    else kind_eval<T, PG_KIND_MATERN52>(sig2, sq, kv, base);
 }
 
 // Strip (tile row tr, first tile tcs, ntile tiles) of workgroup `b` of a 1-D grid: a workgroup walks up to S consecutive tiles of

@@ -15,9 +15,13 @@
 //
 // a = (x - x_0) l: coordinates relative to the first point (stationary kernels do not care; the expansion's absolute error is
 // eps |a|^2, so uncentred data would lose digits) times the inverse length scales.  What stays on the VALU is what is per ELEMENT:
-// the exponential, the weight, the clamp -- about 25 operations, independent of d.  One stationary component (+ white noise), d <= 16,
-// of the kinds with a body here (squared exponential, Matern-5/2, Matern-3/2: all 1 - O(r^2) near r = 0, so the expansion's error in sq
-// enters K linearly); everything else -- Matern-1/2 among it -- keeps the kernels of kbuild.hip.  PG_KB_MFMA=0 / PG_GRAD_MFMA=0 switch back.
+// the exponential, the weight, the clamp -- about 25 operations, independent of d.
+//
+// What runs here (the routing is in pg_kbuild / pg_nlml_grad_t, kbuild.hip): one stationary component (+ white noise), d <= 16, of the
+// kinds with a body here (squared exponential, Matern-5/2, Matern-3/2: all 1 - O(r^2) near r = 0, so the expansion's error in sq enters K
+// linearly).  The contraction takes every such input; the build all but the fp64 squared exponential at d <= 8, which the VALU fast body
+// of kbuild.hip serves (PG_KB_MFMA=2 sends it here too).  Everything else -- Matern-1/2, d > 16, several components, an accumulate pass --
+// keeps the direct-difference kernels of kbuild.hip; PG_KB_MFMA=0 / PG_GRAD_MFMA=0 send every input there (the tests' yardstick).
 #include "kbuild.h"
 #include "kfun.h"
 #include "kmfma.h"
@@ -263,7 +267,7 @@ template int pg_kbuild_mfma<float>(hipStream_t, const pg_covspec&, const double*
 // the sixteen columns of one).  Those two products accumulate in the matrix pipe's registers for the whole walk (their rows are the
 // wave's columns j); they, the column sums of G and the sigma / noise sums are folded once per workgroup into part[blk][nhp]
 // (entries in the `presc` convention of pg_grad_reduce_kernel: sums of (l_k D_k)^2 terms).
-template <typename T, int DP, int KIND, bool GRIDX_COL = true>
+template <typename T, int DP, int KIND>
 __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void pg_grad_mfma_kernel(pg_covspec spec, const double* __restrict__ hp, const T* __restrict__ X, long ldx, int n,
                                                            int d, const T* __restrict__ Kinv, long ldk, const T* __restrict__ alpha,
                                                            double* __restrict__ part, int nhp, GradBatch gb, int gch) {
@@ -275,11 +279,10 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void pg_grad_mfma_kern
     X += blockIdx.z * gb.eX; hp += blockIdx.z * gb.ehp; Kinv += blockIdx.z * gb.eK; alpha += blockIdx.z * gb.ea; part += blockIdx.z * gb.epart;
     // grid.x = tile column (fastest), grid.y = which stretch of `gch` tile rows below its diagonal: the workgroups in flight together
     // walk the SAME stretch of every tile column -- equally long walks, and K^-1 is read in whole row bands instead of sixteen 512-byte
-    // columns of every row at once.  N = 16384, fp64: D = 16 721 -> 437 us, D = 8 491 -> 309 us (PG_GRAD_GRID=0: the transposed mapping of the
-    // first version, tile column on grid.y; fp32 does not care: 1031 us both ways at n = 33792).
-    constexpr bool colfast = GRIDX_COL;
-    const int tc = colfast ? blockIdx.x : blockIdx.y, tiles = colfast ? gridDim.x : gridDim.y;
-    const int chunk = colfast ? blockIdx.y : blockIdx.x, nchunk = colfast ? gridDim.y : gridDim.x;
+    // columns of every row at once.  N = 16384, fp64: D = 16 721 -> 437 us, D = 8 491 -> 309 us against the transposed mapping of the first
+    // version (tile column on grid.y; fp32 did not care: 1031 us both ways at n = 33792).
+    const int tc = blockIdx.x, tiles = gridDim.x;
+    const int chunk = blockIdx.y, nchunk = gridDim.y;
     const int r_begin = tc + chunk * gch, r_end = min(r_begin + gch, tiles);
     const int blk = tc * nchunk + chunk;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c16 = lane & 15;
@@ -287,7 +290,6 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void pg_grad_mfma_kern
     if (r_begin >= tiles) return;
     __shared__ T xc[KT * LDP], ncs[KT], acs[KT], xr[2][KT * LDP], nrs[2][KT], ars[2][KT], cs[4][16];
     __shared__ double tab[32], tab2[32], red[4][18];   // tab2 = 2 tab: the weight 2 of an interior tile rides in the covariance value
-    constexpr bool W2TAB = true;
     const T sig2x2 = (T)(2.0 * hp[spec.off[0]] * hp[spec.off[0]]);
     const int o = spec.off[0];
     const int kk = tid % DP;
@@ -329,15 +331,13 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void pg_grad_mfma_kern
     // kernel is not bound by its loads: tools/probe_tile_bodies.py).  The blocks follow one another sixteen rows
     // apart through the whole walk: one running pointer per accumulator register, advanced by 16 ldk per block (a 64-bit multiply per
     // load before); only a block that reaches past the last real row takes the clamped form.
-    constexpr bool DEEP = false;
-    constexpr int NQ = DEEP ? 4 : 1;
     const T* kp[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) kp[r] = Kinv + (long)(r_begin * KT + Mfma<T>::row(lane, r)) * ldk + jcol;
     const long kstep = 16 * ldk;
     int krow = r_begin * KT;          // first row of the block the pointers stand on
     const int krow_end = r_end * KT;
-    T kq[NQ][4];                      // [block in flight][register]
+    T kq[4];                          // the block in flight
     auto kfetch = [&](T (&dst)[4]) {  // the block at krow -> dst, pointers on to the next one
         if (krow + 16 <= n) {
 #pragma unroll
@@ -350,8 +350,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void pg_grad_mfma_kern
         for (int r = 0; r < 4; ++r) kp[r] += kstep;
         krow += 16;
     };
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) kfetch(kq[q]);
+    kfetch(kq);
     for (int tr = r_begin, it = 0; tr < r_end; ++tr, ++it) {
         const int cur = it & 1;
         const bool more = tr + 1 < r_end;
@@ -375,8 +374,8 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void pg_grad_mfma_kern
                 const int i0 = 16 * rb;
                 T kin[4];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) kin[r] = kq[DEEP ? rb : 0][r];
-                if (krow < krow_end) kfetch(kq[DEEP ? rb : 0]);
+                for (int r = 0; r < 4; ++r) kin[r] = kq[r];
+                if (krow < krow_end) kfetch(kq);
                 T af[NS], nri[4], ai[4];
 #pragma unroll
                 for (int s = 0; s < NS; ++s) af[s] = xb[(i0 + c16) * LDP + 4 * s + g];
@@ -437,8 +436,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void pg_grad_mfma_kern
                     // (a squared exponential takes the expansion's rounding below zero as it is: exp(1e-16) = 1; a root does not)
                     if (!INTERIOR || KIND != PG_KIND_RBF) sq = sq < (T)0 ? (T)0 : sq;
                     T w = kin[r] - ai[r] * aj;
-                    if (INTERIOR) { if (!W2TAB) w *= (T)2; }
-                    else {
+                    if (!INTERIOR) {        // (interior: the weight 2 rides in tab2 / sig2x2)
                         const int gi = tr * KT + i0 + Mfma<T>::row(lane, r);
                         if (gi == gj && sq == sq) sq = (T)0;
                         if (gi >= n || gj > gi) w = (T)0;
@@ -446,7 +444,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void pg_grad_mfma_kern
                         else trw += (double)w;
                     }
                     T kv, base;
-                    KmVal<T, KIND>::run(sq, (INTERIOR && W2TAB) ? sig2x2 : sig2, (INTERIOR && W2TAB) ? tab2 : tab, kv, base);
+                    KmVal<T, KIND>::run(sq, INTERIOR ? sig2x2 : sig2, INTERIOR ? tab2 : tab, kv, base);
                     accs_t += w * kv;
                     gr_[r] = w * base;
                     pgs += gr_[r];
@@ -519,13 +517,8 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void pg_grad_mfma_kern
 template <typename T, int DP, int KIND>
 static int grad_mfma_launch(hipStream_t st, const pg_covspec& spec, const double* hp, const T* X, long ldx, int n, int d, const T* Kinv, long ldk,
                             const T* alpha, double* part, int nhp, int tiles, const GradBatch& gb, int nexp, int gch) {
-    const int gridmode = getenv("PG_GRAD_GRID") ? atoi(getenv("PG_GRAD_GRID")) : 1;
-    if (gridmode)
-        hipLaunchKernelGGL((pg_grad_mfma_kernel<T, DP, KIND, true>), dim3(tiles, (tiles + gch - 1) / gch, nexp), dim3(256), 0, st, spec, hp, X, ldx, n,
-                           d, Kinv, ldk, alpha, part, nhp, gb, gch);
-    else
-        hipLaunchKernelGGL((pg_grad_mfma_kernel<T, DP, KIND, false>), dim3((tiles + gch - 1) / gch, tiles, nexp), dim3(256), 0, st, spec, hp, X, ldx, n,
-                           d, Kinv, ldk, alpha, part, nhp, gb, gch);
+    hipLaunchKernelGGL((pg_grad_mfma_kernel<T, DP, KIND>), dim3(tiles, (tiles + gch - 1) / gch, nexp), dim3(256), 0, st, spec, hp, X, ldx, n, d,
+                       Kinv, ldk, alpha, part, nhp, gb, gch);
     PG_CHECK(hipGetLastError());
     return 0;
 }

@@ -1,6 +1,6 @@
 """Derivatives in the test points (pg_kernel_xgrad, Exact_GP.predict_grad), fp64 d = 8, squared exponential and Matern-5/2:
   * the contraction alone with both weight forms (u and B) at m = n = 16384 and at m = 128, n = 16384 (the column split);
-  * the comparison point: the VALU gradient contraction pg_nlml_grad at N = 16384 (PG_GRAD_MFMA=0 PG_GRAD_FAST=0: n^2 / 2 pairs);
+  * the comparison point: the VALU gradient contraction pg_nlml_grad at N = 16384 (PG_GRAD_MFMA=0: n^2 / 2 pairs);
   * predict_grad(var="diag") against predict(var="diag") at n = 16384, m = 4096.
 One child process per (kind, case), each under its own time limit; the first child that fails or runs out of time ends the probe.
 Times are medians of 10 after 2 warm-ups (us); `ps/pair` divides by the pairs each call covers.
@@ -92,7 +92,7 @@ def main():
         for case in CASES:
             env = dict(os.environ)
             if case == "nlml_grad_valu":
-                env.update(PG_GRAD_MFMA="0", PG_GRAD_FAST="0")
+                env.update(PG_GRAD_MFMA="0")
             try:
                 r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", case, str(kind)], capture_output=True, text=True,
                                    timeout=limit, env=env)
