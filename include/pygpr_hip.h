@@ -44,6 +44,9 @@ extern "C" {
                               Squared_exponential.distance (covar.py:102-127) when l = 1 */
 #define PG_KIND_MATERN32 3 /* new (not in the reference), same hp layout: sigma^2 (1 + sqrt3 r) exp(-sqrt3 r) */
 #define PG_KIND_MATERN12 4 /* new (not in the reference), same hp layout: sigma^2 exp(-r) (exponential / Ornstein-Uhlenbeck) */
+/* 5 is unassigned and stays an unknown kind */
+#define PG_KIND_RQ (6)     /* new (not in the reference): rational quadratic, hp = [sigma, l_1..l_d, alpha] (d + 2 values):
+                              sigma^2 (1 + sq / alpha^2)^(-alpha^2), sq the scaled squared distance of the squared exponential */
 #define PG_MAX_COMP 4
 #define PG_MAX_DIM 64
 
@@ -55,7 +58,8 @@ typedef struct pg_ctx* pg_handle;
 typedef struct pg_covspec {
     int ncomp;                  /* stationary components                                     */
     int kind[PG_MAX_COMP];      /* PG_KIND_*                                                 */
-    int off[PG_MAX_COMP];       /* index of [sigma, l_1..l_d] of component c inside hp       */
+    int off[PG_MAX_COMP];       /* index of component c's sigma inside hp: [sigma, l_1..l_d], */
+                                /* and for PG_KIND_RQ its shape alpha at off[c] + d + 1       */
     int nnoise;                 /* White_noise children (covar.py:209-269)                   */
     int noise_off[PG_MAX_COMP]; /* index of each sigma_n inside hp                           */
 } pg_covspec;

@@ -9,6 +9,8 @@ Same names, hyper-parameter layout and shapes as the reference:
                            (covar.py:28-81)
   * `Matern52`             NEW (no reference counterpart), same hp layout as the SE.
   * `Matern32`, `Matern12` NEW, the rest of the Matern family (nu = 3/2 and 1/2, the exponential kernel), same hp layout.
+  * `Rational_quadratic`   NEW, hp = [sigma, l_1..l_d, alpha] (d + 2 values): sigma^2 (1 + sq / alpha^2)^(-alpha^2) with the SE's
+                           scaled squared distance sq; the squared exponential as alpha grows.
 Leading batch dims on hp and/or x follow the reference's flatten-to-one-batch-dim rule.  Tensors come
 back on the device of `x` (CPU in -> CPU out); the arithmetic always runs on the GPU in the dtype of
 `x` (float64, or float32 as an explicit opt-in) -- unlike the reference, nothing here touches torch's
@@ -196,6 +198,29 @@ class Matern12(Squared_exponential):
     K = sig^2 exp(-r).  dK/dl_k = -sig^2 exp(-r) l_k (x_k-x'_k)^2 / r, 0 at r = 0 (its limit)."""
 
     _kind = _lib.PG_KIND_MATERN12
+
+
+class Rational_quadratic(Squared_exponential):
+    """ARD rational quadratic, hp = [sigma, l_1..l_d, alpha]: d + 2 values, the shape alpha behind the SE's block.  The conventions are
+    the SE's: l are INVERSE length scales, no 1/2 in the distance, and every parameter enters SQUARED, the shape included, so that an
+    unconstrained optimiser cannot leave the domain.  With D_k = x_k - x'_k:
+
+        sq = sum_k l_k^2 D_k^2,   a = alpha^2,   t = sq / a
+        K         = sigma^2 (1 + t)^(-a) = sigma^2 exp(-a log1p(t))
+        dK/dsigma = 2 K / sigma
+        dK/dl_k   = -2 [K / (1 + t)] l_k D_k^2
+        dK/dalpha = 2 alpha K [t / (1 + t) - log1p(t)]        (0 at sq = 0)
+        dK/dx*_k  = -2 [K / (1 + t)] l_k^2 D_k
+
+    A scale mixture of squared exponentials: K tends to this library's SE, sigma^2 exp(-sq), from above as a grows,
+    0 <= K - K_SE <= K_SE (exp(sq^2 / (2 a)) - 1).  alpha = 0 gives NaN (0 * inf) and is not worked around."""
+
+    _kind = _lib.PG_KIND_RQ
+
+    def _collect(self, d, base, kinds, offs, noise):
+        kinds.append(self._kind)
+        offs.append(base)
+        return d + 2
 
 
 class White_noise(_DeviceKernel):

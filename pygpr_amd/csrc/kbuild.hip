@@ -2,9 +2,9 @@
 //
 // pg_kbuild: K[i][j] = sum_c k_c(r_i, c_j) (+ (sum sigma_n^2 + jitter) on the diagonal of a symmetric build); k_c is the ARD squared
 // exponential of PyGPR/covar.py:129-167 (hp = [sigma, l_1..l_d], l are INVERSE length scales, no 1/2 in the exponent) or Matern-5/2,
-// -3/2, -1/2 with the same hp layout.  Rows/columns >= the real point count are padding: identity for a symmetric build (keeps the
+// -3/2, -1/2 with the same hp layout, or the rational quadratic with its shape alpha behind that block (kind_nparam, kfun.h).  Rows/columns >= the real point count are padding: identity for a symmetric build (keeps the
 // padded Cholesky trivial), zero for a cross build.  Which body serves which input:
-//   * one child of kind SE / Matern-5/2 / Matern-3/2, d <= 16, no accumulate pass: the matrix-pipe kernel of kmfma.hip -- except the
+//   * one child of kind SE / Matern-5/2 / Matern-3/2 / rational quadratic, d <= 16, no accumulate pass: the matrix-pipe kernel of kmfma.hip -- except the
 //     fp64 squared exponential at d <= 8, which the FAST body here serves at 0.63-0.66 of the HBM peak;
 //   * one fp64 SE child, no accumulate pass, d <= 8 or d > 16: kb_body<FAST>, the expansion |x|^2 + |x'|^2 - 2 x.x' on the VALU;
 //   * any other single child (Matern-1/2, d > 16, an accumulate pass): kb_body<PRESC>, direct differences of coordinates
@@ -16,7 +16,8 @@
 // pg_nlml_grad: g_k = 1/2 sum_ij (K^-1 - a a^T)_ij dK_ij/dtheta_k over the lower triangle, with dK recomputed from the point tiles
 // on the fly: dK/dsigma = 2K/sigma, dK/dl_k = -2 l_k D_k^2 K (covar.py:169-206), dK/dsigma_n = 2 sigma_n I (covar.py:247-269); the
 // Matern kinds as dK/dl_k = coef base l_k D_k^2 (kind_hcoef: coef / 2).  The reference materialises dK[nhp,n,n] and solves against
-// it (loss.py:116-121); this is the same number by the K^-1 route.  One child of kind SE / Matern-5/2 / Matern-3/2 at d <= 16 takes
+// it (loss.py:116-121); this is the same number by the K^-1 route.  The rational quadratic adds dK/dalpha = 2 alpha fs (rq_terms).  One
+// child of kind SE / Matern-5/2 / Matern-3/2 / rational quadratic at d <= 16 takes
 // the matrix-pipe contraction of kmfma.hip; everything else (Matern-1/2, d > 16, several children, PG_GRAD_MFMA=0) takes
 // pg_grad_kernel here: direct differences on the VALU.
 #include "kbuild.h"
@@ -122,13 +123,15 @@ __device__ __forceinline__ void kb_body(const pg_covspec& spec, const T* xr, con
             // behind its own branch and the sixteen exponentials ran one after the other, each a chain of dependent operations
             const int kind = spec.kind[cp];
             const T s2 = sg2[cp];
+            const T sh = sg2[PG_MAX_COMP + 2 + cp], ish = sg2[2 * PG_MAX_COMP + 2 + cp];      // rational quadratic: alpha^2, 1 / alpha^2
             auto add = [&](auto kind_c) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) out[r][c] += kind_value<T, decltype(kind_c)::value>(s2, sq[r][c]);
+                    for (int c = 0; c < 4; ++c) out[r][c] += kind_value<T, decltype(kind_c)::value>(s2, sq[r][c], sh, ish);
             };
-            if (kind == PG_KIND_RBF) add(std::integral_constant<int, PG_KIND_RBF>{});
+            if (kind == PG_KIND_RQ) add(std::integral_constant<int, PG_KIND_RQ>{});
+            else if (kind == PG_KIND_RBF) add(std::integral_constant<int, PG_KIND_RBF>{});
             else if (kind == PG_KIND_SQDIST) add(std::integral_constant<int, PG_KIND_SQDIST>{});
             else if (kind == PG_KIND_MATERN52) add(std::integral_constant<int, PG_KIND_MATERN52>{});
             else if (kind == PG_KIND_MATERN32) add(std::integral_constant<int, PG_KIND_MATERN32>{});
@@ -199,8 +202,8 @@ __global__ __launch_bounds__(256) void pg_kbuild_kernel(pg_covspec spec, const d
     T* xr = reinterpret_cast<T*>(smem_raw);
     T* xc = xr + KT * d;            // two buffers [d][64]
     T* l2 = xc + 2 * KT * d;        // [ncomp][d] squared inverse length scales
-    T* sg2 = l2 + PG_MAX_COMP * d;  // [PG_MAX_COMP] sigma^2, then the diagonal term
-    T* tt = sg2 + PG_MAX_COMP + 2;  // MIRROR: [64][TLD] transposed tile
+    T* sg2 = l2 + PG_MAX_COMP * d;  // [PG_MAX_COMP] sigma^2, the diagonal term (+ 1 spare), [PG_MAX_COMP] shapes alpha^2 and their reciprocals
+    T* tt = sg2 + 3 * PG_MAX_COMP + 2;  // MIRROR: [64][TLD] transposed tile
     T* nrm = tt + (MIRROR ? KT * TLD : 0);                      // fast path: -|x|^2 of the row points [64], of the column points [2][64]
     double* tab = reinterpret_cast<double*>(nrm + 3 * KT);      // fast path: sigma^2 2^(j/32) [32] (fp64 builds only)
     constexpr bool fast = FASTK;                                // host: one squared-exponential component, fp64, no accumulate pass (presc = 2)
@@ -244,6 +247,11 @@ __global__ __launch_bounds__(256) void pg_kbuild_kernel(pg_covspec spec, const d
     if (tid < spec.ncomp) {
         const double sg = hp[spec.off[tid]];
         sg2[tid] = (T)(sg * sg);
+    }
+    if (tid >= 128 && tid < 128 + spec.ncomp) {
+        const double a = kind_shape2(spec, hp, tid - 128, d);
+        sg2[PG_MAX_COMP + 2 + tid - 128] = (T)a;
+        sg2[2 * PG_MAX_COMP + 2 + tid - 128] = (T)(1.0 / a);      // (unused unless the kind has a shape)
     }
     if (tid == 64) {
         double dg = jitter;
@@ -310,7 +318,7 @@ __global__ __launch_bounds__(256) void pg_kbuild_pad_kernel(T* __restrict__ K, l
 
 // LDS of pg_kbuild_kernel in bytes at dimension d (the fast body's norms and table are always counted)
 template <typename T> static constexpr size_t kb_lds_bytes(int d, bool mirror) {
-    return (size_t)(3 * KT * d + PG_MAX_COMP * d + PG_MAX_COMP + 2 + (mirror ? KT * TLD : 0) + 3 * KT) * sizeof(T) + 32 * sizeof(double);
+    return (size_t)(3 * KT * d + PG_MAX_COMP * d + 3 * PG_MAX_COMP + 2 + (mirror ? KT * TLD : 0) + 3 * KT) * sizeof(T) + 32 * sizeof(double);
 }
 
 // One instantiation of pg_kbuild_kernel: its dynamic-LDS limit once, then the launch.
@@ -378,7 +386,7 @@ int pg_kbuild(hipStream_t st, const pg_covspec& spec, const double* hp, const T*
     // (mirrored, lower-only and cross builds of one (kind, dtype, d) all take the same body: their values agree bit for bit)
     // (Matern-1/2 never: it is 1 - r near 0, so the expansion's error in sq reaches K as its square root -- DESIGN.md)
     if (mfma_env && spec.ncomp == 1 && !accumulate && d <= 16 &&
-        (spec.kind[0] == PG_KIND_RBF || spec.kind[0] == PG_KIND_MATERN52 || spec.kind[0] == PG_KIND_MATERN32) &&
+        (spec.kind[0] == PG_KIND_RBF || spec.kind[0] == PG_KIND_MATERN52 || spec.kind[0] == PG_KIND_MATERN32 || spec.kind[0] == PG_KIND_RQ) &&
         (mfma_env >= 2 || presc != 2 || d > 8))
         return pg_kbuild_mfma<T>(st, spec, hp, Xr, ldr, nr, Xc, ldc, nc, d, symmetric, mirror ? 1 : 0, jitter, K, ldk, c0, c1, S, strips, nexp, eX,
                                  ehp, eK, eXr);
@@ -428,9 +436,13 @@ __global__ __launch_bounds__(256) void pg_kgrad_kernel(pg_covspec spec, const do
             const T df = xi[k] - xj[k];
             sq += (T)(l * l) * df * df;
         }
-        T kv, base;
+        T kv, base, fs;
         if (spec.kind[cp] == PG_KIND_RBF) kind_eval<T, PG_KIND_RBF>((T)(sg * sg), sq, kv, base);
-        else matern_val<T>(spec.kind[cp], (T)(sg * sg), sq, kv, base);
+        else {
+            const double a = kind_shape2(spec, hp, cp, d);
+            matern_val<T>(spec.kind[cp], (T)(sg * sg), sq, kv, base, (T)a, (T)(1.0 / a), fs);
+            if (spec.kind[cp] == PG_KIND_RQ) dK[(long)(o + d + 1) * slab + e] = (T)(2.0 * hp[o + d + 1]) * fs;      // the shape slab
+        }
         const T coef = (T)(2.0 * kind_hcoef(spec.kind[cp]));
         dK[(long)o * slab + e] = kv * (T)(2.0 / sg);
         for (int k = 0; k < d; ++k) {
@@ -525,7 +537,7 @@ __global__ __launch_bounds__(256) void pg_grad_kernel(pg_covspec spec, const dou
         return;
     }
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    double* red = reinterpret_cast<double*>(smem_raw);             // [4 waves][DMAX + 2]
+    double* red = reinterpret_cast<double*>(smem_raw);             // [4 waves][DMAX + 2]: sigma, l_1..l_DMAX, the shape
     T* xr = reinterpret_cast<T*>(red + 4 * (DMAX + 2));             // [DMAX][64], zero for k >= d
     T* xc = xr + KT * DMAX;                                         // two buffers [DMAX][64]
     T* l2 = xc + 2 * KT * DMAX;                                     // [ncomp][DMAX], zero for k >= d
@@ -552,6 +564,9 @@ __global__ __launch_bounds__(256) void pg_grad_kernel(pg_covspec spec, const dou
         const T sig2 = (T)(sg * sg);
         const T* lc = l2 + cp * DMAX;
         const int kind = have ? spec.kind[cp] : PG_KIND_RBF;
+        const double sh = have ? kind_shape2(spec, hp, cp, d) : 0.0;
+        const T sha = (T)sh, ish = (T)(1.0 / sh);      // rational quadratic: alpha^2, 1 / alpha^2
+        double accf = 0.0;                            // ... and its shape entry, sum W K fs
         double acc[DMAX + 1];
 #pragma unroll
         for (int k = 0; k <= DMAX; ++k) acc[k] = 0.0;
@@ -586,10 +601,11 @@ __global__ __launch_bounds__(256) void pg_grad_kernel(pg_covspec spec, const dou
                     kv = (double)kind_value<T, PG_KIND_RBF>(sig2, sq);
                     base = kv;
                 } else {
-                    T kt, bt;
-                    matern_val<T>(kind, sig2, sq, kt, bt);
+                    T kt, bt, ft;
+                    matern_val<T>(kind, sig2, sq, kt, bt, sha, ish, ft);
                     kv = (double)kt;
                     base = (double)bt;
+                    accf += w * (double)ft;
                 }
                 acc[0] += w * kv;
                 const double wb = w * base;
@@ -606,10 +622,15 @@ __global__ __launch_bounds__(256) void pg_grad_kernel(pg_covspec spec, const dou
                 const double s = wave_sum(acc[k]);
                 if (lane == 0) red[wave * (DMAX + 2) + k] = s;
             }
+            if (kind == PG_KIND_RQ) {
+                const double s = wave_sum(accf);
+                if (lane == 0) red[wave * (DMAX + 2) + DMAX + 1] = s;
+            }
             __syncthreads();
-            if (tid <= d)
-                part[(long)blk * nhp + o + tid] =
-                    red[tid] + red[(DMAX + 2) + tid] + red[2 * (DMAX + 2) + tid] + red[3 * (DMAX + 2) + tid];
+            if (tid < kind_nparam(kind, d)) {      // the child's block: sigma, l_1..l_d (slots 0..d), the shape (slot DMAX + 1)
+                const int q = tid <= d ? tid : DMAX + 1;
+                part[(long)blk * nhp + o + tid] = red[q] + red[(DMAX + 2) + q] + red[2 * (DMAX + 2) + q] + red[3 * (DMAX + 2) + q];
+            }
             __syncthreads();
         }
     }
@@ -648,6 +669,9 @@ __global__ __launch_bounds__(256) void pg_grad_reduce_kernel(pg_covspec spec, co
                 scale = hc * hp[p];
                 // the matrix-pipe contraction summed (l_k D_k)^2: -l_k S = -S' / l_k (l_k = 0: S' = 0 and the derivative is 0)
                 if (presc) scale = hp[p] != 0.0 ? hc / hp[p] : 0.0;
+                mine = true;
+            } else if (spec.kind[c] == PG_KIND_RQ && p == o + d + 1) {
+                scale = 0.5 * 2.0 * hp[p];      // dK/dalpha = 2 alpha K fs (the partial sums hold sum W K fs)
                 mine = true;
             }
         }
@@ -688,7 +712,7 @@ int pg_nlml_grad_t(hipStream_t st, const pg_covspec& spec, const double* hp, con
     const int mfma_env = getenv("PG_GRAD_MFMA") ? atoi(getenv("PG_GRAD_MFMA")) : 1;   // (read per call: tests compare the bodies in one process)
     // (not Matern-1/2: its factor e^-r / r is unbounded near r = 0, and the expansion's cancellation error is u |x|^2 sum |G| -- DESIGN.md)
     if (mfma_env && spec.ncomp == 1 && d <= 16 && n >= 1 &&
-        (spec.kind[0] == PG_KIND_RBF || spec.kind[0] == PG_KIND_MATERN52 || spec.kind[0] == PG_KIND_MATERN32)) {
+        (spec.kind[0] == PG_KIND_RBF || spec.kind[0] == PG_KIND_MATERN52 || spec.kind[0] == PG_KIND_MATERN32 || spec.kind[0] == PG_KIND_RQ)) {
         int nblk = 0;
         if ((rc = pg_grad_mfma<T>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp, &nblk))) return rc;
         hipLaunchKernelGGL(pg_grad_reduce_kernel, dim3(nhp, 1, nexp), dim3(256), 0, st, spec, hp, work, nblk, nhp, d, grad, 1, gb);

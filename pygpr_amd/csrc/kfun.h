@@ -78,19 +78,66 @@ __device__ __forceinline__ double pg_sqrt_pos(double x) {
 
 // Half the factor `coef` of the length-scale derivative dK/dl_k = coef base l_k D_k^2, per stationary kind (base: see kind_eval)
 __device__ __forceinline__ double kind_hcoef(int kind) {
-    if (kind == PG_KIND_RBF) return -1.0;
+    if (kind == PG_KIND_RBF || kind == PG_KIND_RQ) return -1.0;
     if (kind == PG_KIND_MATERN52) return 0.5 * -(5.0 / 3.0);
     if (kind == PG_KIND_MATERN32) return -1.5;
     return -0.5;                               // PG_KIND_MATERN12
 }
 
+// Hyper-parameters of one stationary child of this kind at dimension d: [sigma, l_1..l_d], and for the rational quadratic its shape
+// alpha behind them (at off + d + 1).  Everything that walks a child's block asks here instead of assuming d + 1.
+__host__ __device__ __forceinline__ int kind_nparam(int kind, int d) { return kind == PG_KIND_RQ ? d + 2 : d + 1; }
+// The squared shape a = alpha^2 of component c (0 for the kinds without one: their blocks end at l_d and hp[off + d + 1] is not theirs)
+__device__ __forceinline__ double kind_shape2(const pg_covspec& spec, const double* hp, int c, int d) {
+    if (spec.kind[c] != PG_KIND_RQ) return 0.0;
+    const double al = hp[spec.off[c] + d + 1];
+    return al * al;
+}
+
+// 1 / u for u >= 1 (a NaN stays a NaN): v_rcp_f64 and two Newton steps, <= 1 ulp -- five fp64 operations where the IEEE division
+// with its scaling is about fifteen.
+__device__ __forceinline__ double pg_rcp_ge1(double u) {
+    double y = __builtin_amdgcn_rcp(u);
+    y = __builtin_fma(y, __builtin_fma(-u, y, 1.0), y);
+    y = __builtin_fma(y, __builtin_fma(-u, y, 1.0), y);
+    return y;
+}
+__device__ __forceinline__ float pg_rcp_ge1(float u) { return 1.0f / u; }
+
+// Rational quadratic from the scaled squared distance sq, the squared shape a = alpha^2 and ia = 1 / a:  t = sq / a,
+//   lg = log1p(t),  ex = exp(-a lg) = (1 + t)^-a  (no sigma^2: the caller's exponential may carry it),  iu = 1 / (1 + t),
+//   fs = t / (1 + t) - log1p(t)  the factor of the shape derivative, dK/dalpha = 2 alpha K fs (0 at sq = 0, -t^2 / 2 + O(t^3) near it).
+// The logarithm is the device library's log1p: exact to an ulp for the small t of a large shape, where K tends to the squared
+// exponential and log(1 + t) would lose every digit of t.  t beyond 1e300 (points an overflow apart) is taken as 1e300: K is 0 there
+// either way, and 1 / (1 + inf) would turn `base` into a NaN.  Select, not fmin: a NaN coordinate or hyper-parameter stays NaN.
+// alpha = 0 gives NaN (0 * inf) and is not worked around.
+template <typename T> struct RqTerms { T arg, iu, fs; };      // arg = -a lg: the exponential's argument
+template <typename T> __device__ __forceinline__ RqTerms<T> rq_terms(T sq, T a, T ia) {
+    T t = sq * ia;
+    const T big = sizeof(T) == 8 ? (T)1.0e300 : (T)1.0e30f;
+    t = (t > big) ? big : t;
+    const T lg = log1p(t);
+    RqTerms<T> r;
+    r.arg = -a * lg;
+    r.iu = pg_rcp_ge1((T)1 + t);
+    r.fs = t * r.iu - lg;
+    return r;
+}
+
 // THE definition of every kind for the VALU bodies: covariance value kv and the factor `base` of dK/dl_k from the scaled squared
 // distance sq of direct differences (the Matern-1/2 factor 1/r is only formed from an exact sq, so it is bounded by |D_k| after the
-// multiplication by l_k D_k^2; 0 at sq = 0, the derivative's limit there).  The kind is a template parameter: callers dispatch on it
+// multiplication by l_k D_k^2; 0 at sq = 0, the derivative's limit there).  The rational quadratic also takes its squared shape a and
+// 1 / a, and gives fs, its shape derivative over 2 alpha: dK/dalpha = 2 alpha fs.  The kind is a template parameter: callers dispatch on it
 // OUTSIDE their element loops.  The matrix-pipe bodies have forms of their own (KmVal in kmfma.hip: other primitives, other bits).
-template <typename T, int KIND> __device__ __forceinline__ void kind_eval(T sig2, T sq, T& kv, T& base) {
+template <typename T, int KIND> __device__ __forceinline__ void kind_eval(T sig2, T sq, T& kv, T& base, T a, T ia, T& fs) {
+    fs = (T)0;
     if constexpr (KIND == PG_KIND_RBF) {
         kv = base = sig2 * pg_exp(-sq);
+    } else if constexpr (KIND == PG_KIND_RQ) {
+        const RqTerms<T> q = rq_terms<T>(sq, a, ia);
+        kv = sig2 * pg_exp(q.arg);
+        base = kv * q.iu;
+        fs = kv * q.fs;
     } else if constexpr (KIND == PG_KIND_SQDIST) {       // Squared_exponential.distance (covar.py:102-127): the scaled squared distance itself
         kv = sq;
         base = (T)0;
@@ -114,15 +161,23 @@ template <typename T, int KIND> __device__ __forceinline__ void kind_eval(T sig2
         base = sig2 * ((T)1 + s5 * rr) * ex;
     }
 }
+template <typename T, int KIND> __device__ __forceinline__ void kind_eval(T sig2, T sq, T& kv, T& base) {
+    static_assert(KIND != PG_KIND_RQ, "the rational quadratic needs its shape");
+    T fs;
+    kind_eval<T, KIND>(sig2, sq, kv, base, (T)0, (T)0, fs);
+}
 // the value alone (the covariance build): `base` is dead code there
-template <typename T, int KIND> __device__ __forceinline__ T kind_value(T sig2, T sq) {
-    T kv, base;
-    kind_eval<T, KIND>(sig2, sq, kv, base);
+template <typename T, int KIND> __device__ __forceinline__ T kind_value(T sig2, T sq, T a = (T)0, T ia = (T)0) {
+    T kv, base, fs;
+    kind_eval<T, KIND>(sig2, sq, kv, base, a, ia, fs);
     return kv;
 }
-// kv and base of a Matern kind chosen at run time (the direct-difference gradient kernels)
-template <typename T> __device__ __forceinline__ void matern_val(int kind, T sig2, T sq, T& kv, T& base) {
-    if (kind == PG_KIND_MATERN12) kind_eval<T, PG_KIND_MATERN12>(sig2, sq, kv, base);
+// kv and base (and the rational quadratic's fs; 0 otherwise) of a kind other than the squared exponential, chosen at run time (the
+// direct-difference gradient kernels)
+template <typename T> __device__ __forceinline__ void matern_val(int kind, T sig2, T sq, T& kv, T& base, T a, T ia, T& fs) {
+    fs = (T)0;
+    if (kind == PG_KIND_RQ) kind_eval<T, PG_KIND_RQ>(sig2, sq, kv, base, a, ia, fs);
+    else if (kind == PG_KIND_MATERN12) kind_eval<T, PG_KIND_MATERN12>(sig2, sq, kv, base);
     else if (kind == PG_KIND_MATERN32) kind_eval<T, PG_KIND_MATERN32>(sig2, sq, kv, base);
     else kind_eval<T, PG_KIND_MATERN52>(sig2, sq, kv, base);
 }

@@ -18,7 +18,7 @@
 // the exponential, the weight, the clamp -- about 25 operations, independent of d.
 //
 // What runs here (the routing is in pg_kbuild / pg_nlml_grad_t, kbuild.hip): one stationary component (+ white noise), d <= 16, of the
-// kinds with a body here (squared exponential, Matern-5/2, Matern-3/2: all 1 - O(r^2) near r = 0, so the expansion's error in sq enters K
+// kinds with a body here (squared exponential, Matern-5/2, Matern-3/2, rational quadratic: all 1 - O(r^2) near r = 0, so the expansion's error in sq enters K
 // linearly).  The contraction takes every such input; the build all but the fp64 squared exponential at d <= 8, which the VALU fast body
 // of kbuild.hip serves (PG_KB_MFMA=2 sends it here too).  Everything else -- Matern-1/2, d > 16, several components, an accumulate pass --
 // keeps the direct-difference kernels of kbuild.hip; PG_KB_MFMA=0 / PG_GRAD_MFMA=0 send every input there (the tests' yardstick).
@@ -114,9 +114,35 @@ template <> struct KmVal<float, PG_KIND_MATERN32> {
         kv = s3 * r * e + e;
     }
 };
-template <int KIND> struct KmHasBody {
-    static constexpr bool value = KIND == PG_KIND_RBF || KIND == PG_KIND_MATERN52 || KIND == PG_KIND_MATERN32;
+// Rational quadratic: K = sigma^2 (1 + t)^-a, t = sq / a, base = K / (1 + t) (coef -2); |dK/dsq| <= sigma^2, so the expansion's error in sq
+// enters K linearly, as for the kinds above.  Its run() takes the squared shape a, 1 / a and also gives fs = K (t / (1 + t) - log1p(t)),
+// the shape derivative over 2 alpha (rq_terms, kfun.h; fp32 too: v_log_f32 of 1 + t would lose t at a large shape).
+template <> struct KmVal<double, PG_KIND_RQ> {
+    static __device__ __forceinline__ void run(double sq, double sig2, const double* tab, double a, double ia, double& kv, double& base, double& fs) {
+        (void)sig2;
+        const RqTerms<double> q = rq_terms<double>(sq, a, ia);
+        kv = pg_exp_tab(q.arg, tab);
+        base = kv * q.iu;
+        fs = kv * q.fs;
+    }
 };
+template <> struct KmVal<float, PG_KIND_RQ> {
+    static __device__ __forceinline__ void run(float sq, float sig2, const double*, float a, float ia, float& kv, float& base, float& fs) {
+        const RqTerms<float> q = rq_terms<float>(sq, a, ia);
+        kv = sig2 * km_expf(q.arg);
+        base = kv * q.iu;
+        fs = kv * q.fs;
+    }
+};
+template <int KIND> struct KmHasBody {
+    static constexpr bool value = KIND == PG_KIND_RBF || KIND == PG_KIND_MATERN52 || KIND == PG_KIND_MATERN32 || KIND == PG_KIND_RQ;
+};
+// one call for every kind: a, ia and fs are the rational quadratic's alone (fs = 0 otherwise)
+template <typename T, int KIND>
+__device__ __forceinline__ void km_val(T sq, T sig2, const double* tab, T a, T ia, T& kv, T& base, T& fs) {
+    if constexpr (KIND == PG_KIND_RQ) KmVal<T, KIND>::run(sq, sig2, tab, a, ia, kv, base, fs);
+    else { fs = (T)0; KmVal<T, KIND>::run(sq, sig2, tab, kv, base); }
+}
 
 // ------------------------------------------------------------------------------------------------
 // covariance build: symmetric lower-only builds and cross builds of ONE stationary component (+ white noise on the diagonal)
@@ -155,6 +181,8 @@ __global__ __launch_bounds__(256) void pg_kbuild_mfma_kernel(pg_covspec spec, co
     double dgd = jitter;
     for (int i = 0; i < spec.nnoise; ++i) { const double s = hp[spec.noise_off[i]]; dgd += s * s; }
     const T dg = (T)dgd;
+    const double shd = kind_shape2(spec, hp, 0, d);
+    const T sha = (T)shd, ish = (T)(1.0 / shd);      // rational quadratic: alpha^2, 1 / alpha^2
     if (sizeof(T) == 8 && tid < 32) tab[tid] = sg * sg * pg_exp2_32[tid];
     pr.store(xr, sc, x0k, tid);
     pc.store(xc[0], sc, x0k, tid);
@@ -193,8 +221,8 @@ __global__ __launch_bounds__(256) void pg_kbuild_mfma_kernel(pg_covspec spec, co
                 T sq = (T)-2 * acc[r];
                 sq = sq < (T)0 ? (T)0 : sq;                                      // rounding of the expansion; a NaN stays a NaN
                 if (!interior && symmetric && gi == gj && sq == sq) sq = (T)0;   // a point against itself: exactly sigma^2
-                T kv, base;
-                KmVal<T, KIND>::run(sq, sig2, tab, kv, base);
+                T kv, base, fs;
+                km_val<T, KIND>(sq, sig2, tab, sha, ish, kv, base, fs);
                 if (!interior) {
                     if (gi >= nr || gj >= nc) kv = (symmetric && gi == gj) ? (T)1 : (T)0;     // padding: identity / zeros
                     else if (symmetric && gi == gj) kv += dg;
@@ -234,7 +262,7 @@ int pg_kbuild_mfma(hipStream_t st, const pg_covspec& spec, const double* hp, con
                    int symmetric, int mirror, double jitter, T* K, long ldk, int c0, int c1, int S, long strips, int nexp, long eX, long ehp,
                    long eK, long eXr) {
     const int kind = spec.kind[0];
-    if (kind != PG_KIND_RBF && kind != PG_KIND_MATERN52 && kind != PG_KIND_MATERN32) {
+    if (kind != PG_KIND_RBF && kind != PG_KIND_MATERN52 && kind != PG_KIND_MATERN32 && kind != PG_KIND_RQ) {
         pg_set_error("pg_kbuild: no matrix-pipe body for kernel kind %d", kind);
         return -2;
     }
@@ -244,6 +272,7 @@ int pg_kbuild_mfma(hipStream_t st, const pg_covspec& spec, const double* hp, con
     do {                                                                                                                   \
         if (kind == PG_KIND_RBF) KB_KIND(DP, PG_KIND_RBF);                                                                 \
         if (kind == PG_KIND_MATERN52) KB_KIND(DP, PG_KIND_MATERN52);                                                       \
+        if (kind == PG_KIND_RQ) KB_KIND(DP, PG_KIND_RQ);                                                                   \
         KB_KIND(DP, PG_KIND_MATERN32);                                                                                     \
     } while (0)
     if (d <= 4) KB_GO(4);
@@ -289,7 +318,8 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void pg_grad_mfma_kern
     for (int idx = tid; idx < nhp; idx += 256) part[(long)blk * nhp + idx] = 0.0;
     if (r_begin >= tiles) return;
     __shared__ T xc[KT * LDP], ncs[KT], acs[KT], xr[2][KT * LDP], nrs[2][KT], ars[2][KT], cs[4][16];
-    __shared__ double tab[32], tab2[32], red[4][18];   // tab2 = 2 tab: the weight 2 of an interior tile rides in the covariance value
+    constexpr bool SHAPE = KIND == PG_KIND_RQ;         // a shape entry behind the length scales: one more sum, one more slot of the fold
+    __shared__ double tab[32], tab2[32], red[4][SHAPE ? 19 : 18];   // tab2 = 2 tab: the weight 2 of an interior tile rides in the covariance value
     const T sig2x2 = (T)(2.0 * hp[spec.off[0]] * hp[spec.off[0]]);
     const int o = spec.off[0];
     const int kk = tid % DP;
@@ -297,6 +327,8 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void pg_grad_mfma_kern
     const double x0k = kk < d ? (double)X[kk] : 0.0;
     const double sg = hp[o];
     const T sig2 = (T)(sg * sg);
+    const double shd = kind_shape2(spec, hp, 0, d);
+    const T sha = (T)shd, ish = (T)(1.0 / shd);      // rational quadratic: alpha^2, 1 / alpha^2
     PT pcol, prow;
     pcol.load(X, ldx, n, tc * KT, d, tid);
     prow.load(X, ldx, n, r_begin * KT, d, tid);
@@ -326,6 +358,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void pg_grad_mfma_kern
     for (int r = 0; r < 4; ++r) { P[r] = (T)0; P2[r] = (T)0; }
     T pgs = (T)0;                     // this lane's share of the column sums of G (column j0 + c16)
     double accs = 0.0, trw = 0.0;     // sum W K (the sigma entry), sum of the diagonal's W (the noise entries)
+    double accf = 0.0;                // SHAPE: sum W K fs (the shape entry)
     const long jcol = min((long)gj, ldk - 1);
     // K^-1 one block ahead of the arithmetic (a whole tile row ahead -- sixteen values per lane in flight -- was measured: no gain, the
     // kernel is not bound by its loads: tools/probe_tile_bodies.py).  The blocks follow one another sixteen rows
@@ -362,6 +395,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void pg_grad_mfma_kern
         const T* nb = nrs[cur];
         const T* ab = ars[cur];
         T accs_t = (T)0;                                             // this tile row's share of sum W K
+        T accf_t = (T)0;                                             // ... and of sum W K fs
         typedef float pf2 __attribute__((ext_vector_type(2)));
         pf2 acc2 = {0.0f, 0.0f}, pgs2 = {0.0f, 0.0f};                // (fp32 interior body: the same sums in pairs)
         // one tile row = four 16 x 16 blocks.  INTERIOR (strictly below the diagonal, inside the real points: weight 2 everywhere) is
@@ -390,7 +424,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void pg_grad_mfma_kern
 #pragma unroll
                 for (int s = 0; s < NS; ++s) acc = Mfma<T>::run(af[s], bq[s], acc);
                 T gr_[4];
-                if constexpr (sizeof(T) == 4 && INTERIOR) {
+                if constexpr (sizeof(T) == 4 && INTERIOR && !SHAPE) {      // (the rational quadratic's logarithm has no packed form)
                     // fp32, interior: the four elements of a lane as two PAIRS on the packed fp32 instructions (v_pk_fma_f32 / v_pk_mul_f32 /
                     // v_pk_add_f32: two elements per issue slot); only the root and the exponential stay one element at a time
                     typedef float f2 __attribute__((ext_vector_type(2)));
@@ -443,9 +477,10 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void pg_grad_mfma_kern
                         else if (gj < gi) w *= (T)2;
                         else trw += (double)w;
                     }
-                    T kv, base;
-                    KmVal<T, KIND>::run(sq, INTERIOR ? sig2x2 : sig2, INTERIOR ? tab2 : tab, kv, base);
+                    T kv, base, fs;
+                    km_val<T, KIND>(sq, INTERIOR ? sig2x2 : sig2, INTERIOR ? tab2 : tab, sha, ish, kv, base, fs);
                     accs_t += w * kv;
+                    if (SHAPE) accf_t += w * fs;
                     gr_[r] = w * base;
                     pgs += gr_[r];
                 }
@@ -467,6 +502,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void pg_grad_mfma_kern
         if (tr > tc && (tr + 1) * KT <= n) tile_row(std::true_type{});
         else tile_row(std::false_type{});
         accs += (double)accs_t + (double)acc2.x + (double)acc2.y;
+        if (SHAPE) accf += (double)accf_t;
         pgs += (T)(pgs2.x + pgs2.y);
         if (more) {
             prow.store(xr[cur ^ 1], sc, x0k, tid);
@@ -508,9 +544,16 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void pg_grad_mfma_kern
         const double s1 = wave_sum(accs), s2 = wave_sum(trw);
         if (lane == 0) { red[wave][16] = s1; red[wave][17] = s2; }
     }
+    if constexpr (SHAPE) {
+        const double s3 = wave_sum(accf);
+        if (lane == 0) red[wave][18] = s3;
+    }
     __syncthreads();
     if (tid == 0) part[(long)blk * nhp + o] = red[0][16] + red[1][16] + red[2][16] + red[3][16];
     else if (tid <= d) part[(long)blk * nhp + o + tid] = red[0][tid - 1] + red[1][tid - 1] + red[2][tid - 1] + red[3][tid - 1];
+    if constexpr (SHAPE) {
+        if (tid == 32) part[(long)blk * nhp + o + d + 1] = red[0][18] + red[1][18] + red[2][18] + red[3][18];
+    }
     if (tid < spec.nnoise) part[(long)blk * nhp + spec.noise_off[tid]] = red[0][17] + red[1][17] + red[2][17] + red[3][17];
 }
 
@@ -533,7 +576,7 @@ int pg_grad_mfma(hipStream_t st, const pg_covspec& spec, const double* hp, const
     const int gch = gch_env > 0 ? std::min(gch_env, 64) : std::max(2, std::min(tiles / 16, 32));
     *nblk = tiles * ((tiles + gch - 1) / gch);
     const int kind = spec.kind[0];
-    if (kind != PG_KIND_RBF && kind != PG_KIND_MATERN52 && kind != PG_KIND_MATERN32) {
+    if (kind != PG_KIND_RBF && kind != PG_KIND_MATERN52 && kind != PG_KIND_MATERN32 && kind != PG_KIND_RQ) {
         pg_set_error("pg_nlml_grad: no matrix-pipe body for kernel kind %d", kind);
         return -2;
     }
@@ -542,6 +585,7 @@ int pg_grad_mfma(hipStream_t st, const pg_covspec& spec, const double* hp, const
     do {                                                                                                                                   \
         if (kind == PG_KIND_RBF) GR_KIND(DP, PG_KIND_RBF);                                                                                 \
         if (kind == PG_KIND_MATERN52) GR_KIND(DP, PG_KIND_MATERN52);                                                                       \
+        if (kind == PG_KIND_RQ) GR_KIND(DP, PG_KIND_RQ);                                                                                   \
         GR_KIND(DP, PG_KIND_MATERN32);                                                                                                     \
     } while (0)
     if (d <= 4) GR_GO(4);

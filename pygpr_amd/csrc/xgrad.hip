@@ -82,6 +82,8 @@ __global__ __launch_bounds__(256) void pg_xgrad_kernel(pg_covspec spec, const do
             const double sg = hp[spec.off[cp]];
             const T sig2 = (T)(sg * sg);
             const double f2 = 2.0 * kind_hcoef(kind);
+            const double sh = kind_shape2(spec, hp, cp, d);
+            const T sha = (T)sh, ish = (T)(1.0 / sh);      // rational quadratic: alpha^2, 1 / alpha^2
             const T* lc = l2s + cp * DMAX;
             for (int tc = t0; tc < t1; ++tc) {
                 __syncthreads();          // the previous tile's readers are done (and, first time round, l2s / xrs are published below)
@@ -119,9 +121,9 @@ __global__ __launch_bounds__(256) void pg_xgrad_kernel(pg_covspec spec, const do
                         if constexpr (HOLD) df[k] = dd;
                         sq += lc[k] * dd * dd;
                     }
-                    T kv, bt;
+                    T kv, bt, ft;
                     if (kind == PG_KIND_RBF) bt = sig2 * pg_exp(-sq);
-                    else matern_val<T>(kind, sig2, sq, kv, bt);
+                    else matern_val<T>(kind, sig2, sq, kv, bt, sha, ish, ft);
                     const double f = f2 * (double)bt;
                     const double wu = HU ? f * (double)us[c] : 0.0;
                     const double wb = HB ? f * (double)bs[lane * BLD + c] : 0.0;

@@ -13,9 +13,10 @@ k = ops.empty(n, n)
 for d in (8, 2, 16):
     rng = np.random.default_rng(d)
     x = torch.from_numpy(rng.random((n, d))).cuda()
-    hp = torch.tensor([1.0] + [1.0] * d + [0.1], dtype=torch.float64).cuda()
-    for kind, name in ((0, "rbf"),):
-        spec = make_spec([kind], [0], [d + 1])
+    for kind, name in ((0, "rbf"), (3, "m32"), (6, "rq")):      # (the rational quadratic's block is one wider: its shape alpha)
+        w = d + 2 if kind == 6 else d + 1
+        hp = torch.tensor([1.0] * w + [0.1], dtype=torch.float64).cuda()
+        spec = make_spec([kind], [0], [w])
         tl = ev(lambda: ops.kernel_build(spec, hp, x, None, k, lower_only=True, jitter=1e-7))
         tf = ev(lambda: ops.kernel_build(spec, hp, x, None, k, jitter=1e-7))
         print(f"d={d:2d} {name:6s} lower {tl:.3f} ms {(4*n*(n+64)+8*n*d)/tl/1e6:.0f} GB/s   full(mirror) {tf:.3f} ms  {8*n*n/tf/1e6:.0f} GB/s", flush=True)
