@@ -1,5 +1,5 @@
 """Device-op layer: torch-ROCm tensors are only buffers + the current stream; every number is
-produced by libpygpr_hip through the C ABI (include/pygpr_hip.h).  No CPU path exists here:
+produced by libpygpr_hip through the C ABI (include/pygpr_hip*.h).  No CPU path exists here:
 `get_ops()` raises when the library or a GPU is missing."""
 import atexit
 import ctypes as C
@@ -320,6 +320,19 @@ class HipOps:
         """m (lower triangle) += q q^T on the n real points (pg_loo_fold)."""
         self._chk(m, q)
         self._call("pg_loo_fold", _code(m.dtype), int(n), _p(m), m.stride(0), _p(q), self._st())
+
+    # -- normal variates (include/pygpr_hip_sample.h) -------------------------------------------
+    def randn(self, out, rows, cols, seed, stream_id=0, row0=0):
+        """out[r][q] = normal(seed, stream_id, row0 + r, q) for r < rows, q < cols, zero in the rest of out (pg_randn): out is a 2-D
+        device tensor or view [rows_pad, cols_pad] with unit stride along a row -- any row stride, any alignment."""
+        if not (out.is_cuda and out.dim() == 2 and out.stride(1) == 1):
+            raise ValueError("randn needs a 2-D CUDA tensor with unit stride along its rows")
+        seed = int(seed)
+        if not -(1 << 63) <= seed < (1 << 63):
+            raise ValueError("randn: the seed must fit a signed 64-bit integer, got %d" % seed)
+        self._call("pg_randn", _code(out.dtype), seed, int(stream_id), int(row0), int(rows), int(cols), _p(out), out.stride(0), out.shape[0],
+                   out.shape[1], self._st())
+        return out
 
     # -- derivatives in the test points -------------------------------------------------------
     def kernel_xgrad(self, spec, hp, xq, z, u=None, b=None, out_u=None, out_b=None, trans_b=False, accumulate=False):

@@ -5,6 +5,7 @@
 #include "chainstep.h"
 #include "linalg.h"
 #include "pygpr_hip_loo.h"
+#include "pygpr_hip_sample.h"
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -616,6 +617,18 @@ int pg_loo_fold(pg_handle h, int dtype, int n, void* M, long ldm, const void* q,
     NEED(n >= 1 && ldm >= n, "1 <= n <= ldm");
     return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
         return pg_loo_fold_t<T>(ST(stream), n, (T*)M, ldm, (const T*)q);
+    });
+}
+
+int pg_randn(pg_handle h, int dtype, long seed, int stream_id, int row0, int rows, int cols, void* Z, long ldz, int rows_pad, int cols_pad,
+             void* stream) {
+    JOIN(h, stream);
+    NEED(h && Z, "null pointer");
+    NEED(rows_pad >= 1 && cols_pad >= 1 && rows >= 0 && rows <= rows_pad && cols >= 0 && cols <= cols_pad && ldz >= cols_pad,
+         "0 <= rows <= rows_pad, 0 <= cols <= cols_pad <= ldz, rows_pad >= 1, cols_pad >= 1");
+    NEED(row0 >= 0 && (long)row0 + rows <= 0x7fffffffL, "row0 >= 0 and row0 + rows <= 2^31 - 1");
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_randn_t<T>(ST(stream), seed, stream_id, row0, rows, cols, (T*)Z, ldz, rows_pad, cols_pad);
     });
 }
 

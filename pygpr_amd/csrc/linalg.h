@@ -87,3 +87,6 @@ int pg_loo_terms_t(hipStream_t, int n, int n_pad, const T* Minv, long ldm, const
                    double* work);
 template <typename T> int pg_loo_weights_t(hipStream_t, int n, const T* c, const T* alpha, T* Kinv, long ldk, T* p, T* q);
 template <typename T> int pg_loo_fold_t(hipStream_t, int n, T* M, long ldm, const T* q);
+// sample.hip: standard normals from the counter-based generator (include/pygpr_hip_sample.h)
+template <typename T>
+int pg_randn_t(hipStream_t, long seed, int stream_id, int row0, int rows, int cols, T* Z, long ldz, int rows_pad, int cols_pad);

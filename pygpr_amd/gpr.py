@@ -15,6 +15,8 @@ Differences a caller can observe:
   * assigning `model.x` / `model.y` marks the model dirty (the reference keeps a stale factor there)
   * `krn`, `krnchd`, `wt` are read-only views materialised on access
   * `append` and `loo_predict` are new: conditioning on further points, and leave-one-out predictions from the cached L^-1
+  * `sampler` / `sample` are new: joint draws from the posterior or the prior at a set of test points (`PosteriorSampler`), with
+    normals from the library's counter-based generator (`randn`)
 """
 import os
 from typing import Sequence
@@ -173,6 +175,12 @@ class GPR:
 
     def loo_predict(self) -> Sequence[Tensor]:
         raise NotImplementedError("%s has no leave-one-out prediction; fit an Exact_GP on the data" % type(self).__name__)
+
+    def sampler(self, xp: Tensor, **kwargs):
+        raise NotImplementedError("%s has no joint sampler; draw from an Exact_GP" % type(self).__name__)
+
+    def sample(self, xp: Tensor, n_samples: int = 1, seed: int = 0, **kwargs) -> Tensor:
+        raise NotImplementedError("%s has no joint sampler; draw from an Exact_GP" % type(self).__name__)
 
     def predict_var(self, xp: Tensor, **kwrgs: Tensor) -> Tensor:
         raise NotImplementedError
@@ -513,6 +521,68 @@ class Exact_GP(GPR):
         ops.loo_terms(self._minv(e), e.alpha, e.y, e.n, c, mu, var, out, work)
         return [mu.to(self._x.device), var.to(self._x.device)]
 
+    # ---- joint draws ------------------------------------------------------------------------------
+    def sampler(self, xp: Tensor, noise: bool = False, jitter: float = 1e-7, prior: bool = False) -> "PosteriorSampler":
+        """A snapshot of the joint Gaussian at xp ([m, d], or [nc, m, d] for a batched model: the rules of `predict`) to draw from.
+        prior=False: mean and covariance of predict(xp, "full"), through the same device path (the mean is predict's, bit for bit).
+        prior=True: mean 0 and covariance cov.kernel(params, xp); needs no fit and triggers none.  Both covariances carry
+        sum sigma_n^2 on their diagonal (White_noise sees xp = None there): noise=True keeps it -- draws of new observations y* --,
+        noise=False (the default) subtracts it -- draws of the latent function.  `jitter` is then added to the diagonal and the matrix is
+        factored (pg_potrf, experts of a batched model together); a failed pivot raises torch.linalg.LinAlgError -- the jitter is never
+        raised silently.  The sampler owns its buffers: later changes of the model do not reach it, and making it changes nothing a
+        later predict returns."""
+        ops = get_ops()
+        dt = self.dtype
+        xpd = self._xp_device(xp)
+        m = xpd.shape[-2]
+        if m < 1:
+            raise ValueError("Exact_GP.sampler: xp holds no points")
+        m_pad = pad_to(m)
+        d = self._x.shape[-1]
+        spec, _ = spec_of(self.cov, d)
+        _, _, noise_offs, _ = layout(self.cov, d)
+        nexp = len(self._device_experts())
+        if xpd.dim() == 3 and xpd.shape[0] not in (1, nexp):
+            raise RuntimeError("batch dimension of xp (%d) does not match the %d experts" % (xpd.shape[0], nexp))
+        hp_rows = self._hp_rows()
+        state = {}
+
+        def enqueue():
+            if prior:
+                mean_all = ops.zeros(nexp, m_pad, dtype=dt)
+                c_all = ops.empty(nexp, m_pad, m_pad, dtype=dt)
+                for b in range(nexp):
+                    hp = ops.to_device(hp_rows[b % hp_rows.shape[0]], torch.float64)
+                    ops.kernel_build(spec, hp, xpd if xpd.dim() == 2 else xpd[b % xpd.shape[0]], None, c_all[b])   # K** + sum sigma_n^2 I, identity padding
+            else:
+                mean_all, c_all = self._predict_device(xpd, "full", padded=True)
+            for b in range(nexp):
+                diag = c_all[b].diagonal()[:m]
+                if not noise:
+                    row = hp_rows[b % hp_rows.shape[0]]
+                    diag.sub_(float(sum(row[o] ** 2 for o in noise_offs)))
+                diag.add_(float(jitter))
+            info = torch.zeros(nexp, dtype=torch.int32, device=ops.device)
+            invd = ops.empty(nexp, ops.potrf_worksize(m_pad, dt), dtype=dt)
+            if nexp == 1:
+                ops.potrf(c_all[0], invd[0], info)
+            else:
+                ops.potrf_trtri_batched(c_all, invd, info, None)
+            state.update(mean=mean_all, chol=c_all, info=info, invd=invd)
+
+        for bad in _checked(enqueue, lambda: state["info"].tolist()):
+            if bad:
+                raise _lin_alg_error(bad, " -- the %s covariance at xp, with jitter = %g and noise = %s, is not positive definite in %s: raise "
+                                          "`jitter` or draw with noise=True" % ("prior" if prior else "posterior", jitter, bool(noise),
+                                                                               "float32" if dt == torch.float32 else "float64"))
+        for b in range(nexp):      # the product of a draw reads the whole diagonal 128-blocks of the factor: clear what potrf left above it
+            ops.tril(state["chol"][b], m_pad)
+        return PosteriorSampler(state["mean"], state["chol"], m, xp.device, nexp > 1, bool(noise), float(jitter))
+
+    def sample(self, xp: Tensor, n_samples: int = 1, seed: int = 0, **sampler_kwargs) -> Tensor:
+        """sampler(xp, **sampler_kwargs).draw(n_samples, seed): [n_samples, m] ([nc, n_samples, m] for a batched model)."""
+        return self.sampler(xp, **sampler_kwargs).draw(n_samples, seed)
+
     def _kss_diag(self, b: int) -> float:
         """diag of cov.kernel(params, xp): sum sigma_c^2 + sum sigma_n^2 (White_noise sees xp=None,
         gpr.py:98), no jitter."""
@@ -550,11 +620,12 @@ class Exact_GP(GPR):
             return mean, var
         return mean, None
 
-    def _predict_full(self, xqs):
+    def _predict_full(self, xqs, padded=False):
         """Mean K* alpha and K** - K* K^-1 K*^T = K** - V^T V with V = L^-1 K*^T (gpr.py:80-85,108-120) for every expert (expert b at the
         points xqs[b]): per expert the test-point-major K* -- built ONCE, the mean is taken from it too (round 4 built it a second time
         for the mean) --, Vt = K* L^-T (both operands read along k) and K**; then ONE rank-n update for all experts -- the 136 lower tiles
-        of one 2048 x 2048 output leave three quarters of the chip idle, eight experts' tiles fill it.  Returns (means, covariances)."""
+        of one 2048 x 2048 output leave three quarters of the chip idle, eight experts' tiles fill it.  Returns (means, covariances);
+        padded: the fresh stacks they are views of instead, mean [nexp, m_pad] and covariance [nexp, m_pad, m_pad] (identity in the padding)."""
         ops = get_ops()
         spec, _ = spec_of(self.cov, self._x.shape[-1])
         experts = self._experts
@@ -593,6 +664,8 @@ class Exact_GP(GPR):
         for i in range(len(experts)):
             ops.symmetrize(c_all[i], m_pad)                 # the upper triangle is the mirror: exactly symmetric
             out.append(c_all[i][:m, :m])
+        if padded:
+            return mean_all, c_all
         return [mean_all[i, :m] for i in range(len(experts))], out
 
     def _predict_batched(self, xpd, want):
@@ -645,7 +718,7 @@ class Exact_GP(GPR):
                                               spec, bat["hp"][b0: b0 + cnt], work[:cnt])
         return [mean_all[b, :m] for b in range(nb)], ([var_all[b, :m] for b in range(nb)] if diag else [None] * nb)
 
-    def _predict_device(self, xpd, want):
+    def _predict_device(self, xpd, want, padded=False):
         """Per-expert device tensors (mean[m], var[m] | cov[m,m] | None) for device-resident test points: xpd [m, d]
         (the same points for every expert) or [nc, m, d] (expert b predicts at xpd[b], as cov.kernel(params, x, xp)
         broadcasts in the reference, gpr.py:79)."""
@@ -654,7 +727,7 @@ class Exact_GP(GPR):
         if xpd.dim() == 3 and xpd.shape[0] not in (1, len(self._experts)):
             raise RuntimeError("batch dimension of xp (%d) does not match the %d experts" % (xpd.shape[0], len(self._experts)))
         if want == "full":       # K* is built once per expert there: mean, Vt and the update all come from it
-            return self._predict_full([xpd if xpd.dim() == 2 else xpd[b % xpd.shape[0]] for b in range(len(self._experts))])
+            return self._predict_full([xpd if xpd.dim() == 2 else xpd[b % xpd.shape[0]] for b in range(len(self._experts))], padded)
         if self._bat is not None and len(self._experts) > 1 and not os.environ.get("PG_PREDICT_SERIAL"):
             self.last_predict_batched = True
             return self._predict_batched(xpd, want)
@@ -882,3 +955,84 @@ class _PredictFn(torch.autograd.Function):
         (xp,) = ctx.saved_tensors
         g = model._predict_vjp(xp, ctx.want, grads) if ctx.needs_input_grad[2] else None
         return None, None, g, None, None, None
+
+
+_DRAW_BYTES = 1 << 30   # PosteriorSampler.draw: Z and the product of one chunk of samples stay under this together
+
+
+class PosteriorSampler:
+    """A joint Gaussian N(mean, L L^T) at m points, as Exact_GP.sampler snapshots it: `mean` [m] ([nc, m] for a batched model), `chol`
+    = L [m, m] ([nc, m, m]; lower, zero upper triangle; materialised on access like Exact_GP.krnchd), `m`, `dtype`, `noise`, `jitter`.
+    The buffers are the sampler's own."""
+
+    def __init__(self, mean_all, chol_all, m, device, batched, noise, jitter):
+        self._mean, self._chol = mean_all, chol_all         # [nexp, m_pad], [nexp, m_pad, m_pad]: block-diag(L, I), upper triangle zero
+        self.m, self.dtype, self.noise, self.jitter = int(m), chol_all.dtype, noise, jitter
+        self._device, self._batched = device, batched
+
+    def _shape(self, t):
+        return (t if self._batched else t[0]).contiguous().to(self._device)
+
+    @property
+    def mean(self) -> Tensor:
+        return self._shape(self._mean[:, : self.m])
+
+    @property
+    def chol(self) -> Tensor:
+        return self._shape(self._chol[:, : self.m, : self.m])
+
+    def draw(self, n_samples: int = 1, seed: int = 0, first: int = 0, z: Tensor = None) -> Tensor:
+        """[n_samples, m] ([nc, n_samples, m] for a batched model) on xp's device: sample s is mean + L z_s with
+        z_s = normal(seed, stream = expert index, first + s, .) from the library's generator (pygpr_amd.randn gives the same values), so
+        draw(n, seed, first = k) continues draw(k, seed) without overlap.  With z given ([n_samples, m] or [nc, n_samples, m]) that array
+        is used in place of the generator and n_samples, seed and first are ignored.  The samples are generated in chunks of rows
+        (Z and the product of a chunk under 1 GiB); by the generator's construction the chunk size cannot change Z."""
+        ops = get_ops()
+        nexp, m_pad = self._chol.shape[0], self._chol.shape[1]
+        m, dt = self.m, self.dtype
+        if z is not None:
+            if not isinstance(z, Tensor) or z.dim() not in (2, 3) or z.shape[-1] != m or (z.dim() == 3 and z.shape[0] != nexp) \
+                    or (z.dim() == 2 and nexp > 1):
+                raise ValueError("PosteriorSampler.draw: z must be [n_samples, %d]%s, got %s"
+                                 % (m, " or [1, n_samples, %d]" % m if nexp == 1 else " with %d leading experts" % nexp,
+                                    tuple(z.shape) if isinstance(z, Tensor) else type(z).__name__))
+            n = z.shape[-2]
+            zd = ops.to_device(z.reshape(nexp, n, m), dt)
+        else:
+            n = int(n_samples)
+            if n < 0:
+                raise ValueError("PosteriorSampler.draw: n_samples must not be negative, got %d" % n)
+            if int(first) < 0:
+                raise ValueError("PosteriorSampler.draw: first must not be negative, got %d" % int(first))
+        out = ops.empty(nexp, n, m, dtype=dt)
+        item = torch.empty(0, dtype=dt).element_size()
+        chunk = max(128, (_DRAW_BYTES // (2 * nexp * m_pad * item)) // 128 * 128)
+        for s0 in range(0, n, chunk):
+            sc = min(chunk, n - s0)
+            s_pad = pad_to(sc, 128)
+            if z is not None:
+                zs = ops.zeros(nexp, s_pad, m_pad, dtype=dt)
+                zs[:, :sc, :m] = zd[:, s0: s0 + sc]
+            else:
+                zs = ops.empty(nexp, s_pad, m_pad, dtype=dt)
+                for b in range(nexp):
+                    ops.randn(zs[b], sc, m, seed, stream_id=b, row0=int(first) + s0)
+            prod = ops.empty(nexp, s_pad, m_pad, dtype=dt)
+            ops.trmm_lower_kt(self._chol, zs, prod)             # Z L^T, every expert in one launch
+            torch.add(prod[:, :sc, :m], self._mean[:, None, :m], out=out[:, s0: s0 + sc])
+        return (out if self._batched else out[0]).to(self._device)
+
+
+def randn(rows: int, cols: int, seed: int = 0, stream: int = 0, first_row: int = 0, dtype=torch.float64) -> Tensor:
+    """Host tensor [rows, cols] of the library's counter-based standard normals (include/pygpr_hip_sample.h: Philox4x32-10 and
+    Box-Muller in fp64): element (r, q) = normal(seed, stream, first_row + r, q), whatever the shape asked for; float32 is the rounding of
+    the float64 value.  What PosteriorSampler.draw multiplies with its factor (stream = expert index, first_row = first)."""
+    rows, cols = int(rows), int(cols)
+    if rows < 0 or cols < 0 or int(first_row) < 0:
+        raise ValueError("randn: rows, cols and first_row must not be negative")
+    if dtype not in (torch.float64, torch.float32):
+        raise TypeError("randn computes in float64 or float32, got %s" % dtype)
+    if rows == 0 or cols == 0:
+        return torch.empty(rows, cols, dtype=dtype)
+    ops = get_ops()
+    return ops.randn(ops.empty(rows, cols, dtype=dtype), rows, cols, seed, stream_id=stream, row0=first_row).cpu()

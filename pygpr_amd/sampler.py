@@ -116,5 +116,6 @@ class MATERN1(UNIFORM):
 
 def sample_gp(*args, **kwargs):
     """Exported by the reference (PyGPR/__init__.py:6) but dead there: sampler.py:122-137 calls `cov(x)` on objects that
-    are not callable ("dead" row).  Kept as a name for import compatibility."""
+    are not callable ("dead" row).  Kept as a name for import compatibility; draws from a GP prior are
+    Exact_GP.sample(xp, prior=True)."""
     raise NotImplementedError("sample_gp is legacy code that cannot run in the reference either (sampler.py:122-137)")
