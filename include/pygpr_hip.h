@@ -47,6 +47,9 @@ extern "C" {
 /* 5 is unassigned and stays an unknown kind */
 #define PG_KIND_RQ (6)     /* new (not in the reference): rational quadratic, hp = [sigma, l_1..l_d, alpha] (d + 2 values):
                               sigma^2 (1 + sq / alpha^2)^(-alpha^2), sq the scaled squared distance of the squared exponential */
+/* 7 is unassigned and stays an unknown kind, like 5 */
+#define PG_KIND_PERIODIC (8) /* new (not in the reference): ARD periodic, hp = [sigma, l_1..l_d, p_1..p_d] (2 d + 1 values):
+                              sigma^2 exp(-sum_k l_k^2 sin^2(pi (x_k - x'_k) / p_k)); never PG_KIND_SQDIST's stand-in */
 #define PG_MAX_COMP 4
 #define PG_MAX_DIM 64
 
@@ -59,7 +62,9 @@ typedef struct pg_covspec {
     int ncomp;                  /* stationary components                                     */
     int kind[PG_MAX_COMP];      /* PG_KIND_*                                                 */
     int off[PG_MAX_COMP];       /* index of component c's sigma inside hp: [sigma, l_1..l_d], */
-                                /* and for PG_KIND_RQ its shape alpha at off[c] + d + 1       */
+                                /* and for PG_KIND_RQ its shape alpha at off[c] + d + 1,      */
+                                /* for PG_KIND_PERIODIC its periods p_1..p_d at               */
+                                /* off[c] + d + 1 .. off[c] + 2 d                             */
     int nnoise;                 /* White_noise children (covar.py:209-269)                   */
     int noise_off[PG_MAX_COMP]; /* index of each sigma_n inside hp                           */
 } pg_covspec;

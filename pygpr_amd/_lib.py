@@ -16,6 +16,7 @@ HEADER_SAMPLE = os.path.join(os.path.dirname(_HERE), "include", "pygpr_hip_sampl
 PG_F64, PG_F32 = 0, 1
 PG_KIND_RBF, PG_KIND_MATERN52, PG_KIND_SQDIST, PG_KIND_MATERN32, PG_KIND_MATERN12 = 0, 1, 2, 3, 4
 PG_KIND_RQ = 6      # (5 is unassigned: the library refuses it)
+PG_KIND_PERIODIC = 8    # hp = [sigma, l_1..l_d, p_1..p_d] (7, like 5, is unassigned: the library refuses it)
 PG_MAX_COMP, PG_MAX_DIM = 4, 64
 PAD = 256  # every dimension given to the O(n^3) entry points is a multiple of this
 

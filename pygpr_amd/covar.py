@@ -11,6 +11,8 @@ Same names, hyper-parameter layout and shapes as the reference:
   * `Matern32`, `Matern12` NEW, the rest of the Matern family (nu = 3/2 and 1/2, the exponential kernel), same hp layout.
   * `Rational_quadratic`   NEW, hp = [sigma, l_1..l_d, alpha] (d + 2 values): sigma^2 (1 + sq / alpha^2)^(-alpha^2) with the SE's
                            scaled squared distance sq; the squared exponential as alpha grows.
+  * `Periodic`             NEW, hp = [sigma, l_1..l_d, p_1..p_d] (2 d + 1 values), one period per dimension:
+                           sigma^2 exp(-sum_k l_k^2 sin^2(pi (x_k - x'_k) / p_k)); the phase is taken from the difference.
 Leading batch dims on hp and/or x follow the reference's flatten-to-one-batch-dim rule.  Tensors come
 back on the device of `x` (CPU in -> CPU out); the arithmetic always runs on the GPU in the dtype of
 `x` (float64, or float32 as an explicit opt-in) -- unlike the reference, nothing here touches torch's
@@ -221,6 +223,35 @@ class Rational_quadratic(Squared_exponential):
         kinds.append(self._kind)
         offs.append(base)
         return d + 2
+
+
+class Periodic(Squared_exponential):
+    """ARD periodic kernel with one period per dimension, hp = [sigma, l_1..l_d, p_1..p_d]: 2 d + 1 values, the periods behind the SE's
+    block.  The conventions are the SE's: l are INVERSE length scales, sigma and l enter squared, and there is no 1/2 and no factor 2 in
+    the exponent.  With D_k = x_k - x'_k, w_k = pi / p_k and s_k = sin(w_k D_k):
+
+        sq        = sum_k l_k^2 s_k^2
+        K         = sigma^2 exp(-sq)
+        dK/dsigma = 2 K / sigma
+        dK/dl_k   = -2 K l_k s_k^2
+        dK/dp_k   = K l_k^2 sin(2 w_k D_k) w_k D_k / p_k
+        dK/dx*_k  = -K l_k^2 sin(2 w_k D_k) w_k         (D = x* - x, rows = test points)
+
+    MacKay's exp(-2 sin^2(pi D / p) / ell^2) is this kernel with l^2 = 2 / ell^2.  K is even in p_k, so the period enters as it is;
+    p_k = 0 gives NaN and is not worked around.  The phase is formed from the coordinate DIFFERENCE, t = D_k / p_k reduced exactly to
+    |t - rint(t)| <= 1/2: K is exactly symmetric, exactly sigma^2 where a point meets itself, and keeps its accuracy on data far from
+    the origin (the squared exponential on the warped point (l_k / 2) [cos, sin](2 pi x_k / p_k) is the same function and loses
+    |x| / p ulps).  Sums with a trend kernel are written Compose([Squared_exponential(), Periodic(), White_noise()])."""
+
+    _kind = _lib.PG_KIND_PERIODIC
+
+    def _collect(self, d, base, kinds, offs, noise):
+        kinds.append(self._kind)
+        offs.append(base)
+        return 2 * d + 1
+
+    def distance(self, x: Tensor, xp: Tensor = None) -> Tensor:
+        raise TypeError("Periodic has no Euclidean distance: Squared_exponential.distance is the squared exponential's")
 
 
 class White_noise(_DeviceKernel):

@@ -350,7 +350,7 @@ static int check_spec(const pg_covspec* s, const char* fn, bool allow_sqdist = f
     }
     for (int c = 0; c < s->ncomp; ++c)
         if (s->kind[c] != PG_KIND_RBF && s->kind[c] != PG_KIND_MATERN52 && s->kind[c] != PG_KIND_MATERN32 && s->kind[c] != PG_KIND_MATERN12 &&
-            s->kind[c] != PG_KIND_RQ && !(allow_sqdist && s->kind[c] == PG_KIND_SQDIST)) {
+            s->kind[c] != PG_KIND_RQ && s->kind[c] != PG_KIND_PERIODIC && !(allow_sqdist && s->kind[c] == PG_KIND_SQDIST)) {
             pg_set_error("%s: unknown kernel kind %d", fn, s->kind[c]);
             return -1;
         }

@@ -9,6 +9,9 @@
 //   * one fp64 SE child, no accumulate pass, d <= 8 or d > 16: kb_body<FAST>, the expansion |x|^2 + |x'|^2 - 2 x.x' on the VALU;
 //   * any other single child (Matern-1/2, d > 16, an accumulate pass): kb_body<PRESC>, direct differences of coordinates
 //     pre-multiplied by the inverse length scales;  several children: the general kb_body, l^2 applied per coordinate.
+//   * a periodic child (hp = [sigma, l_1..l_d, p_1..p_d]: K = sigma^2 exp(-sum_k l_k^2 sin^2(pi D_k / p_k))), alone or among others: the
+//     general kb_body in its PER instantiation -- the phase from the direct difference, 1 / p_k staged beside l^2; never PRESC, FAST or
+//     the matrix pipe.
 // Direct differences are exactly symmetric and never negative (the reference expands into a GEMM, covar.py:102-127).  One 64x64
 // output tile per 256-thread workgroup at a time; both point tiles are staged in LDS k-major ([d][64]); each thread owns a 4x4
 // micro-tile whose columns are two 16-byte vectors, so every store instruction writes 256 contiguous bytes per row.
@@ -18,8 +21,9 @@
 // Matern kinds as dK/dl_k = coef base l_k D_k^2 (kind_hcoef: coef / 2).  The reference materialises dK[nhp,n,n] and solves against
 // it (loss.py:116-121); this is the same number by the K^-1 route.  The rational quadratic adds dK/dalpha = 2 alpha fs (rq_terms).  One
 // child of kind SE / Matern-5/2 / Matern-3/2 / rational quadratic at d <= 16 takes
-// the matrix-pipe contraction of kmfma.hip; everything else (Matern-1/2, d > 16, several children, PG_GRAD_MFMA=0) takes
-// pg_grad_kernel here: direct differences on the VALU.
+// the matrix-pipe contraction of kmfma.hip; everything else (Matern-1/2, the periodic kind, d > 16, several children, PG_GRAD_MFMA=0)
+// takes pg_grad_kernel here: direct differences on the VALU.  The periodic kind: dK/dl_k = -2 K l_k s_k^2, dK/dp_k = K l_k^2
+// sin(2 pi t_k) pi t_k / p_k with t_k = D_k / p_k, s_k = sin(pi t_k) (per_terms, kfun.h).
 #include "kbuild.h"
 #include "kfun.h"
 #include "kmfma.h"
@@ -55,10 +59,16 @@ __device__ __forceinline__ void stage_points(T* dst, const T* __restrict__ X, lo
 //            |x|^2 + |x'|^2 - 2 x.x' (covar.py:102-127, there a matmul): one FMA per coordinate instead of a subtraction and an
 //            FMA.  The rows are staged times two, -|x|^2 per point waits in LDS (nrm_r, nrm_c), so the accumulator STARTS at
 //            -|x|^2 - |x'|^2 and ends as the exponential's argument; pg_exp_tab with sigma^2 folded into its table.
-template <typename T, bool PRESC, bool CHECKED, bool MIRROR, bool FAST = false>
+//   PER    : the spec holds a periodic component (never PRESC or FAST: l cannot be folded into the coordinates, the distance is
+//            sum_k l_k^2 sin^2(pi D_k / p_k)).  Its coordinate loop takes the phase from the difference, t = D_k / p_k with 1 / p_k
+//            staged beside l^2 (ipl); the radial function is the squared exponential's.  An instantiation of its own: the bodies
+//            of the other kinds compile exactly as they did without it.
+template <typename T, bool PRESC, bool CHECKED, bool MIRROR, bool FAST = false, bool PER = false>
 __device__ __forceinline__ void kb_body(const pg_covspec& spec, const T* xr, const T* xc, const T* l2, const T* sg2, T* tt, int d,
                                         int tr, int tc, int nr, int nc, int symmetric, int accumulate, T* __restrict__ K, long ldk,
-                                        int tid, const T* nrm_r = nullptr, const T* nrm_c = nullptr, const double* tab = nullptr) {
+                                        int tid, const T* nrm_r = nullptr, const T* nrm_c = nullptr, const double* tab = nullptr,
+                                        const T* ipl = nullptr) {
+    static_assert(!PER || (!PRESC && !FAST), "the periodic kind takes the general direct-difference body only");
     constexpr int VE = VecOf<T>::N, NVC = 4 / VE;   // vectors per row of the micro-tile
     typedef typename VecOf<T>::type vec_t;
     const int tx = tid & 15, ty = tid >> 4;
@@ -83,8 +93,31 @@ __device__ __forceinline__ void kb_body(const pg_covspec& spec, const T* xr, con
 #pragma unroll
                 for (int c = 0; c < 4; ++c) sq[r][c] = na[r] + nb[c];
         }
+        bool periodic = false;
+        if constexpr (PER) periodic = spec.kind[cp] == PG_KIND_PERIODIC;
+        if constexpr (PER) {
+            if (periodic) {
+                const T* ipc = ipl + cp * d;
+                for (int k = 0; k < d; ++k) {
+                    T a[4], b[4];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) a[r] = xr[k * KT + ty * 4 + r];
+#pragma unroll
+                    for (int v = 0; v < NVC; ++v) {
+                        const vec_t bv = *reinterpret_cast<const vec_t*>(xc + k * KT + v * (16 * VE) + tx * VE);
+#pragma unroll
+                        for (int e = 0; e < VE; ++e) b[v * VE + e] = bv[e];
+                    }
+                    const T w = lc[k], ip = ipc[k];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) sq[r][c] += w * per_sin2<T>((a[r] - b[c]) * ip);
+                }
+            }
+        }
 #pragma unroll 2
-        for (int k = 0; k < d; ++k) {      // (two coordinates' LDS reads in flight per trip)
+        for (int k = 0; k < (periodic ? 0 : d); ++k) {      // (two coordinates' LDS reads in flight per trip; a periodic component is done)
             T a[4], b[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) a[r] = xr[k * KT + ty * 4 + r];
@@ -131,7 +164,7 @@ __device__ __forceinline__ void kb_body(const pg_covspec& spec, const T* xr, con
                     for (int c = 0; c < 4; ++c) out[r][c] += kind_value<T, decltype(kind_c)::value>(s2, sq[r][c], sh, ish);
             };
             if (kind == PG_KIND_RQ) add(std::integral_constant<int, PG_KIND_RQ>{});
-            else if (kind == PG_KIND_RBF) add(std::integral_constant<int, PG_KIND_RBF>{});
+            else if (kind == PG_KIND_RBF || (PER && kind == PG_KIND_PERIODIC)) add(std::integral_constant<int, PG_KIND_RBF>{});
             else if (kind == PG_KIND_SQDIST) add(std::integral_constant<int, PG_KIND_SQDIST>{});
             else if (kind == PG_KIND_MATERN52) add(std::integral_constant<int, PG_KIND_MATERN52>{});
             else if (kind == PG_KIND_MATERN32) add(std::integral_constant<int, PG_KIND_MATERN32>{});
@@ -186,7 +219,8 @@ __device__ __forceinline__ void kb_body(const pg_covspec& spec, const T* xr, con
 // and the launch are paid once per strip, and the next tile's column points are fetched (global -> registers -> the other LDS
 // buffer) while the current tile is computed.  A tile's time was 7 us of staging latency, synchronisation and drain around 1 us of
 // arithmetic with four workgroups per CU to hide it (rocprof: 2.55 TB/s on the lower-only build); the strip hides it behind work.
-template <typename T, bool MIRROR, int NPF, bool FASTK = false>
+// PER: the spec holds a periodic component (kb_body): 1 / p_k staged behind everything else, the general body only.
+template <typename T, bool MIRROR, int NPF, bool FASTK = false, bool PER = false>
 __global__ __launch_bounds__(256) void pg_kbuild_kernel(pg_covspec spec, const double* __restrict__ hp,
                                                         const T* __restrict__ Xr, long ldr, int nr,
                                                         const T* __restrict__ Xc, long ldc, int nc, int d,
@@ -206,6 +240,7 @@ __global__ __launch_bounds__(256) void pg_kbuild_kernel(pg_covspec spec, const d
     T* tt = sg2 + 3 * PG_MAX_COMP + 2;  // MIRROR: [64][TLD] transposed tile
     T* nrm = tt + (MIRROR ? KT * TLD : 0);                      // fast path: -|x|^2 of the row points [64], of the column points [2][64]
     double* tab = reinterpret_cast<double*>(nrm + 3 * KT);      // fast path: sigma^2 2^(j/32) [32] (fp64 builds only)
+    T* ipl = reinterpret_cast<T*>(tab + 32);                    // PER: [ncomp][d] reciprocal periods (0 for the other kinds)
     constexpr bool fast = FASTK;                                // host: one squared-exponential component, fp64, no accumulate pass (presc = 2)
     const int tid = threadIdx.x;
     const double* scale = presc ? hp + spec.off[0] + 1 : nullptr;
@@ -243,6 +278,7 @@ __global__ __launch_bounds__(256) void pg_kbuild_kernel(pg_covspec spec, const d
         const int c = idx / d, k = idx % d;
         const double l = hp[spec.off[c] + 1 + k];
         l2[idx] = (T)(l * l);
+        if constexpr (PER) ipl[idx] = spec.kind[c] == PG_KIND_PERIODIC ? (T)(1.0 / hp[spec.off[c] + d + 1 + k]) : (T)0;
     }
     if (tid < spec.ncomp) {
         const double sg = hp[spec.off[tid]];
@@ -286,8 +322,8 @@ __global__ __launch_bounds__(256) void pg_kbuild_kernel(pg_covspec spec, const d
         for (int t = 0; t < ntile; ++t) {
             const int tc = tcs + t, cur = t & 1, nxt = cur ^ 1;
             if (t + 1 < ntile) load_cols(tc + 1);           // in flight while this tile is computed
-            kb_body<T, decltype(presc_c)::value, decltype(checked_c)::value, MIRROR, FASTK>(
-                spec, xr, xc + cur * KT * d, l2, sg2, tt, d, tr, tc, nr, nc, symmetric, accumulate, K, ldk, tid, nrm, nrm + KT + cur * KT, tab);
+            kb_body<T, decltype(presc_c)::value, decltype(checked_c)::value, MIRROR, FASTK, PER>(
+                spec, xr, xc + cur * KT * d, l2, sg2, tt, d, tr, tc, nr, nc, symmetric, accumulate, K, ldk, tid, nrm, nrm + KT + cur * KT, tab, ipl);
             if (t + 1 < ntile) {
                 store_cols(xc + nxt * KT * d);
                 __syncthreads();   // publishes the next tile's points; also orders this tile's reads of `tt` before the next one's writes
@@ -298,7 +334,8 @@ __global__ __launch_bounds__(256) void pg_kbuild_kernel(pg_covspec spec, const d
             }
         }
     };
-    if (FASTK || presc) { if (interior) walk(std::true_type{}, std::false_type{}); else walk(std::true_type{}, std::true_type{}); }
+    if constexpr (PER) { if (interior) walk(std::false_type{}, std::false_type{}); else walk(std::false_type{}, std::true_type{}); }
+    else if (FASTK || presc) { if (interior) walk(std::true_type{}, std::false_type{}); else walk(std::true_type{}, std::true_type{}); }
     else if constexpr (!FASTK) { if (interior) walk(std::false_type{}, std::false_type{}); else walk(std::false_type{}, std::true_type{}); }
 }
 
@@ -316,21 +353,23 @@ __global__ __launch_bounds__(256) void pg_kbuild_pad_kernel(T* __restrict__ K, l
     }
 }
 
-// LDS of pg_kbuild_kernel in bytes at dimension d (the fast body's norms and table are always counted)
-template <typename T> static constexpr size_t kb_lds_bytes(int d, bool mirror) {
-    return (size_t)(3 * KT * d + PG_MAX_COMP * d + 3 * PG_MAX_COMP + 2 + (mirror ? KT * TLD : 0) + 3 * KT) * sizeof(T) + 32 * sizeof(double);
+// LDS of pg_kbuild_kernel in bytes at dimension d (the fast body's norms and table are always counted; the reciprocal periods only
+// for a spec with a periodic component)
+template <typename T> static constexpr size_t kb_lds_bytes(int d, bool mirror, bool per = false) {
+    return (size_t)(3 * KT * d + PG_MAX_COMP * d + 3 * PG_MAX_COMP + 2 + (mirror ? KT * TLD : 0) + 3 * KT) * sizeof(T) + 32 * sizeof(double) +
+           (per ? (size_t)PG_MAX_COMP * d * sizeof(T) : 0);
 }
 
 // One instantiation of pg_kbuild_kernel: its dynamic-LDS limit once, then the launch.
-template <typename T, bool MIRROR, int NPF, bool FAST, typename... Args>
+template <typename T, bool MIRROR, int NPF, bool FAST, bool PER, typename... Args>
 static int kb_launch(dim3 grid, size_t lds, hipStream_t st, Args... args) {
     static bool attr_done = false;
     if (!attr_done) {   // large d passes the 64 KB a kernel gets without opting in (134 KB for the mirrored fp64 build at d = 64)
-        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_kbuild_kernel<T, MIRROR, NPF, FAST>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kb_lds_bytes<T>(PG_MAX_DIM, true)));
+        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_kbuild_kernel<T, MIRROR, NPF, FAST, PER>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kb_lds_bytes<T>(PG_MAX_DIM, true, PER)));
         attr_done = true;
     }
-    hipLaunchKernelGGL((pg_kbuild_kernel<T, MIRROR, NPF, FAST>), grid, dim3(256), lds, st, args...);
+    hipLaunchKernelGGL((pg_kbuild_kernel<T, MIRROR, NPF, FAST, PER>), grid, dim3(256), lds, st, args...);
     PG_CHECK(hipGetLastError());
     return 0;
 }
@@ -345,7 +384,9 @@ int pg_kbuild(hipStream_t st, const pg_covspec& spec, const double* hp, const T*
         return -2;
     }
     const bool mirror = symmetric && !lower_only;
-    const size_t lds = kb_lds_bytes<T>(d, mirror);
+    bool per = false;      // a periodic component: the general direct-difference body in its own instantiation, never PRESC / FAST / the matrix pipe
+    for (int c = 0; c < spec.ncomp; ++c) per = per || spec.kind[c] == PG_KIND_PERIODIC;
+    const size_t lds = kb_lds_bytes<T>(d, mirror, per);
     // columns [col0, col1) only (col1 <= 0: all): a lower-only symmetric build in two column windows lets the factorisation
     // start on the first panel while the rest is still being written (pg_potrf_t, BuildReq)
     if (col1 <= 0) { col0 = 0; col1 = cols_pad; }
@@ -378,7 +419,7 @@ int pg_kbuild(hipStream_t st, const pg_covspec& spec, const double* hp, const T*
     // one stationary component (the common Compose([SE, WN])): its inverse length scales go into the staged coordinates (presc = 1; in
     // fp64 (x l) - (x' l) rounds differently from l^2 (x - x')^2 in the last bit) ... and when that component is the squared
     // exponential, fp64 builds take the fast body (kb_body, FAST): presc = 2.  Several components: presc = 0
-    const int presc = spec.ncomp != 1 ? 0 : ((sizeof(T) == 8 && spec.kind[0] == PG_KIND_RBF && !accumulate) ? 2 : 1);
+    const int presc = (spec.ncomp != 1 || per) ? 0 : ((sizeof(T) == 8 && spec.kind[0] == PG_KIND_RBF && !accumulate) ? 2 : 1);
     // One stationary component, d <= 16, no accumulate pass: the distance on the matrix pipe (kmfma.hip).  PG_KB_MFMA = 0: never;
     // 1 (default): wherever the VALU bodies have no fast form -- d > 8, Matern-5/2 and -3/2, fp32; 2: also for the fp64 squared exponential at
     // d <= 8, which the fast body of round 3 serves at 0.63-0.66 of the HBM peak.
@@ -391,22 +432,25 @@ int pg_kbuild(hipStream_t st, const pg_covspec& spec, const double* hp, const T*
         return pg_kbuild_mfma<T>(st, spec, hp, Xr, ldr, nr, Xc, ldc, nc, d, symmetric, mirror ? 1 : 0, jitter, K, ldk, c0, c1, S, strips, nexp, eX,
                                  ehp, eK, eXr);
     const int npf = d <= 8 ? 2 : (d <= 16 ? 4 : 16);
-    // (mirror, npf, fast) -> kb_launch<T, MIRROR, NPF, FAST>; the fast body exists in fp64 only
-    auto go = [&](auto mirror_c, auto npf_c, auto fast_c) {
-        return kb_launch<T, decltype(mirror_c)::value, decltype(npf_c)::value, decltype(fast_c)::value>(
+    // (mirror, npf, fast, per) -> kb_launch<T, MIRROR, NPF, FAST, PER>; the fast body exists in fp64 only
+    auto go = [&](auto mirror_c, auto npf_c, auto fast_c, auto per_c) {
+        return kb_launch<T, decltype(mirror_c)::value, decltype(npf_c)::value, decltype(fast_c)::value, decltype(per_c)::value>(
             dim3((unsigned)strips, (unsigned)nexp), lds, st, spec, hp, Xr, ldr, nr, Xc, ldc, nc, d, symmetric, accumulate, jitter, K, ldk, c0, c1,
             presc, S, eX, ehp, eK, eXr);
     };
-    auto with_npf = [&](auto mirror_c, auto fast_c) {
-        if (npf == 2) return go(mirror_c, std::integral_constant<int, 2>{}, fast_c);
-        if (npf == 4) return go(mirror_c, std::integral_constant<int, 4>{}, fast_c);
-        return go(mirror_c, std::integral_constant<int, 16>{}, fast_c);
+    auto with_npf = [&](auto mirror_c, auto fast_c, auto per_c) {
+        if (npf == 2) return go(mirror_c, std::integral_constant<int, 2>{}, fast_c, per_c);
+        if (npf == 4) return go(mirror_c, std::integral_constant<int, 4>{}, fast_c, per_c);
+        return go(mirror_c, std::integral_constant<int, 16>{}, fast_c, per_c);
     };
-    auto with_mirror = [&](auto fast_c) { return mirror ? with_npf(std::true_type{}, fast_c) : with_npf(std::false_type{}, fast_c); };
+    auto with_mirror = [&](auto fast_c, auto per_c) {
+        return mirror ? with_npf(std::true_type{}, fast_c, per_c) : with_npf(std::false_type{}, fast_c, per_c);
+    };
+    if (per) return with_mirror(std::false_type{}, std::true_type{});
     if constexpr (sizeof(T) == 8) {
-        if (presc == 2) return with_mirror(std::true_type{});
+        if (presc == 2) return with_mirror(std::true_type{}, std::false_type{});
     }
-    return with_mirror(std::false_type{});
+    return with_mirror(std::false_type{}, std::false_type{});
 }
 template int pg_kbuild<double>(hipStream_t, const pg_covspec&, const double*, const double*, long, int,
                                const double*, long, int, int, int, int, int, double, double*, long, int, int, int, int, int, long, long, long, long);
@@ -430,6 +474,24 @@ __global__ __launch_bounds__(256) void pg_kgrad_kernel(pg_covspec spec, const do
     for (int cp = 0; cp < spec.ncomp; ++cp) {
         const int o = spec.off[cp];
         const double sg = hp[o];
+        if (spec.kind[cp] == PG_KIND_PERIODIC) {      // sigma, the length-scale slabs from sin^2, the period slabs o + d + 1 .. o + 2 d
+            T sp = (T)0;
+            for (int k = 0; k < d; ++k) {
+                const double l = hp[o + 1 + k];
+                sp += (T)(l * l) * per_sin2<T>((xi[k] - xj[k]) * (T)(1.0 / hp[o + d + 1 + k]));
+            }
+            const T kp = (T)(sg * sg) * pg_exp(-sp);
+            dK[(long)o * slab + e] = kp * (T)(2.0 / sg);
+            for (int k = 0; k < d; ++k) {
+                const double l = hp[o + 1 + k], ip = 1.0 / hp[o + d + 1 + k];
+                const T t = (xi[k] - xj[k]) * (T)ip;
+                T s2, s2w;
+                per_terms<T>(t, s2, s2w);
+                dK[(long)(o + 1 + k) * slab + e] = (T)(-2.0 * l) * s2 * kp;
+                dK[(long)(o + d + 1 + k) * slab + e] = kp * (T)(l * l * PG_PI * ip) * s2w * t;
+            }
+            continue;
+        }
         T sq = (T)0;
         for (int k = 0; k < d; ++k) {
             const double l = hp[o + 1 + k];
@@ -519,8 +581,12 @@ template int pg_centres<float>(hipStream_t, const float*, long, int, const float
 // cross-wave reduction and the partial-sum row are paid once per strip instead of once per 64 x 64 tile.  Measured at
 // N = 16384, D = 8 (contraction + reduce): one tile per workgroup 873 + 120 us, strips of 4 826 + 33 us, strips of 16
 // 1061 + 11 us (imbalance); keeping the column point and squared differences in registers (138 VGPRs) 1179 us.
+// PER: the spec holds a periodic component.  Its element takes sin^2(pi D_k / p_k) where the others take D_k^2 (length-scale entries)
+// and sums sin(2 pi D_k / p_k) D_k / p_k for its d period entries; the fold's slots of a child follow its block, kind_nparam wide:
+// sigma, l_1..l_DMAX, then whatever the kind keeps behind them (the rational quadratic's shape, the periods) from slot DMAX + 1 on.
+// An instantiation of its own: the other kinds' kernels compile exactly as they did without it.
 #define GCH 4
-template <typename T, int DMAX>
+template <typename T, int DMAX, bool PER = false>
 __global__ __launch_bounds__(256) void pg_grad_kernel(pg_covspec spec, const double* __restrict__ hp,
                                                       const T* __restrict__ X, long ldx, int n, int d,
                                                       const T* __restrict__ Kinv, long ldk,
@@ -537,10 +603,12 @@ __global__ __launch_bounds__(256) void pg_grad_kernel(pg_covspec spec, const dou
         return;
     }
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    double* red = reinterpret_cast<double*>(smem_raw);             // [4 waves][DMAX + 2]: sigma, l_1..l_DMAX, the shape
-    T* xr = reinterpret_cast<T*>(red + 4 * (DMAX + 2));             // [DMAX][64], zero for k >= d
+    constexpr int RS = kind_nparam(PER ? PG_KIND_PERIODIC : PG_KIND_RQ, DMAX);      // slots of the widest block this kernel folds
+    double* red = reinterpret_cast<double*>(smem_raw);             // [4 waves][RS]: sigma, l_1..l_DMAX, the shape | the periods
+    T* xr = reinterpret_cast<T*>(red + 4 * RS);                     // [DMAX][64], zero for k >= d
     T* xc = xr + KT * DMAX;                                         // two buffers [DMAX][64]
     T* l2 = xc + 2 * KT * DMAX;                                     // [ncomp][DMAX], zero for k >= d
+    T* ipl = l2 + PG_MAX_COMP * DMAX;                               // PER: [ncomp][DMAX] reciprocal periods, zero for k >= d / other kinds
     for (int idx = tid; idx < KT * DMAX; idx += 256) {
         const int p = idx / DMAX, k = idx % DMAX;
         const int gr = tr * KT + p;
@@ -550,6 +618,7 @@ __global__ __launch_bounds__(256) void pg_grad_kernel(pg_covspec spec, const dou
         const int c = idx / DMAX, k = idx % DMAX;
         const double l = (k < d) ? hp[spec.off[c] + 1 + k] : 0.0;
         l2[idx] = (T)(l * l);
+        if constexpr (PER) ipl[idx] = (k < d && spec.kind[c] == PG_KIND_PERIODIC) ? (T)(1.0 / hp[spec.off[c] + d + 1 + k]) : (T)0;
     }
     for (int idx = tid; idx < nhp; idx += 256) part[(long)blk * nhp + idx] = 0.0;
 
@@ -570,6 +639,9 @@ __global__ __launch_bounds__(256) void pg_grad_kernel(pg_covspec spec, const dou
         double acc[DMAX + 1];
 #pragma unroll
         for (int k = 0; k <= DMAX; ++k) acc[k] = 0.0;
+        double accp[PER ? DMAX : 1];                  // ... the periodic kind's period entries, sum W K sin(2 pi t_k) t_k
+#pragma unroll
+        for (int k = 0; k < (PER ? DMAX : 1); ++k) accp[k] = 0.0;
         for (int tc = c0; tc < c1; ++tc, ++it) {
             T* xb = xc + (it & 1) * KT * DMAX;
             for (int idx = tid; idx < KT * DMAX; idx += 256) {
@@ -590,6 +662,25 @@ __global__ __launch_bounds__(256) void pg_grad_kernel(pg_covspec spec, const dou
                     if (gj < gi) w *= 2.0; else if (cp == 0) tr_w += w;
                 }
                 if (!have) continue;
+                if constexpr (PER) {
+                    if (kind == PG_KIND_PERIODIC) {      // (padding coordinates: l^2 = 1 / p = 0, so t = 0 and both terms vanish)
+                        const T* ipc = ipl + cp * DMAX;
+                        T sp = (T)0;
+#pragma unroll
+                        for (int k = 0; k < DMAX; ++k) sp += lc[k] * per_sin2<T>((xr[k * KT + row] - xb[k * KT + lane]) * ipc[k]);
+                        const double wk = w * (double)kind_value<T, PG_KIND_RBF>(sig2, sp);
+                        acc[0] += wk;
+#pragma unroll
+                        for (int k = 0; k < DMAX; ++k) {
+                            const T t = (xr[k * KT + row] - xb[k * KT + lane]) * ipc[k];
+                            T s2, s2w;
+                            per_terms<T>(t, s2, s2w);
+                            acc[1 + k] += wk * (double)s2;
+                            accp[k] += wk * (double)s2w * (double)t;
+                        }
+                        continue;
+                    }
+                }
                 T sq = (T)0;
 #pragma unroll
                 for (int k = 0; k < DMAX; ++k) {
@@ -620,27 +711,36 @@ __global__ __launch_bounds__(256) void pg_grad_kernel(pg_covspec spec, const dou
 #pragma unroll
             for (int k = 0; k <= DMAX; ++k) {
                 const double s = wave_sum(acc[k]);
-                if (lane == 0) red[wave * (DMAX + 2) + k] = s;
+                if (lane == 0) red[wave * RS + k] = s;
             }
             if (kind == PG_KIND_RQ) {
                 const double s = wave_sum(accf);
-                if (lane == 0) red[wave * (DMAX + 2) + DMAX + 1] = s;
+                if (lane == 0) red[wave * RS + DMAX + 1] = s;
+            }
+            if constexpr (PER) {
+                if (kind == PG_KIND_PERIODIC) {
+#pragma unroll
+                    for (int k = 0; k < DMAX; ++k) {
+                        const double s = wave_sum(accp[k]);
+                        if (lane == 0) red[wave * RS + DMAX + 1 + k] = s;
+                    }
+                }
             }
             __syncthreads();
-            if (tid < kind_nparam(kind, d)) {      // the child's block: sigma, l_1..l_d (slots 0..d), the shape (slot DMAX + 1)
-                const int q = tid <= d ? tid : DMAX + 1;
-                part[(long)blk * nhp + o + tid] = red[q] + red[(DMAX + 2) + q] + red[2 * (DMAX + 2) + q] + red[3 * (DMAX + 2) + q];
+            if (tid < kind_nparam(kind, d)) {      // the child's block: sigma, l_1..l_d (slots 0..d), what sits behind them (slots DMAX + 1 ..)
+                const int q = tid <= d ? tid : DMAX + 1 + (tid - d - 1);
+                part[(long)blk * nhp + o + tid] = red[q] + red[RS + q] + red[2 * RS + q] + red[3 * RS + q];
             }
             __syncthreads();
         }
     }
     {
         const double s = wave_sum(tr_w);
-        if (lane == 0) red[wave * (DMAX + 2)] = s;
+        if (lane == 0) red[wave * RS] = s;
         __syncthreads();
         if (tid < spec.nnoise)
             part[(long)blk * nhp + spec.noise_off[tid]] =
-                red[0] + red[DMAX + 2] + red[2 * (DMAX + 2)] + red[3 * (DMAX + 2)];
+                red[0] + red[RS] + red[2 * RS] + red[3 * RS];
     }
 }
 
@@ -673,6 +773,10 @@ __global__ __launch_bounds__(256) void pg_grad_reduce_kernel(pg_covspec spec, co
             } else if (spec.kind[c] == PG_KIND_RQ && p == o + d + 1) {
                 scale = 0.5 * 2.0 * hp[p];      // dK/dalpha = 2 alpha K fs (the partial sums hold sum W K fs)
                 mine = true;
+            } else if (spec.kind[c] == PG_KIND_PERIODIC && p > o + d && p <= o + 2 * d) {
+                const double l = hp[p - d];     // dK/dp_k = K l_k^2 sin(2 pi t_k) pi t_k / p_k (the partial sums hold sum W K sin(2 pi t_k) t_k)
+                scale = 0.5 * l * l * PG_PI / hp[p];
+                mine = true;
             }
         }
         for (int i = 0; i < spec.nnoise; ++i)
@@ -681,17 +785,18 @@ __global__ __launch_bounds__(256) void pg_grad_reduce_kernel(pg_covspec spec, co
     }
 }
 
-template <typename T, int DMAX>
+template <typename T, int DMAX, bool PER>
 static int launch_grad(hipStream_t st, const pg_covspec& spec, const double* hp, const T* X, long ldx, int n,
                        int d, const T* Kinv, long ldk, const T* alpha, double* part, int nhp, int tiles, const GradBatch& gb, int nexp) {
-    const size_t lds = (size_t)(3 * KT * DMAX + PG_MAX_COMP * DMAX) * sizeof(T) + 4 * (DMAX + 2) * sizeof(double);
+    const size_t lds = (size_t)(3 * KT * DMAX + (PER ? 2 : 1) * PG_MAX_COMP * DMAX) * sizeof(T) +
+                       4 * kind_nparam(PER ? PG_KIND_PERIODIC : PG_KIND_RQ, DMAX) * sizeof(double);
     static bool attr_done = false;
     if (!attr_done) {   // d > 32 needs more than the 64 KB a kernel gets without opting in
-        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_grad_kernel<T, DMAX>),
+        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_grad_kernel<T, DMAX, PER>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_done = true;
     }
-    hipLaunchKernelGGL((pg_grad_kernel<T, DMAX>), dim3((tiles + GCH - 1) / GCH, tiles, nexp), dim3(256), lds, st, spec, hp, X, ldx,
+    hipLaunchKernelGGL((pg_grad_kernel<T, DMAX, PER>), dim3((tiles + GCH - 1) / GCH, tiles, nexp), dim3(256), lds, st, spec, hp, X, ldx,
                        n, d, Kinv, ldk, alpha, part, nhp, gb);
     PG_CHECK(hipGetLastError());
     return 0;
@@ -719,12 +824,18 @@ int pg_nlml_grad_t(hipStream_t st, const pg_covspec& spec, const double* hp, con
         PG_CHECK(hipGetLastError());
         return 0;
     }
-    if (d <= 4) rc = launch_grad<T, 4>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
-    else if (d <= 8) rc = launch_grad<T, 8>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
-    else if (d <= 16) rc = launch_grad<T, 16>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
-    else if (d <= 32) rc = launch_grad<T, 32>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
-    else if (d <= 64) rc = launch_grad<T, 64>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
-    else { pg_set_error("pg_nlml_grad: d=%d > %d", d, PG_MAX_DIM); return -2; }
+    bool per = false;      // a periodic component: pg_grad_kernel's own instantiation (never the matrix pipe: the whitelist above)
+    for (int c = 0; c < spec.ncomp; ++c) per = per || spec.kind[c] == PG_KIND_PERIODIC;
+    auto go = [&](auto per_c) {
+        constexpr bool P = decltype(per_c)::value;
+        if (d <= 4) return launch_grad<T, 4, P>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
+        if (d <= 8) return launch_grad<T, 8, P>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
+        if (d <= 16) return launch_grad<T, 16, P>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
+        if (d <= 32) return launch_grad<T, 32, P>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
+        return launch_grad<T, 64, P>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
+    };
+    if (d > PG_MAX_DIM) { pg_set_error("pg_nlml_grad: d=%d > %d", d, PG_MAX_DIM); return -2; }
+    rc = per ? go(std::true_type{}) : go(std::false_type{});
     if (rc) return rc;
     hipLaunchKernelGGL(pg_grad_reduce_kernel, dim3(nhp, 1, nexp), dim3(256), 0, st, spec, hp, work, tiles * ((tiles + GCH - 1) / GCH), nhp,
                        d, grad, 0, gb);

@@ -76,17 +76,92 @@ __device__ __forceinline__ double pg_sqrt_pos(double x) {
     return r;
 }
 
-// Half the factor `coef` of the length-scale derivative dK/dl_k = coef base l_k D_k^2, per stationary kind (base: see kind_eval)
+// sin(pi t) and cos(pi t) for the periodic kernel: branch-free, r = t - rint(t) (exact: |r| <= 1/2, odd in t, so sin^2 is exactly
+// even in the difference it came from), then the Taylor polynomials of sin(pi r) = r S(r^2) and cos(pi r) = C(r^2) with the powers of
+// pi folded into the coefficients -- no product pi * r is ever rounded.  fp64: S to r^21 and C to r^22, truncation (pi/2)^23 / 23! =
+// 1.3e-18 and (pi/2)^24 / 24! = 8e-20; fp32: S to r^13 and C to r^14 (7e-10, 7e-11).  No other argument reduction is needed, so the
+// n^2 d evaluations of a build never meet the device library's large-argument path.  A NaN stays a NaN, an infinite t (a period of 0)
+// becomes one (inf - inf).  Measured against a 50-digit evaluation over t in [-40, 40]: DESIGN.md 4.9b.
+#define PG_PI 3.14159265358979323846
+__device__ __forceinline__ void pg_sincospi(double t, double* s, double* c) {
+    const double r = t - __builtin_rint(t);
+    const double z = r * r;
+    double p = 5.392664662608129e-10;                    // pi^21 / 21!
+    p = __builtin_fma(p, z, -2.2948428997269873e-08);    // -pi^19 / 19!
+    p = __builtin_fma(p, z, 7.952054001475513e-07);      // pi^17 / 17!
+    p = __builtin_fma(p, z, -2.1915353447830217e-05);    // -pi^15 / 15!
+    p = __builtin_fma(p, z, 4.6630280576761255e-04);     // pi^13 / 13!
+    p = __builtin_fma(p, z, -7.3704309457143504e-03);    // -pi^11 / 11!
+    p = __builtin_fma(p, z, 8.214588661112823e-02);      // pi^9 / 9!
+    p = __builtin_fma(p, z, -5.992645293207921e-01);     // -pi^7 / 7!
+    p = __builtin_fma(p, z, 2.5501640398773455);         // pi^5 / 5!
+    p = __builtin_fma(p, z, -5.16771278004997);          // -pi^3 / 3!
+    p = __builtin_fma(p, z, 3.141592653589793);          // pi
+    *s = r * p;
+    double q = -7.700707130601354e-11;                   // -pi^22 / 22!
+    q = __builtin_fma(q, z, 3.604730797462501e-09);      // pi^20 / 20!
+    q = __builtin_fma(q, z, -1.3878952462213771e-07);    // -pi^18 / 18!
+    q = __builtin_fma(q, z, 4.303069587032947e-06);      // pi^16 / 16!
+    q = __builtin_fma(q, z, -1.046381049248457e-04);     // -pi^14 / 14!
+    q = __builtin_fma(q, z, 1.9295743094039231e-03);     // pi^12 / 12!
+    q = __builtin_fma(q, z, -2.580689139001406e-02);     // -pi^10 / 10!
+    q = __builtin_fma(q, z, 2.353306303588932e-01);      // pi^8 / 8!
+    q = __builtin_fma(q, z, -1.3352627688545895);        // -pi^6 / 6!
+    q = __builtin_fma(q, z, 4.0587121264167685);         // pi^4 / 4!
+    q = __builtin_fma(q, z, -4.934802200544679);         // -pi^2 / 2!
+    *c = __builtin_fma(q, z, 1.0);
+}
+__device__ __forceinline__ void pg_sincospi(float t, float* s, float* c) {
+    const float r = t - __builtin_rintf(t);
+    const float z = r * r;
+    float p = 4.6630280576761255e-04f;                   // pi^13 / 13!
+    p = __builtin_fmaf(p, z, -7.3704309457143504e-03f);
+    p = __builtin_fmaf(p, z, 8.214588661112823e-02f);
+    p = __builtin_fmaf(p, z, -5.992645293207921e-01f);
+    p = __builtin_fmaf(p, z, 2.5501640398773455f);
+    p = __builtin_fmaf(p, z, -5.16771278004997f);
+    p = __builtin_fmaf(p, z, 3.141592653589793f);
+    *s = r * p;
+    float q = -1.046381049248457e-04f;                   // -pi^14 / 14!
+    q = __builtin_fmaf(q, z, 1.9295743094039231e-03f);
+    q = __builtin_fmaf(q, z, -2.580689139001406e-02f);
+    q = __builtin_fmaf(q, z, 2.353306303588932e-01f);
+    q = __builtin_fmaf(q, z, -1.3352627688545895f);
+    q = __builtin_fmaf(q, z, 4.0587121264167685f);
+    q = __builtin_fmaf(q, z, -4.934802200544679f);
+    *c = __builtin_fmaf(q, z, 1.0f);
+}
+
+// Half the factor `coef` of the length-scale derivative dK/dl_k = coef base l_k D_k^2, per stationary kind (base: see kind_eval).  The
+// periodic kind has sin^2(pi D_k / p_k) where the others have D_k^2: dK/dl_k = -2 K l_k s_k^2, the squared exponential's factor.
 __device__ __forceinline__ double kind_hcoef(int kind) {
-    if (kind == PG_KIND_RBF || kind == PG_KIND_RQ) return -1.0;
+    if (kind == PG_KIND_RBF || kind == PG_KIND_RQ || kind == PG_KIND_PERIODIC) return -1.0;
     if (kind == PG_KIND_MATERN52) return 0.5 * -(5.0 / 3.0);
     if (kind == PG_KIND_MATERN32) return -1.5;
     return -0.5;                               // PG_KIND_MATERN12
 }
 
 // Hyper-parameters of one stationary child of this kind at dimension d: [sigma, l_1..l_d], and for the rational quadratic its shape
-// alpha behind them (at off + d + 1).  Everything that walks a child's block asks here instead of assuming d + 1.
-__host__ __device__ __forceinline__ int kind_nparam(int kind, int d) { return kind == PG_KIND_RQ ? d + 2 : d + 1; }
+// alpha behind them (at off + d + 1), for the periodic kind its d periods there (off + d + 1 .. off + 2 d).  Everything that walks a
+// child's block asks here instead of assuming d + 1.
+__host__ __device__ constexpr int kind_nparam(int kind, int d) {
+    return kind == PG_KIND_PERIODIC ? 2 * d + 1 : (kind == PG_KIND_RQ ? d + 2 : d + 1);
+}
+// The periodic kind's terms of one coordinate pair from t = D_k / p_k:  s2 = sin^2(pi t)  (the scaled distance is sum_k l_k^2 s2_k and
+// K = sigma^2 exp(-sq): the squared exponential's radial function),  s2w = sin(2 pi t) = 2 sin cos  (the period and test-point derivatives:
+// dK/dp_k = K l_k^2 s2w pi t / p_k,  dK/dx*_k = -K l_k^2 s2w pi / p_k).  The phase comes from the DIFFERENCE: the warped-point form
+// (the squared exponential on (l/2) [cos, sin](2 pi x / p)) takes the phase of the coordinate and loses |x| / p ulps.
+template <typename T> __device__ __forceinline__ void per_terms(T t, T& s2, T& s2w) {
+    T s, c;
+    pg_sincospi(t, &s, &c);
+    s2 = s * s;
+    s2w = (T)2 * s * c;
+}
+template <typename T> __device__ __forceinline__ T per_sin2(T t) {
+    T s2, s2w;
+    per_terms(t, s2, s2w);
+    return s2;
+}
 // The squared shape a = alpha^2 of component c (0 for the kinds without one: their blocks end at l_d and hp[off + d + 1] is not theirs)
 __device__ __forceinline__ double kind_shape2(const pg_covspec& spec, const double* hp, int c, int d) {
     if (spec.kind[c] != PG_KIND_RQ) return 0.0;

@@ -17,7 +17,9 @@
 //   * the squared distance is formed in the model's dtype as the covariance build forms it; everything downstream is fp64;
 //   * Matern-1/2 has a cusp at r = 0: matern_val's base is 0 there (the derivative's limit along any direction is bounded, its sign is
 //     not), so a test point on a training point contributes nothing for that pair;
-//   * a NaN coordinate of a test point reaches that point's row only (pg_exp keeps a NaN, matern_val's selects are NaN-transparent).
+//   * a NaN coordinate of a test point reaches that point's row only (pg_exp keeps a NaN, matern_val's selects are NaN-transparent);
+//   * the periodic kind has dk/dx*_pk = -K l_k^2 sin(2 pi D_k / p_k) pi / p_k: the same contraction with sin(2 pi t_k) pi / (2 p_k) in
+//     the place of D_k and K as `base`, the phase taken from the difference (per_terms, kfun.h); 1 / p_k is staged beside l^2.
 #include "kbuild.h"
 #include "kfun.h"
 
@@ -55,6 +57,7 @@ __global__ __launch_bounds__(256) void pg_xgrad_kernel(pg_covspec spec, const do
     T* l2s = xrs + (HOLD ? 0 : XT * (DMAX + 1));              // [ncomp][DMAX] squared inverse length scales, zero beyond d
     T* us = l2s + PG_MAX_COMP * DMAX;                         // [64]
     T* bs = us + XT;                                          // [64][BLD]: bs[p][i] = W of test point p, training point i
+    T* ips = bs + XT * BLD;                                   // [ncomp][DMAX] reciprocal periods of the periodic children, zero otherwise
 
     const int p = row0 + lane;
     T xr[HOLD ? DMAX : 1];
@@ -71,6 +74,7 @@ __global__ __launch_bounds__(256) void pg_xgrad_kernel(pg_covspec spec, const do
         const int c = idx / DMAX, k = idx % DMAX;
         const double l = (k < d) ? hp[spec.off[c] + 1 + k] : 0.0;
         l2s[idx] = (T)(l * l);
+        ips[idx] = (k < d && spec.kind[c] == PG_KIND_PERIODIC) ? (T)(1.0 / hp[spec.off[c] + d + 1 + k]) : (T)0;
     }
 
     for (int k0 = 0; k0 < (HOLD ? 1 : d); k0 += KC) {
@@ -109,6 +113,30 @@ __global__ __launch_bounds__(256) void pg_xgrad_kernel(pg_covspec spec, const do
                     }
                 }
                 __syncthreads();
+                if (kind == PG_KIND_PERIODIC) {
+                    const T* ipc = ips + cp * DMAX;
+                    for (int j = 0; j < 16; ++j) {
+                        const int c = wave * 16 + j;
+                        const T* zc = xc + c * DMAX;
+                        T sq = (T)0;
+#pragma unroll
+                        for (int k = 0; k < DMAX; ++k)
+                            sq += lc[k] * per_sin2<T>(((HOLD ? xr[k] : xrs[lane * (DMAX + 1) + k]) - zc[k]) * ipc[k]);
+                        const double f = f2 * (double)(sig2 * pg_exp(-sq));
+                        const double wu = HU ? f * (double)us[c] : 0.0;
+                        const double wb = HB ? f * (double)bs[lane * BLD + c] : 0.0;
+#pragma unroll
+                        for (int kk = 0; kk < KC; ++kk) {
+                            const int k = k0 + kk;
+                            T s2, s2w;
+                            per_terms<T>(((HOLD ? xr[HOLD ? kk : 0] : xrs[lane * (DMAX + 1) + k]) - zc[k]) * ipc[k], s2, s2w);
+                            const double t = (double)lc[k] * (double)s2w * (0.5 * PG_PI) * (double)ipc[k];
+                            if (HU) au[kk] += wu * t;
+                            if (HB) ab[kk] += wb * t;
+                        }
+                    }
+                    continue;
+                }
 #pragma unroll 2
                 for (int j = 0; j < 16; ++j) {
                     const int c = wave * 16 + j;
@@ -200,7 +228,7 @@ static int launch_xgrad(hipStream_t st, const pg_covspec& spec, const double* hp
                         const XgradBatch& xb, int nexp) {
     constexpr int KC = DMAX <= 16 ? DMAX : 16;
     const size_t lds = (size_t)4 * KC * XT * sizeof(double) +
-                       (size_t)(XT * DMAX + (DMAX <= 16 ? 0 : XT * (DMAX + 1)) + PG_MAX_COMP * DMAX + XT + XT * BLD) * sizeof(T);
+                       (size_t)(XT * DMAX + (DMAX <= 16 ? 0 : XT * (DMAX + 1)) + 2 * PG_MAX_COMP * DMAX + XT + XT * BLD) * sizeof(T);
     static bool attr_done = false;
     if (!attr_done) {   // d > 16 in fp64 passes the 64 KB a kernel gets without opting in
         PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_xgrad_kernel<T, DMAX, HU, HB>),

@@ -17,9 +17,11 @@ for d in (8, 16):
     kinv = torch.randn(n, n, device="cuda", dtype=torch.float64, generator=g)
     alpha = torch.randn(n, device="cuda", dtype=torch.float64, generator=g)
     k = ops.empty(n, n)
-    for kind, name in ((0, "rbf"), (3, "m32"), (6, "rq")):      # (the rational quadratic's block is one wider: its shape alpha)
-        w = d + 2 if kind == 6 else d + 1
-        hp = torch.tensor([1.0] + [0.7] * d + ([1.0] if kind == 6 else []) + [0.1], dtype=torch.float64).cuda()
+    # (the rational quadratic's block is one wider: its shape alpha; the periodic kind's is d wider: its periods.  Matern-1/2 and the
+    # periodic kind share the direct-difference VALU route: their difference is what the per-coordinate sine costs)
+    for kind, name in ((0, "rbf"), (3, "m32"), (6, "rq"), (4, "m12"), (8, "per")):
+        w = d + 2 if kind == 6 else (2 * d + 1 if kind == 8 else d + 1)
+        hp = torch.tensor([1.0] + [0.7] * d + ([1.0] if kind == 6 else []) + ([0.3] * d if kind == 8 else []) + [0.1], dtype=torch.float64).cuda()
         spec = make_spec([kind], [0], [w])
         grad = ops.zeros(w + 1); work = ops.empty(ops.nlml_grad_worksize(n, w + 1))
         t = ev(lambda: ops.nlml_grad(spec, hp, x, n, kinv, alpha, grad, work))

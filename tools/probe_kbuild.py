@@ -13,9 +13,11 @@ k = ops.empty(n, n)
 for d in (8, 2, 16):
     rng = np.random.default_rng(d)
     x = torch.from_numpy(rng.random((n, d))).cuda()
-    for kind, name in ((0, "rbf"), (3, "m32"), (6, "rq")):      # (the rational quadratic's block is one wider: its shape alpha)
-        w = d + 2 if kind == 6 else d + 1
-        hp = torch.tensor([1.0] * w + [0.1], dtype=torch.float64).cuda()
+    # (the rational quadratic's block is one wider: its shape alpha; the periodic kind's is d wider: its periods.  Matern-1/2 and the
+    # periodic kind share the direct-difference VALU route: their difference is what the per-coordinate sine costs)
+    for kind, name in ((0, "rbf"), (3, "m32"), (6, "rq"), (4, "m12"), (8, "per")):
+        w = d + 2 if kind == 6 else (2 * d + 1 if kind == 8 else d + 1)
+        hp = torch.tensor([1.0] * (d + 1) + ([0.3] * d if kind == 8 else [1.0] * (w - d - 1)) + [0.1], dtype=torch.float64).cuda()
         spec = make_spec([kind], [0], [w])
         tl = ev(lambda: ops.kernel_build(spec, hp, x, None, k, lower_only=True, jitter=1e-7))
         tf = ev(lambda: ops.kernel_build(spec, hp, x, None, k, jitter=1e-7))
