@@ -36,6 +36,12 @@ loo_mean, loo_var = gp.loo_predict()   # leave-one-out check of the fit on its o
 print("LOO standardised residuals: std %.3f (1 = calibrated), worst %.1f sigma" % (
     float(((y - loo_mean) / loo_var.sqrt()).std()), float(((y - loo_mean) / loo_var.sqrt()).abs().max())))
 
+# ---- the locally periodic kernel, SE x Periodic (a seasonal shape that drifts), as one term of a sum: hp = the children's blocks in order
+lp = PyGPR.Compose([PyGPR.Product([PyGPR.Squared_exponential(), PyGPR.Periodic()]), PyGPR.White_noise()])
+gp_lp = PyGPR.Exact_GP(x, y, lp)
+gp_lp.set_params(torch.tensor([1.0] + [0.5] * d + [1.0] + [1.0] * d + [2.0] * d + [0.1], dtype=torch.float64))
+print("locally periodic kernel: NLML %.4f" % float(PyGPR.MLE(gp_lp).loss(gp_lp.params.numpy())))
+
 # ---- grBCM committee: 4 local experts + a global communication set, shared hyper-parameters
 nc, nls, ng = 4, 400, 200
 xl, yl = x[: nc * nls].reshape(nc, nls, d), y[: nc * nls].reshape(nc, nls)

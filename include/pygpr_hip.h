@@ -52,14 +52,21 @@ extern "C" {
                               sigma^2 exp(-sum_k l_k^2 sin^2(pi (x_k - x'_k) / p_k)); never PG_KIND_SQDIST's stand-in */
 #define PG_MAX_COMP 4
 #define PG_MAX_DIM 64
+#define PG_SPEC_PRODUCT 0x100 /* or-ed into pg_covspec.ncomp: the spec's 1..PG_MAX_COMP stationary components are MULTIPLIED into one
+                                 term (Product([...]): the locally periodic kernel is SE x Periodic); the noise terms are still added */
 
 typedef struct pg_ctx* pg_handle;
 
 /* A Compose([...]) of up to PG_MAX_COMP stationary kernels plus white-noise terms (covar.py:28-81).  A longer Compose is
  * evaluated in passes of PG_MAX_COMP children (pg_kernel_build's `accumulate`; the gradient entries of different
- * children are disjoint, so pg_nlml_grad / pg_kernel_grad_build passes simply write different entries). */
+ * children are disjoint, so pg_nlml_grad / pg_kernel_grad_build passes simply write different entries).
+ * With PG_SPEC_PRODUCT in ncomp the stationary components are the factors of ONE product term, K = prod_c k_c (+ the noise on the
+ * diagonal of a symmetric build): dK/dtheta_{c,j} = (prod_{c' != c} k_c') dk_c/dtheta_{c,j}, every factor keeping its own block and
+ * its own sigma; the others' product is formed explicitly, never as K / k_c, so a factor that underflows gives 0, not NaN.  A sum
+ * with further terms is evaluated in passes, one flagged spec per product.  A flagged spec holds 1..PG_MAX_COMP components and
+ * never PG_KIND_SQDIST; the struct itself is unchanged. */
 typedef struct pg_covspec {
-    int ncomp;                  /* stationary components                                     */
+    int ncomp;                  /* stationary components (| PG_SPEC_PRODUCT: multiplied)     */
     int kind[PG_MAX_COMP];      /* PG_KIND_*                                                 */
     int off[PG_MAX_COMP];       /* index of component c's sigma inside hp: [sigma, l_1..l_d], */
                                 /* and for PG_KIND_RQ its shape alpha at off[c] + d + 1,      */

@@ -18,6 +18,8 @@ PG_KIND_RBF, PG_KIND_MATERN52, PG_KIND_SQDIST, PG_KIND_MATERN32, PG_KIND_MATERN1
 PG_KIND_RQ = 6      # (5 is unassigned: the library refuses it)
 PG_KIND_PERIODIC = 8    # hp = [sigma, l_1..l_d, p_1..p_d] (7, like 5, is unassigned: the library refuses it)
 PG_MAX_COMP, PG_MAX_DIM = 4, 64
+# or-ed into CovSpec.ncomp: the stationary components are multiplied into one term (read from the header: the C side owns the value)
+PG_SPEC_PRODUCT = int(re.search(r"#define\s+PG_SPEC_PRODUCT\s+(0[xX][0-9a-fA-F]+|\d+)", open(HEADER).read()).group(1), 0)
 PAD = 256  # every dimension given to the O(n^3) entry points is a multiple of this
 
 GEMM_NT, GEMM_NT_RP, GEMM_NN, GEMM_TN, GEMM_TT, GEMM_NT_64, GEMM_NT_64x128, GEMM_NT_32x64, GEMM_NT_32x128, GEMM_TT_64, GEMM_NT_32x32 = 0, 1, 2, 3, 5, 6, 7, 8, 9, 10, 11

@@ -621,12 +621,15 @@ def make_specs(kinds, offs, noise_offs):
     return [make_spec(kinds[i * q: (i + 1) * q], offs[i * q: (i + 1) * q], noise_offs[i * q: (i + 1) * q]) for i in range(npass)]
 
 
-def make_spec(kinds, offs, noise_offs):
+def make_spec(kinds, offs, noise_offs, product=False):
+    """One pg_covspec; product: the stationary components are the factors of one product term (PG_SPEC_PRODUCT in ncomp)."""
     s = CovSpec()
     if len(kinds) > _lib.PG_MAX_COMP or len(noise_offs) > _lib.PG_MAX_COMP:
         raise ValueError("one pg_covspec holds at most %d stationary and %d noise kernels (make_specs splits a longer Compose)"
                          % (_lib.PG_MAX_COMP, _lib.PG_MAX_COMP))
-    s.ncomp = len(kinds)
+    if product and not kinds:
+        raise ValueError("a product spec needs at least one factor")
+    s.ncomp = len(kinds) | (_lib.PG_SPEC_PRODUCT if product else 0)
     for i, (k, o) in enumerate(zip(kinds, offs)):
         s.kind[i], s.off[i] = k, o
     s.nnoise = len(noise_offs)

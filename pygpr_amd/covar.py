@@ -13,6 +13,10 @@ Same names, hyper-parameter layout and shapes as the reference:
                            scaled squared distance sq; the squared exponential as alpha grows.
   * `Periodic`             NEW, hp = [sigma, l_1..l_d, p_1..p_d] (2 d + 1 values), one period per dimension:
                            sigma^2 exp(-sum_k l_k^2 sin^2(pi (x_k - x'_k) / p_k)); the phase is taken from the difference.
+  * `Product`              NEW, the product of two to PG_MAX_COMP stationary kernels (no White_noise, no nesting), hp concatenated in
+                           list order like Compose's, every factor keeping its own block and its own sigma: K = prod_c K_c,
+                           dK/dtheta_{c,j} = (prod_{c' != c} K_c') dK_c/dtheta_{c,j}.  The locally periodic kernel is
+                           Product([Squared_exponential(), Periodic()]); alone or as a child of Compose.
 Leading batch dims on hp and/or x follow the reference's flatten-to-one-batch-dim rule.  Tensors come
 back on the device of `x` (CPU in -> CPU out); the arithmetic always runs on the GPU in the dtype of
 `x` (float64, or float32 as an explicit opt-in) -- unlike the reference, nothing here touches torch's
@@ -25,7 +29,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._ops import get_ops, make_specs, pad_to
+from ._ops import get_ops, make_spec, make_specs, pad_to
 
 
 class Covar(Protocol):
@@ -58,11 +62,28 @@ def layout(cov, d):
     return kinds, offs, noise, nhp
 
 
+def terms(cov, d):
+    """(terms, noise_offsets, nhp): the covariance as the sum it is.  One entry per stationary term in list order, each a tuple
+    (product, kinds, offsets): a plain stationary child is (False, (kind,), (offset,)), a Product (True, its factors' kinds, their
+    offsets).  layout() flattens the same walk and cannot tell Product([a, b]) from Compose([a, b])."""
+    tms, noise = [], []
+    nhp = cov._terms(d, 0, tms, noise)
+    return tuple(tms), noise, nhp
+
+
 def spec_of(cov, d):
-    """(passes, nhp): the pg_covspec list the device ops take (one entry unless the Compose has more than
-    PG_MAX_COMP stationary or noise children)."""
-    kinds, offs, noise, nhp = layout(cov, d)
-    return make_specs(kinds, offs, noise), nhp
+    """(passes, nhp): the pg_covspec list the device ops take.  A sum of stationary and noise children is one entry unless it has more
+    than PG_MAX_COMP of either.  A Product alone, or beside nothing but up to PG_MAX_COMP White_noise children, is ONE product spec (the
+    fused, batched and checked paths take one spec); in any other sum the plain children go first, as they always did and with the noise
+    in the earliest passes, and every Product follows in a product pass of its own without noise (`accumulate` and the disjoint gradient
+    entries serve those as they serve a long Compose)."""
+    tms, noise, nhp = terms(cov, d)
+    plain = [t for t in tms if not t[0]]
+    prods = [t for t in tms if t[0]]
+    if len(prods) == 1 and not plain and len(noise) <= _lib.PG_MAX_COMP:
+        return [make_spec(prods[0][1], prods[0][2], noise, product=True)], nhp
+    passes = make_specs([t[1][0] for t in plain], [t[2][0] for t in plain], noise) if (plain or noise or not prods) else []
+    return passes + [make_spec(t[1], t[2], [], product=True) for t in prods], nhp
 
 
 class _DeviceKernel:
@@ -73,6 +94,12 @@ class _DeviceKernel:
 
     def _nhp(self, d):
         return self._collect(d, 0, [], [], [])
+
+    def _terms(self, d, base, tms, noise):  # -> number of parameters consumed; a leaf: one plain term per stationary kind it collects
+        kinds, offs = [], []
+        used = self._collect(d, base, kinds, offs, noise)
+        tms.extend((False, (k,), (o,)) for k, o in zip(kinds, offs))
+        return used
 
     # ---- protocol ---------------------------------------------------------------------------
     def get_params_shape(self, x: Tensor) -> List[int]:
@@ -282,6 +309,12 @@ class Compose(_DeviceKernel):
             used += c._collect(d, base + used, kinds, offs, noise)
         return used
 
+    def _terms(self, d, base, tms, noise):
+        used = 0
+        for c in self.covars:
+            used += c._terms(d, base + used, tms, noise)
+        return used
+
     def init_params(self, x: Tensor) -> Tensor:  # covar.py:45-48
         return torch.cat([c.init_params(x) for c in self.covars], dim=-1)
 
@@ -290,3 +323,41 @@ class Compose(_DeviceKernel):
             assert hp.shape[-1] == self._nhp(x.shape[-1])
             return torch.tensor(0)  # a sum of White_noise children only
         return super().kernel(hp, x, xp)
+
+
+class Product(_DeviceKernel):
+    """Product of stationary covariance kernels, K = prod_c K_c: not in the reference, whose Compose can only add.  hp is the factors'
+    blocks concatenated in list order, as in Compose; each factor keeps its block as it is, its own sigma included (the product's
+    amplitude is prod_c sigma_c^2: the sigmas are not identified separately by data, and are not tied here).  With K_{-c} the product of
+    the other factors:
+
+        dK/dtheta_{c,j} = K_{-c} dK_c/dtheta_{c,j},      dK/dx* = sum_c K_{-c} dK_c/dx*
+
+    K_{-c} is formed explicitly on the device, never as K / K_c: a factor that underflows to 0 gives K = 0 and zero derivatives.
+    Factors are the stationary kinds (Squared_exponential, Matern52/32/12, Rational_quadratic, Periodic), two to PG_MAX_COMP of them; a
+    White_noise, Compose or Product factor is a TypeError.  The locally periodic kernel is Product([Squared_exponential(), Periodic()]);
+    a Product stands alone or as a child of Compose, beside stationary kernels, other Products and White_noise."""
+
+    def __init__(self, covars: Sequence[Covar]) -> None:
+        covars = list(covars)
+        for c in covars:
+            if not isinstance(c, Squared_exponential):      # (every stationary kind derives from it; White_noise, Compose and Product do not)
+                raise TypeError("Product multiplies stationary kernels only, got %s" % type(c).__name__)
+        if not 2 <= len(covars) <= _lib.PG_MAX_COMP:
+            raise ValueError("Product takes 2 to %d factors, got %d" % (_lib.PG_MAX_COMP, len(covars)))
+        self.covars = covars
+
+    def _collect(self, d, base, kinds, offs, noise):
+        used = 0
+        for c in self.covars:
+            used += c._collect(d, base + used, kinds, offs, noise)
+        return used
+
+    def _terms(self, d, base, tms, noise):
+        kinds, offs = [], []
+        used = self._collect(d, base, kinds, offs, noise)
+        tms.append((True, tuple(kinds), tuple(offs)))
+        return used
+
+    def init_params(self, x: Tensor) -> Tensor:
+        return torch.cat([c.init_params(x) for c in self.covars], dim=-1)

@@ -343,12 +343,21 @@ int pg_destroy(pg_handle h) {
     return 0;
 }
 
+// A product spec (PG_SPEC_PRODUCT or-ed into ncomp) holds 1..PG_MAX_COMP factors and never PG_KIND_SQDIST; an unflagged spec is checked
+// as it always was.  The flag itself is stripped further down (pg_spec_strip, kbuild.h), by every host routine that takes a spec.
 static int check_spec(const pg_covspec* s, const char* fn, bool allow_sqdist = false) {
-    if (!s || s->ncomp < 0 || s->ncomp > PG_MAX_COMP || s->nnoise < 0 || s->nnoise > PG_MAX_COMP) {
+    const bool prod = s && s->ncomp >= 0 && (s->ncomp & PG_SPEC_PRODUCT);
+    const int ncomp = !s ? 0 : (prod ? (s->ncomp ^ PG_SPEC_PRODUCT) : s->ncomp);
+    if (prod && (ncomp < 1 || ncomp > PG_MAX_COMP)) {
+        pg_set_error("%s: a product spec needs 1..%d factors, got %d", fn, PG_MAX_COMP, ncomp);
+        return -1;
+    }
+    if (prod) allow_sqdist = false;
+    if (!s || ncomp < 0 || ncomp > PG_MAX_COMP || s->nnoise < 0 || s->nnoise > PG_MAX_COMP) {
         pg_set_error("%s: bad covariance spec", fn);
         return -1;
     }
-    for (int c = 0; c < s->ncomp; ++c)
+    for (int c = 0; c < ncomp; ++c)
         if (s->kind[c] != PG_KIND_RBF && s->kind[c] != PG_KIND_MATERN52 && s->kind[c] != PG_KIND_MATERN32 && s->kind[c] != PG_KIND_MATERN12 &&
             s->kind[c] != PG_KIND_RQ && s->kind[c] != PG_KIND_PERIODIC && !(allow_sqdist && s->kind[c] == PG_KIND_SQDIST)) {
             pg_set_error("%s: unknown kernel kind %d", fn, s->kind[c]);

@@ -5,6 +5,13 @@
 struct GradBatch {          // strides between batched experts of the gradient contraction (elements); all zero for one expert
     long eX, ehp, eK, ea, epart, egrad;
 };
+// A product spec (PG_SPEC_PRODUCT in ncomp): every host routine below takes the spec as the caller gave it and strips the flag with
+// this before anything loops over ncomp -- the kernels get the clean copy and the choice of their PROD instantiation.
+static inline bool pg_spec_strip(const pg_covspec& in, pg_covspec& out) {
+    out = in;
+    out.ncomp = in.ncomp & ~PG_SPEC_PRODUCT;
+    return (in.ncomp & PG_SPEC_PRODUCT) != 0;
+}
 template <typename T>
 int pg_kbuild(hipStream_t st, const pg_covspec& spec, const double* hp, const T* Xr, long ldr, int nr,
               const T* Xc, long ldc, int nc, int d, int symmetric, int lower_only, int accumulate, double jitter, T* K,

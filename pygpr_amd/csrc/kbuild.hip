@@ -12,6 +12,8 @@
 //   * a periodic child (hp = [sigma, l_1..l_d, p_1..p_d]: K = sigma^2 exp(-sum_k l_k^2 sin^2(pi D_k / p_k))), alone or among others: the
 //     general kb_body in its PER instantiation -- the phase from the direct difference, 1 / p_k staged beside l^2; never PRESC, FAST or
 //     the matrix pipe.
+//   * a product spec (PG_SPEC_PRODUCT in ncomp, stripped here on the host: K = prod_c k_c, the locally periodic kernel SE x Periodic): the
+//     general kb_body in its PROD instantiation, which always carries the periodic case; never PRESC, FAST or the matrix pipe.
 // Direct differences are exactly symmetric and never negative (the reference expands into a GEMM, covar.py:102-127).  One 64x64
 // output tile per 256-thread workgroup at a time; both point tiles are staged in LDS k-major ([d][64]); each thread owns a 4x4
 // micro-tile whose columns are two 16-byte vectors, so every store instruction writes 256 contiguous bytes per row.
@@ -24,6 +26,8 @@
 // the matrix-pipe contraction of kmfma.hip; everything else (Matern-1/2, the periodic kind, d > 16, several children, PG_GRAD_MFMA=0)
 // takes pg_grad_kernel here: direct differences on the VALU.  The periodic kind: dK/dl_k = -2 K l_k s_k^2, dK/dp_k = K l_k^2
 // sin(2 pi t_k) pi t_k / p_k with t_k = D_k / p_k, s_k = sin(pi t_k) (per_terms, kfun.h).
+// A product spec: dK/dtheta_{c,j} = (prod_{c' != c} k_c') dk_c/dtheta_{c,j} -- pg_grad_kernel's PROD instantiation multiplies the
+// element's weight by the other components' values, and every entry of c follows from the code of the sum.
 #include "kbuild.h"
 #include "kfun.h"
 #include "kmfma.h"
@@ -63,12 +67,16 @@ __device__ __forceinline__ void stage_points(T* dst, const T* __restrict__ X, lo
 //            sum_k l_k^2 sin^2(pi D_k / p_k)).  Its coordinate loop takes the phase from the difference, t = D_k / p_k with 1 / p_k
 //            staged beside l^2 (ipl); the radial function is the squared exponential's.  An instantiation of its own: the bodies
 //            of the other kinds compile exactly as they did without it.
-template <typename T, bool PRESC, bool CHECKED, bool MIRROR, bool FAST = false, bool PER = false>
+//   PROD   : a product spec (PG_SPEC_PRODUCT): the components' values are MULTIPLIED into the element instead of added (an accumulate
+//            pass then adds the product to what is there).  Always with PER -- one instantiation carries every kind --, so never
+//            PRESC, FAST or the matrix pipe.  A factor that underflows to 0 gives 0; a NaN factor stays NaN.
+template <typename T, bool PRESC, bool CHECKED, bool MIRROR, bool FAST = false, bool PER = false, bool PROD = false>
 __device__ __forceinline__ void kb_body(const pg_covspec& spec, const T* xr, const T* xc, const T* l2, const T* sg2, T* tt, int d,
                                         int tr, int tc, int nr, int nc, int symmetric, int accumulate, T* __restrict__ K, long ldk,
                                         int tid, const T* nrm_r = nullptr, const T* nrm_c = nullptr, const double* tab = nullptr,
                                         const T* ipl = nullptr) {
     static_assert(!PER || (!PRESC && !FAST), "the periodic kind takes the general direct-difference body only");
+    static_assert(!PROD || PER, "a product takes the body that carries every kind");
     constexpr int VE = VecOf<T>::N, NVC = 4 / VE;   // vectors per row of the micro-tile
     typedef typename VecOf<T>::type vec_t;
     const int tx = tid & 15, ty = tid >> 4;
@@ -161,7 +169,11 @@ __device__ __forceinline__ void kb_body(const pg_covspec& spec, const T* xr, con
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) out[r][c] += kind_value<T, decltype(kind_c)::value>(s2, sq[r][c], sh, ish);
+                    for (int c = 0; c < 4; ++c) {
+                        const T kv = kind_value<T, decltype(kind_c)::value>(s2, sq[r][c], sh, ish);
+                        if constexpr (PROD) out[r][c] = cp == 0 ? kv : out[r][c] * kv;
+                        else out[r][c] += kv;
+                    }
             };
             if (kind == PG_KIND_RQ) add(std::integral_constant<int, PG_KIND_RQ>{});
             else if (kind == PG_KIND_RBF || (PER && kind == PG_KIND_PERIODIC)) add(std::integral_constant<int, PG_KIND_RBF>{});
@@ -220,7 +232,8 @@ __device__ __forceinline__ void kb_body(const pg_covspec& spec, const T* xr, con
 // buffer) while the current tile is computed.  A tile's time was 7 us of staging latency, synchronisation and drain around 1 us of
 // arithmetic with four workgroups per CU to hide it (rocprof: 2.55 TB/s on the lower-only build); the strip hides it behind work.
 // PER: the spec holds a periodic component (kb_body): 1 / p_k staged behind everything else, the general body only.
-template <typename T, bool MIRROR, int NPF, bool FASTK = false, bool PER = false>
+// PROD: a product spec (the host strips PG_SPEC_PRODUCT from ncomp first): kb_body multiplies the components; always with PER.
+template <typename T, bool MIRROR, int NPF, bool FASTK = false, bool PER = false, bool PROD = false>
 __global__ __launch_bounds__(256) void pg_kbuild_kernel(pg_covspec spec, const double* __restrict__ hp,
                                                         const T* __restrict__ Xr, long ldr, int nr,
                                                         const T* __restrict__ Xc, long ldc, int nc, int d,
@@ -322,7 +335,7 @@ __global__ __launch_bounds__(256) void pg_kbuild_kernel(pg_covspec spec, const d
         for (int t = 0; t < ntile; ++t) {
             const int tc = tcs + t, cur = t & 1, nxt = cur ^ 1;
             if (t + 1 < ntile) load_cols(tc + 1);           // in flight while this tile is computed
-            kb_body<T, decltype(presc_c)::value, decltype(checked_c)::value, MIRROR, FASTK, PER>(
+            kb_body<T, decltype(presc_c)::value, decltype(checked_c)::value, MIRROR, FASTK, PER, PROD>(
                 spec, xr, xc + cur * KT * d, l2, sg2, tt, d, tr, tc, nr, nc, symmetric, accumulate, K, ldk, tid, nrm, nrm + KT + cur * KT, tab, ipl);
             if (t + 1 < ntile) {
                 store_cols(xc + nxt * KT * d);
@@ -361,23 +374,25 @@ template <typename T> static constexpr size_t kb_lds_bytes(int d, bool mirror, b
 }
 
 // One instantiation of pg_kbuild_kernel: its dynamic-LDS limit once, then the launch.
-template <typename T, bool MIRROR, int NPF, bool FAST, bool PER, typename... Args>
+template <typename T, bool MIRROR, int NPF, bool FAST, bool PER, bool PROD, typename... Args>
 static int kb_launch(dim3 grid, size_t lds, hipStream_t st, Args... args) {
     static bool attr_done = false;
     if (!attr_done) {   // large d passes the 64 KB a kernel gets without opting in (134 KB for the mirrored fp64 build at d = 64)
-        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_kbuild_kernel<T, MIRROR, NPF, FAST, PER>),
+        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_kbuild_kernel<T, MIRROR, NPF, FAST, PER, PROD>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kb_lds_bytes<T>(PG_MAX_DIM, true, PER)));
         attr_done = true;
     }
-    hipLaunchKernelGGL((pg_kbuild_kernel<T, MIRROR, NPF, FAST, PER>), grid, dim3(256), lds, st, args...);
+    hipLaunchKernelGGL((pg_kbuild_kernel<T, MIRROR, NPF, FAST, PER, PROD>), grid, dim3(256), lds, st, args...);
     PG_CHECK(hipGetLastError());
     return 0;
 }
 
 template <typename T>
-int pg_kbuild(hipStream_t st, const pg_covspec& spec, const double* hp, const T* Xr, long ldr, int nr,
+int pg_kbuild(hipStream_t st, const pg_covspec& spec_in, const double* hp, const T* Xr, long ldr, int nr,
               const T* Xc, long ldc, int nc, int d, int symmetric, int lower_only, int accumulate, double jitter, T* K,
               long ldk, int rows_pad, int cols_pad, int col0, int col1, int nexp, long eX, long ehp, long eK, long eXr) {
+    pg_covspec spec;
+    const bool prod = pg_spec_strip(spec_in, spec);      // a product spec: the PROD instantiation of the general body (below)
     if (eXr < 0 || symmetric) eXr = eX;      // symmetric builds: one point set per expert
     if (rows_pad % KT || cols_pad % KT || d < 1 || d > PG_MAX_DIM) {
         pg_set_error("pg_kbuild: bad shape rows_pad=%d cols_pad=%d d=%d", rows_pad, cols_pad, d);
@@ -386,6 +401,7 @@ int pg_kbuild(hipStream_t st, const pg_covspec& spec, const double* hp, const T*
     const bool mirror = symmetric && !lower_only;
     bool per = false;      // a periodic component: the general direct-difference body in its own instantiation, never PRESC / FAST / the matrix pipe
     for (int c = 0; c < spec.ncomp; ++c) per = per || spec.kind[c] == PG_KIND_PERIODIC;
+    per = per || prod;     // the product's body always carries the periodic case
     const size_t lds = kb_lds_bytes<T>(d, mirror, per);
     // columns [col0, col1) only (col1 <= 0: all): a lower-only symmetric build in two column windows lets the factorisation
     // start on the first panel while the rest is still being written (pg_potrf_t, BuildReq)
@@ -426,31 +442,33 @@ int pg_kbuild(hipStream_t st, const pg_covspec& spec, const double* hp, const T*
     const int mfma_env = getenv("PG_KB_MFMA") ? atoi(getenv("PG_KB_MFMA")) : 1;      // (read per call: tests compare the bodies in one process)
     // (mirrored, lower-only and cross builds of one (kind, dtype, d) all take the same body: their values agree bit for bit)
     // (Matern-1/2 never: it is 1 - r near 0, so the expansion's error in sq reaches K as its square root -- DESIGN.md)
-    if (mfma_env && spec.ncomp == 1 && !accumulate && d <= 16 &&
+    if (mfma_env && !prod && spec.ncomp == 1 && !accumulate && d <= 16 &&
         (spec.kind[0] == PG_KIND_RBF || spec.kind[0] == PG_KIND_MATERN52 || spec.kind[0] == PG_KIND_MATERN32 || spec.kind[0] == PG_KIND_RQ) &&
         (mfma_env >= 2 || presc != 2 || d > 8))
         return pg_kbuild_mfma<T>(st, spec, hp, Xr, ldr, nr, Xc, ldc, nc, d, symmetric, mirror ? 1 : 0, jitter, K, ldk, c0, c1, S, strips, nexp, eX,
                                  ehp, eK, eXr);
     const int npf = d <= 8 ? 2 : (d <= 16 ? 4 : 16);
-    // (mirror, npf, fast, per) -> kb_launch<T, MIRROR, NPF, FAST, PER>; the fast body exists in fp64 only
-    auto go = [&](auto mirror_c, auto npf_c, auto fast_c, auto per_c) {
-        return kb_launch<T, decltype(mirror_c)::value, decltype(npf_c)::value, decltype(fast_c)::value, decltype(per_c)::value>(
+    // (mirror, npf, fast, per, prod) -> kb_launch<T, MIRROR, NPF, FAST, PER, PROD>; the fast body exists in fp64 only
+    auto go = [&](auto mirror_c, auto npf_c, auto fast_c, auto per_c, auto prod_c) {
+        return kb_launch<T, decltype(mirror_c)::value, decltype(npf_c)::value, decltype(fast_c)::value, decltype(per_c)::value,
+                         decltype(prod_c)::value>(
             dim3((unsigned)strips, (unsigned)nexp), lds, st, spec, hp, Xr, ldr, nr, Xc, ldc, nc, d, symmetric, accumulate, jitter, K, ldk, c0, c1,
             presc, S, eX, ehp, eK, eXr);
     };
-    auto with_npf = [&](auto mirror_c, auto fast_c, auto per_c) {
-        if (npf == 2) return go(mirror_c, std::integral_constant<int, 2>{}, fast_c, per_c);
-        if (npf == 4) return go(mirror_c, std::integral_constant<int, 4>{}, fast_c, per_c);
-        return go(mirror_c, std::integral_constant<int, 16>{}, fast_c, per_c);
+    auto with_npf = [&](auto mirror_c, auto fast_c, auto per_c, auto prod_c) {
+        if (npf == 2) return go(mirror_c, std::integral_constant<int, 2>{}, fast_c, per_c, prod_c);
+        if (npf == 4) return go(mirror_c, std::integral_constant<int, 4>{}, fast_c, per_c, prod_c);
+        return go(mirror_c, std::integral_constant<int, 16>{}, fast_c, per_c, prod_c);
     };
-    auto with_mirror = [&](auto fast_c, auto per_c) {
-        return mirror ? with_npf(std::true_type{}, fast_c, per_c) : with_npf(std::false_type{}, fast_c, per_c);
+    auto with_mirror = [&](auto fast_c, auto per_c, auto prod_c) {
+        return mirror ? with_npf(std::true_type{}, fast_c, per_c, prod_c) : with_npf(std::false_type{}, fast_c, per_c, prod_c);
     };
-    if (per) return with_mirror(std::false_type{}, std::true_type{});
+    if (prod) return with_mirror(std::false_type{}, std::true_type{}, std::true_type{});
+    if (per) return with_mirror(std::false_type{}, std::true_type{}, std::false_type{});
     if constexpr (sizeof(T) == 8) {
-        if (presc == 2) return with_mirror(std::true_type{}, std::false_type{});
+        if (presc == 2) return with_mirror(std::true_type{}, std::false_type{}, std::false_type{});
     }
-    return with_mirror(std::false_type{}, std::false_type{});
+    return with_mirror(std::false_type{}, std::false_type{}, std::false_type{});
 }
 template int pg_kbuild<double>(hipStream_t, const pg_covspec&, const double*, const double*, long, int,
                                const double*, long, int, int, int, int, int, double, double*, long, int, int, int, int, int, long, long, long, long);
@@ -461,7 +479,36 @@ template int pg_kbuild<float>(hipStream_t, const pg_covspec&, const double*, con
 // dK stack of the public Covar.kernel_and_grad (covar.py:64-81,169-206,247-269): dK[p][i][j] for
 // every hyper-parameter p.  Only the drop-in surface needs it; the NLML path never materialises it.
 // ------------------------------------------------------------------------------------------------
+// The value of component c at one pair of points, straight from global memory: the factors of a product spec (pg_kgrad_kernel<PROD>)
 template <typename T>
+__device__ __forceinline__ T kgrad_value(const pg_covspec& spec, const double* __restrict__ hp, int c, const T* xi, const T* xj, int d) {
+    const int o = spec.off[c];
+    const double sg = hp[o];
+    T sq = (T)0;
+    if (spec.kind[c] == PG_KIND_PERIODIC) {
+        for (int k = 0; k < d; ++k) {
+            const double l = hp[o + 1 + k];
+            sq += (T)(l * l) * per_sin2<T>((xi[k] - xj[k]) * (T)(1.0 / hp[o + d + 1 + k]));
+        }
+        return (T)(sg * sg) * pg_exp(-sq);
+    }
+    for (int k = 0; k < d; ++k) {
+        const double l = hp[o + 1 + k];
+        const T df = xi[k] - xj[k];
+        sq += (T)(l * l) * df * df;
+    }
+    T kv, base, fs;
+    if (spec.kind[c] == PG_KIND_RBF) kind_eval<T, PG_KIND_RBF>((T)(sg * sg), sq, kv, base);
+    else {
+        const double a = kind_shape2(spec, hp, c, d);
+        matern_val<T>(spec.kind[c], (T)(sg * sg), sq, kv, base, (T)a, (T)(1.0 / a), fs);
+    }
+    return kv;
+}
+
+// PROD: a product spec -- every slab of component cp is the sum spec's slab times the product of the OTHER components' values, formed
+// explicitly (never K / k_cp: a factor that underflows gives 0).  An instantiation of its own; the sum kernel computes what it did.
+template <typename T, bool PROD = false>
 __global__ __launch_bounds__(256) void pg_kgrad_kernel(pg_covspec spec, const double* __restrict__ hp,
                                                        const T* __restrict__ X, long ldx, int n, int d,
                                                        T* __restrict__ dK, long slab) {
@@ -471,9 +518,19 @@ __global__ __launch_bounds__(256) void pg_kgrad_kernel(pg_covspec spec, const do
     const long e = (long)i * n + j;
     const T* xi = X + (long)i * ldx;
     const T* xj = X + (long)j * ldx;
+    T oth = (T)1;      // PROD: the product of the components other than cp at this pair
+    auto put = [&](long idx, T v) {
+        if constexpr (PROD) dK[idx] = v * oth;
+        else dK[idx] = v;
+    };
     for (int cp = 0; cp < spec.ncomp; ++cp) {
         const int o = spec.off[cp];
         const double sg = hp[o];
+        if constexpr (PROD) {
+            oth = (T)1;
+            for (int c2 = 0; c2 < spec.ncomp; ++c2)
+                if (c2 != cp) oth *= kgrad_value<T>(spec, hp, c2, xi, xj, d);
+        }
         if (spec.kind[cp] == PG_KIND_PERIODIC) {      // sigma, the length-scale slabs from sin^2, the period slabs o + d + 1 .. o + 2 d
             T sp = (T)0;
             for (int k = 0; k < d; ++k) {
@@ -481,14 +538,14 @@ __global__ __launch_bounds__(256) void pg_kgrad_kernel(pg_covspec spec, const do
                 sp += (T)(l * l) * per_sin2<T>((xi[k] - xj[k]) * (T)(1.0 / hp[o + d + 1 + k]));
             }
             const T kp = (T)(sg * sg) * pg_exp(-sp);
-            dK[(long)o * slab + e] = kp * (T)(2.0 / sg);
+            put((long)o * slab + e, kp * (T)(2.0 / sg));
             for (int k = 0; k < d; ++k) {
                 const double l = hp[o + 1 + k], ip = 1.0 / hp[o + d + 1 + k];
                 const T t = (xi[k] - xj[k]) * (T)ip;
                 T s2, s2w;
                 per_terms<T>(t, s2, s2w);
-                dK[(long)(o + 1 + k) * slab + e] = (T)(-2.0 * l) * s2 * kp;
-                dK[(long)(o + d + 1 + k) * slab + e] = kp * (T)(l * l * PG_PI * ip) * s2w * t;
+                put((long)(o + 1 + k) * slab + e, (T)(-2.0 * l) * s2 * kp);
+                put((long)(o + d + 1 + k) * slab + e, kp * (T)(l * l * PG_PI * ip) * s2w * t);
             }
             continue;
         }
@@ -503,13 +560,13 @@ __global__ __launch_bounds__(256) void pg_kgrad_kernel(pg_covspec spec, const do
         else {
             const double a = kind_shape2(spec, hp, cp, d);
             matern_val<T>(spec.kind[cp], (T)(sg * sg), sq, kv, base, (T)a, (T)(1.0 / a), fs);
-            if (spec.kind[cp] == PG_KIND_RQ) dK[(long)(o + d + 1) * slab + e] = (T)(2.0 * hp[o + d + 1]) * fs;      // the shape slab
+            if (spec.kind[cp] == PG_KIND_RQ) put((long)(o + d + 1) * slab + e, (T)(2.0 * hp[o + d + 1]) * fs);      // the shape slab
         }
         const T coef = (T)(2.0 * kind_hcoef(spec.kind[cp]));
-        dK[(long)o * slab + e] = kv * (T)(2.0 / sg);
+        put((long)o * slab + e, kv * (T)(2.0 / sg));
         for (int k = 0; k < d; ++k) {
             const T df = xi[k] - xj[k];
-            dK[(long)(o + 1 + k) * slab + e] = coef * (T)hp[o + 1 + k] * df * df * base;
+            put((long)(o + 1 + k) * slab + e, coef * (T)hp[o + 1 + k] * df * df * base);
         }
     }
     for (int q = 0; q < spec.nnoise; ++q)
@@ -517,10 +574,14 @@ __global__ __launch_bounds__(256) void pg_kgrad_kernel(pg_covspec spec, const do
 }
 
 template <typename T>
-int pg_kgrad(hipStream_t st, const pg_covspec& spec, const double* hp, const T* X, long ldx, int n, int d, T* dK) {
+int pg_kgrad(hipStream_t st, const pg_covspec& spec_in, const double* hp, const T* X, long ldx, int n, int d, T* dK) {
     if (n <= 0 || d < 1 || d > PG_MAX_DIM) { pg_set_error("pg_kernel_grad_build: bad shape n=%d d=%d", n, d); return -2; }
-    hipLaunchKernelGGL(pg_kgrad_kernel<T>, dim3((n + 63) / 64, (n + 3) / 4), dim3(256), 0, st, spec, hp, X, ldx, n, d, dK,
-                       (long)n * n);
+    pg_covspec spec;
+    const dim3 grid((n + 63) / 64, (n + 3) / 4);
+    if (pg_spec_strip(spec_in, spec))
+        hipLaunchKernelGGL((pg_kgrad_kernel<T, true>), grid, dim3(256), 0, st, spec, hp, X, ldx, n, d, dK, (long)n * n);
+    else
+        hipLaunchKernelGGL((pg_kgrad_kernel<T, false>), grid, dim3(256), 0, st, spec, hp, X, ldx, n, d, dK, (long)n * n);
     PG_CHECK(hipGetLastError());
     return 0;
 }
@@ -585,8 +646,13 @@ template int pg_centres<float>(hipStream_t, const float*, long, int, const float
 // and sums sin(2 pi D_k / p_k) D_k / p_k for its d period entries; the fold's slots of a child follow its block, kind_nparam wide:
 // sigma, l_1..l_DMAX, then whatever the kind keeps behind them (the rational quadratic's shape, the periods) from slot DMAX + 1 on.
 // An instantiation of its own: the other kinds' kernels compile exactly as they did without it.
+// PROD: a product spec (always with PER: one instantiation carries every kind).  The product rule enters as a WEIGHT: for component
+// cp the element's weight is multiplied by the product of the other components' values, evaluated from the operands already in LDS
+// (elem_value) -- explicitly, never as K / k_cp: a factor that underflows gives 0.  Every entry of cp (sigma, length scales, shape,
+// periods) then follows from the code of the sum; the trace of W for the noise entries takes the unmodified weight, and the reduce
+// kernel's scales are unchanged.
 #define GCH 4
-template <typename T, int DMAX, bool PER = false>
+template <typename T, int DMAX, bool PER = false, bool PROD = false>
 __global__ __launch_bounds__(256) void pg_grad_kernel(pg_covspec spec, const double* __restrict__ hp,
                                                       const T* __restrict__ X, long ldx, int n, int d,
                                                       const T* __restrict__ Kinv, long ldk,
@@ -621,6 +687,31 @@ __global__ __launch_bounds__(256) void pg_grad_kernel(pg_covspec spec, const dou
         if constexpr (PER) ipl[idx] = (k < d && spec.kind[c] == PG_KIND_PERIODIC) ? (T)(1.0 / hp[spec.off[c] + d + 1 + k]) : (T)0;
     }
     for (int idx = tid; idx < nhp; idx += 256) part[(long)blk * nhp + idx] = 0.0;
+    static_assert(!PROD || PER, "a product takes the instantiation that carries every kind");
+    // PROD: component c's value at (row, this lane's column) of the point tile xb
+    auto elem_value = [&](int c, int row, const T* xb) -> T {
+        const T* lc = l2 + c * DMAX;
+        const int kind = spec.kind[c];
+        const double sg = hp[spec.off[c]];
+        const T sig2 = (T)(sg * sg);
+        T sq = (T)0;
+        if (kind == PG_KIND_PERIODIC) {
+            const T* ipc = ipl + c * DMAX;
+#pragma unroll
+            for (int k = 0; k < DMAX; ++k) sq += lc[k] * per_sin2<T>((xr[k * KT + row] - xb[k * KT + lane]) * ipc[k]);
+            return kind_value<T, PG_KIND_RBF>(sig2, sq);
+        }
+#pragma unroll
+        for (int k = 0; k < DMAX; ++k) {
+            const T df = xr[k * KT + row] - xb[k * KT + lane];
+            sq += lc[k] * df * df;
+        }
+        if (kind == PG_KIND_RBF) return kind_value<T, PG_KIND_RBF>(sig2, sq);
+        const double sh = kind_shape2(spec, hp, c, d);
+        T kt, bt, ft;
+        matern_val<T>(kind, sig2, sq, kt, bt, (T)sh, (T)(1.0 / sh), ft);
+        return kt;
+    };
 
     // element e of this thread: row = 4 e + wave (one wave reads one 64-wide row: 512 contiguous bytes),
     // column = lane.  W = weight * (Kinv - a a^T): 2 below the diagonal, 1 on it, 0 above / in padding.
@@ -662,6 +753,10 @@ __global__ __launch_bounds__(256) void pg_grad_kernel(pg_covspec spec, const dou
                     if (gj < gi) w *= 2.0; else if (cp == 0) tr_w += w;
                 }
                 if (!have) continue;
+                if constexpr (PROD) {      // the product rule: the others' values weigh this component's element
+                    for (int c2 = 0; c2 < spec.ncomp; ++c2)
+                        if (c2 != cp) w *= (double)elem_value(c2, row, xb);
+                }
                 if constexpr (PER) {
                     if (kind == PG_KIND_PERIODIC) {      // (padding coordinates: l^2 = 1 / p = 0, so t = 0 and both terms vanish)
                         const T* ipc = ipl + cp * DMAX;
@@ -785,27 +880,29 @@ __global__ __launch_bounds__(256) void pg_grad_reduce_kernel(pg_covspec spec, co
     }
 }
 
-template <typename T, int DMAX, bool PER>
+template <typename T, int DMAX, bool PER, bool PROD>
 static int launch_grad(hipStream_t st, const pg_covspec& spec, const double* hp, const T* X, long ldx, int n,
                        int d, const T* Kinv, long ldk, const T* alpha, double* part, int nhp, int tiles, const GradBatch& gb, int nexp) {
     const size_t lds = (size_t)(3 * KT * DMAX + (PER ? 2 : 1) * PG_MAX_COMP * DMAX) * sizeof(T) +
                        4 * kind_nparam(PER ? PG_KIND_PERIODIC : PG_KIND_RQ, DMAX) * sizeof(double);
     static bool attr_done = false;
     if (!attr_done) {   // d > 32 needs more than the 64 KB a kernel gets without opting in
-        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_grad_kernel<T, DMAX, PER>),
+        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_grad_kernel<T, DMAX, PER, PROD>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_done = true;
     }
-    hipLaunchKernelGGL((pg_grad_kernel<T, DMAX, PER>), dim3((tiles + GCH - 1) / GCH, tiles, nexp), dim3(256), lds, st, spec, hp, X, ldx,
+    hipLaunchKernelGGL((pg_grad_kernel<T, DMAX, PER, PROD>), dim3((tiles + GCH - 1) / GCH, tiles, nexp), dim3(256), lds, st, spec, hp, X, ldx,
                        n, d, Kinv, ldk, alpha, part, nhp, gb);
     PG_CHECK(hipGetLastError());
     return 0;
 }
 
 template <typename T>
-int pg_nlml_grad_t(hipStream_t st, const pg_covspec& spec, const double* hp, const T* X, long ldx, int n, int d,
+int pg_nlml_grad_t(hipStream_t st, const pg_covspec& spec_in, const double* hp, const T* X, long ldx, int n, int d,
                    const T* Kinv, long ldk, const T* alpha, double* grad, int nhp, double* work, long lwork,
                    int nexp, long ehp, long eX, long eK, long ea, long egrad) {
+    pg_covspec spec;
+    const bool prod = pg_spec_strip(spec_in, spec);      // a product spec: pg_grad_kernel's PROD instantiation, never the matrix pipe
     const int tiles = (n + KT - 1) / KT;
     const long need = (long)tiles * tiles * nhp;
     if (nexp < 1 || nexp > 65535) { pg_set_error("pg_nlml_grad: 1 <= nexp <= 65535"); return -2; }
@@ -816,7 +913,7 @@ int pg_nlml_grad_t(hipStream_t st, const pg_covspec& spec, const double* hp, con
     // the independent direct-difference yardstick of the tests)
     const int mfma_env = getenv("PG_GRAD_MFMA") ? atoi(getenv("PG_GRAD_MFMA")) : 1;   // (read per call: tests compare the bodies in one process)
     // (not Matern-1/2: its factor e^-r / r is unbounded near r = 0, and the expansion's cancellation error is u |x|^2 sum |G| -- DESIGN.md)
-    if (mfma_env && spec.ncomp == 1 && d <= 16 && n >= 1 &&
+    if (mfma_env && !prod && spec.ncomp == 1 && d <= 16 && n >= 1 &&
         (spec.kind[0] == PG_KIND_RBF || spec.kind[0] == PG_KIND_MATERN52 || spec.kind[0] == PG_KIND_MATERN32 || spec.kind[0] == PG_KIND_RQ)) {
         int nblk = 0;
         if ((rc = pg_grad_mfma<T>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp, &nblk))) return rc;
@@ -826,16 +923,16 @@ int pg_nlml_grad_t(hipStream_t st, const pg_covspec& spec, const double* hp, con
     }
     bool per = false;      // a periodic component: pg_grad_kernel's own instantiation (never the matrix pipe: the whitelist above)
     for (int c = 0; c < spec.ncomp; ++c) per = per || spec.kind[c] == PG_KIND_PERIODIC;
-    auto go = [&](auto per_c) {
-        constexpr bool P = decltype(per_c)::value;
-        if (d <= 4) return launch_grad<T, 4, P>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
-        if (d <= 8) return launch_grad<T, 8, P>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
-        if (d <= 16) return launch_grad<T, 16, P>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
-        if (d <= 32) return launch_grad<T, 32, P>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
-        return launch_grad<T, 64, P>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
+    auto go = [&](auto per_c, auto prod_c) {
+        constexpr bool P = decltype(per_c)::value, Q = decltype(prod_c)::value;
+        if (d <= 4) return launch_grad<T, 4, P, Q>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
+        if (d <= 8) return launch_grad<T, 8, P, Q>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
+        if (d <= 16) return launch_grad<T, 16, P, Q>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
+        if (d <= 32) return launch_grad<T, 32, P, Q>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
+        return launch_grad<T, 64, P, Q>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
     };
     if (d > PG_MAX_DIM) { pg_set_error("pg_nlml_grad: d=%d > %d", d, PG_MAX_DIM); return -2; }
-    rc = per ? go(std::true_type{}) : go(std::false_type{});
+    rc = prod ? go(std::true_type{}, std::true_type{}) : (per ? go(std::true_type{}, std::false_type{}) : go(std::false_type{}, std::false_type{}));
     if (rc) return rc;
     hipLaunchKernelGGL(pg_grad_reduce_kernel, dim3(nhp, 1, nexp), dim3(256), 0, st, spec, hp, work, tiles * ((tiles + GCH - 1) / GCH), nhp,
                        d, grad, 0, gb);

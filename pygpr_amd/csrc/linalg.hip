@@ -1040,14 +1040,18 @@ int pg_predict_mean_q_kt_t(pg_ctx* ctx, hipStream_t st, int n, int m, const T* K
 // var_e[j] = kss_e - sum_rc part_e[rc][j] with kss_e = sum sigma_c^2 + sum sigma_n^2 of expert e's hyper-parameters: the constant diagonal
 // of K** (gpr.py:98: White_noise sees xp = None), formed here so that the batched prediction needs no host arithmetic per expert.
 // (products and sums kept apart -- no FMA contraction -- so that the value is the one the host computes for the one-expert call)
+// prod: a product spec (PG_SPEC_PRODUCT, stripped by the host) -- its stationary term is ONE product, prior variance prod sigma_c^2.
 template <typename T>
 __global__ __launch_bounds__(256) void predict_var_reduce_kernel(const T* __restrict__ part, long ldp, int nrc, int cols, T* __restrict__ out,
-                                                                 pg_covspec spec, const double* __restrict__ hp, long ehp, long ep, long eo) {
+                                                                 pg_covspec spec, const double* __restrict__ hp, long ehp, long ep, long eo, int prod) {
     part += blockIdx.z * ep; out += blockIdx.z * eo; hp += blockIdx.z * ehp;
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= cols) return;
-    double s1 = 0.0, s2 = 0.0;
-    for (int c = 0; c < spec.ncomp; ++c) s1 = __dadd_rn(s1, __dmul_rn(hp[spec.off[c]], hp[spec.off[c]]));
+    double s1 = prod ? 1.0 : 0.0, s2 = 0.0;
+    for (int c = 0; c < spec.ncomp; ++c) {
+        const double sg2 = __dmul_rn(hp[spec.off[c]], hp[spec.off[c]]);
+        s1 = prod ? __dmul_rn(s1, sg2) : __dadd_rn(s1, sg2);
+    }
     for (int c = 0; c < spec.nnoise; ++c) s2 = __dadd_rn(s2, __dmul_rn(hp[spec.noise_off[c]], hp[spec.noise_off[c]]));
     const double kss = __dadd_rn(s1, s2);
     double s = 0.0;
@@ -1061,8 +1065,10 @@ __global__ __launch_bounds__(256) void predict_var_reduce_kernel(const T* __rest
 // the one-expert launch with the expert as the core's second batch level: per expert the same tiles in the same k order, bit for bit.
 template <typename T>
 int pg_predict_mean_q_kt_batched_t(pg_ctx* ctx, hipStream_t st, int n, int m, const T* Kt, long ldkt, long ekt, const T* M, long ldm, long em,
-                                   const T* alpha, long ea, T* mean, long emean, T* q, long evar, const pg_covspec& spec, const double* hp,
+                                   const T* alpha, long ea, T* mean, long emean, T* q, long evar, const pg_covspec& spec_in, const double* hp,
                                    long ehp, T* work, long ew, int nexp) {
+    pg_covspec spec;
+    const int prod = pg_spec_strip(spec_in, spec) ? 1 : 0;
     if (n % PG_PAD || m % 256 || n <= 0 || m <= 0) { pg_set_error("pg_predict_mean_q_kt_batched: n_pad=%d m_pad=%d must be multiples of 256", n, m); return -2; }
     if (nexp < 1 || nexp > 65535) { pg_set_error("pg_predict_mean_q_kt_batched: 1 <= nexp <= 65535"); return -2; }
     hipLaunchKernelGGL(gemv_rows_kernel<T>, dim3(m / 4, nexp), dim3(256), 0, st, Kt, ldkt, n, alpha, mean, ekt, ea, emean);
@@ -1074,7 +1080,7 @@ int pg_predict_mean_q_kt_batched_t(pg_ctx* ctx, hipStream_t st, int n, int m, co
         p.nexp = nexp; p.eA = em; p.eB = ekt; p.eC = ew;
         int rc = pg_gemm<T>(ctx, st, GEMM_NT_128_SS, p);
         if (rc) return rc;
-        hipLaunchKernelGGL(predict_var_reduce_kernel<T>, dim3(m / 256, 1, nexp), dim3(256), 0, st, (const T*)work, (long)m, n / 64, m, q, spec, hp, ehp, ew, evar);
+        hipLaunchKernelGGL(predict_var_reduce_kernel<T>, dim3(m / 256, 1, nexp), dim3(256), 0, st, (const T*)work, (long)m, n / 64, m, q, spec, hp, ehp, ew, evar, prod);
         LAUNCH_CHECK();
     }
     return 0;

@@ -20,8 +20,12 @@
 //   * a NaN coordinate of a test point reaches that point's row only (pg_exp keeps a NaN, matern_val's selects are NaN-transparent);
 //   * the periodic kind has dk/dx*_pk = -K l_k^2 sin(2 pi D_k / p_k) pi / p_k: the same contraction with sin(2 pi t_k) pi / (2 p_k) in
 //     the place of D_k and K as `base`, the phase taken from the difference (per_terms, kfun.h); 1 / p_k is staged beside l^2.
+//   * a product spec (PG_SPEC_PRODUCT, stripped by the host; the PROD instantiation): dk/dx* = sum_c (prod_{c' != c} k_c') dk_c/dx*, so
+//     each component's factor f of a pair is multiplied by the other components' values at that pair (`others`), for u and B alike;
+//     the product is formed explicitly, never as K / k_c: a factor that underflows gives 0.
 #include "kbuild.h"
 #include "kfun.h"
+#include <type_traits>
 
 #define XT 64        // test points of a workgroup = training points of a staged tile
 #define BLD 65       // odd leading dimension of the staged B tile: a lane reads its own row
@@ -32,7 +36,7 @@ struct XgradBatch {  // strides between batched experts (elements); 0 shares an 
 
 // HOLD (d <= 16): the test point and the sixteen differences of a pair live in registers; otherwise the test points are read from
 // LDS and the accumulators cover KC = 16 coordinates per pass (passes over the coordinates repeat the distances: d > 16 is rare).
-template <typename T, int DMAX, bool HU, bool HB>
+template <typename T, int DMAX, bool HU, bool HB, bool PROD = false>
 __global__ __launch_bounds__(256) void pg_xgrad_kernel(pg_covspec spec, const double* __restrict__ hp, const T* __restrict__ Xq, long ldq,
                                                        int m, const T* __restrict__ Z, long ldz, int n, int d, const T* __restrict__ u,
                                                        const T* __restrict__ B, long ldb, int trans_b, double* __restrict__ part, int ct,
@@ -76,6 +80,39 @@ __global__ __launch_bounds__(256) void pg_xgrad_kernel(pg_covspec spec, const do
         l2s[idx] = (T)(l * l);
         ips[idx] = (k < d && spec.kind[c] == PG_KIND_PERIODIC) ? (T)(1.0 / hp[spec.off[c] + d + 1 + k]) : (T)0;
     }
+
+    // PROD: the product of the values of every component but cp at (this lane's test point, the staged training point zc)
+    auto others = [&](int cp, const T* zc) -> double {
+        double oth = 1.0;
+        for (int c2 = 0; c2 < spec.ncomp; ++c2) {
+            if (c2 == cp) continue;
+            const T* l = l2s + c2 * DMAX;
+            const int kind2 = spec.kind[c2];
+            const double sg2 = hp[spec.off[c2]];
+            const T s2 = (T)(sg2 * sg2);
+            T sq = (T)0, kv;
+            if (kind2 == PG_KIND_PERIODIC) {
+                const T* ip = ips + c2 * DMAX;
+#pragma unroll
+                for (int k = 0; k < DMAX; ++k) sq += l[k] * per_sin2<T>(((HOLD ? xr[HOLD ? k : 0] : xrs[lane * (DMAX + 1) + k]) - zc[k]) * ip[k]);
+                kv = s2 * pg_exp(-sq);
+            } else {
+#pragma unroll
+                for (int k = 0; k < DMAX; ++k) {
+                    const T dd = (HOLD ? xr[HOLD ? k : 0] : xrs[lane * (DMAX + 1) + k]) - zc[k];
+                    sq += l[k] * dd * dd;
+                }
+                if (kind2 == PG_KIND_RBF) kv = s2 * pg_exp(-sq);
+                else {
+                    const double sh2 = kind_shape2(spec, hp, c2, d);
+                    T bt, ft;
+                    matern_val<T>(kind2, s2, sq, kv, bt, (T)sh2, (T)(1.0 / sh2), ft);
+                }
+            }
+            oth *= (double)kv;
+        }
+        return oth;
+    };
 
     for (int k0 = 0; k0 < (HOLD ? 1 : d); k0 += KC) {
         double au[KC], ab[KC];
@@ -122,7 +159,8 @@ __global__ __launch_bounds__(256) void pg_xgrad_kernel(pg_covspec spec, const do
 #pragma unroll
                         for (int k = 0; k < DMAX; ++k)
                             sq += lc[k] * per_sin2<T>(((HOLD ? xr[k] : xrs[lane * (DMAX + 1) + k]) - zc[k]) * ipc[k]);
-                        const double f = f2 * (double)(sig2 * pg_exp(-sq));
+                        double f = f2 * (double)(sig2 * pg_exp(-sq));
+                        if constexpr (PROD) f *= others(cp, zc);
                         const double wu = HU ? f * (double)us[c] : 0.0;
                         const double wb = HB ? f * (double)bs[lane * BLD + c] : 0.0;
 #pragma unroll
@@ -152,7 +190,8 @@ __global__ __launch_bounds__(256) void pg_xgrad_kernel(pg_covspec spec, const do
                     T kv, bt, ft;
                     if (kind == PG_KIND_RBF) bt = sig2 * pg_exp(-sq);
                     else matern_val<T>(kind, sig2, sq, kv, bt, sha, ish, ft);
-                    const double f = f2 * (double)bt;
+                    double f = f2 * (double)bt;
+                    if constexpr (PROD) f *= others(cp, zc);
                     const double wu = HU ? f * (double)us[c] : 0.0;
                     const double wb = HB ? f * (double)bs[lane * BLD + c] : 0.0;
 #pragma unroll
@@ -222,7 +261,7 @@ long pg_xgrad_worksize_impl(int ncu, int m, int n, int d, int nexp) {
     return 2L * nexp * nsplit * d * mrows;
 }
 
-template <typename T, int DMAX, bool HU, bool HB>
+template <typename T, int DMAX, bool HU, bool HB, bool PROD>
 static int launch_xgrad(hipStream_t st, const pg_covspec& spec, const double* hp, const T* Xq, long ldq, int m, const T* Z, long ldz,
                         int n, int d, const T* u, const T* B, long ldb, int trans_b, double* part, int nsplit, int ct, long mrows,
                         const XgradBatch& xb, int nexp) {
@@ -231,29 +270,31 @@ static int launch_xgrad(hipStream_t st, const pg_covspec& spec, const double* hp
                        (size_t)(XT * DMAX + (DMAX <= 16 ? 0 : XT * (DMAX + 1)) + 2 * PG_MAX_COMP * DMAX + XT + XT * BLD) * sizeof(T);
     static bool attr_done = false;
     if (!attr_done) {   // d > 16 in fp64 passes the 64 KB a kernel gets without opting in
-        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_xgrad_kernel<T, DMAX, HU, HB>),
+        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_xgrad_kernel<T, DMAX, HU, HB, PROD>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_done = true;
     }
-    hipLaunchKernelGGL((pg_xgrad_kernel<T, DMAX, HU, HB>), dim3(nsplit, (m + XT - 1) / XT, nexp), dim3(256), lds, st, spec, hp, Xq, ldq, m, Z,
+    hipLaunchKernelGGL((pg_xgrad_kernel<T, DMAX, HU, HB, PROD>), dim3(nsplit, (m + XT - 1) / XT, nexp), dim3(256), lds, st, spec, hp, Xq, ldq, m, Z,
                        ldz, n, d, u, B, ldb, trans_b, part, ct, mrows, xb);
     PG_CHECK(hipGetLastError());
     return 0;
 }
 
-template <typename T, int DMAX>
+template <typename T, int DMAX, bool PROD>
 static int launch_xgrad_w(hipStream_t st, const pg_covspec& spec, const double* hp, const T* Xq, long ldq, int m, const T* Z, long ldz,
                           int n, int d, const T* u, const T* B, long ldb, int trans_b, double* part, int nsplit, int ct, long mrows,
                           const XgradBatch& xb, int nexp) {
-    if (u && B) return launch_xgrad<T, DMAX, true, true>(st, spec, hp, Xq, ldq, m, Z, ldz, n, d, u, B, ldb, trans_b, part, nsplit, ct, mrows, xb, nexp);
-    if (u) return launch_xgrad<T, DMAX, true, false>(st, spec, hp, Xq, ldq, m, Z, ldz, n, d, u, B, ldb, trans_b, part, nsplit, ct, mrows, xb, nexp);
-    return launch_xgrad<T, DMAX, false, true>(st, spec, hp, Xq, ldq, m, Z, ldz, n, d, u, B, ldb, trans_b, part, nsplit, ct, mrows, xb, nexp);
+    if (u && B) return launch_xgrad<T, DMAX, true, true, PROD>(st, spec, hp, Xq, ldq, m, Z, ldz, n, d, u, B, ldb, trans_b, part, nsplit, ct, mrows, xb, nexp);
+    if (u) return launch_xgrad<T, DMAX, true, false, PROD>(st, spec, hp, Xq, ldq, m, Z, ldz, n, d, u, B, ldb, trans_b, part, nsplit, ct, mrows, xb, nexp);
+    return launch_xgrad<T, DMAX, false, true, PROD>(st, spec, hp, Xq, ldq, m, Z, ldz, n, d, u, B, ldb, trans_b, part, nsplit, ct, mrows, xb, nexp);
 }
 
 template <typename T>
-int pg_xgrad_t(hipStream_t st, int ncu, const pg_covspec& spec, const double* hp, long hp_stride, const T* Xq, long ldq, long xq_stride, int m,
+int pg_xgrad_t(hipStream_t st, int ncu, const pg_covspec& spec_in, const double* hp, long hp_stride, const T* Xq, long ldq, long xq_stride, int m,
                const T* Z, long ldz, long z_stride, int n, int d, const T* u, long u_stride, T* out_u, long ldou, long ou_stride, const T* B,
                long ldb, long b_stride, int trans_b, T* out_b, long ldob, long ob_stride, int accumulate, double* work, long lwork, int nexp) {
+    pg_covspec spec;
+    const bool prod = pg_spec_strip(spec_in, spec);      // a product spec: the kernel's PROD instantiation
     if (m <= 0) return 0;
     if (n <= 0 || spec.ncomp == 0) {      // no training points / no stationary child: the derivative is 0
         if (accumulate) return 0;
@@ -272,12 +313,15 @@ int pg_xgrad_t(hipStream_t st, int ncu, const pg_covspec& spec, const double* hp
     if (lwork < need) { pg_set_error("pg_kernel_xgrad: workspace %ld < %ld doubles", lwork, need); return -3; }
     const long mrows = (long)((m + XT - 1) / XT) * XT;
     const XgradBatch xb = {xq_stride, z_stride, hp_stride, u_stride, b_stride};
-    int rc;
-    if (d <= 4) rc = launch_xgrad_w<T, 4>(st, spec, hp, Xq, ldq, m, Z, ldz, n, d, u, B, ldb, trans_b, work, nsplit, ct, mrows, xb, nexp);
-    else if (d <= 8) rc = launch_xgrad_w<T, 8>(st, spec, hp, Xq, ldq, m, Z, ldz, n, d, u, B, ldb, trans_b, work, nsplit, ct, mrows, xb, nexp);
-    else if (d <= 16) rc = launch_xgrad_w<T, 16>(st, spec, hp, Xq, ldq, m, Z, ldz, n, d, u, B, ldb, trans_b, work, nsplit, ct, mrows, xb, nexp);
-    else if (d <= 32) rc = launch_xgrad_w<T, 32>(st, spec, hp, Xq, ldq, m, Z, ldz, n, d, u, B, ldb, trans_b, work, nsplit, ct, mrows, xb, nexp);
-    else rc = launch_xgrad_w<T, 64>(st, spec, hp, Xq, ldq, m, Z, ldz, n, d, u, B, ldb, trans_b, work, nsplit, ct, mrows, xb, nexp);
+    auto go = [&](auto prod_c) {
+        constexpr bool P = decltype(prod_c)::value;
+        if (d <= 4) return launch_xgrad_w<T, 4, P>(st, spec, hp, Xq, ldq, m, Z, ldz, n, d, u, B, ldb, trans_b, work, nsplit, ct, mrows, xb, nexp);
+        if (d <= 8) return launch_xgrad_w<T, 8, P>(st, spec, hp, Xq, ldq, m, Z, ldz, n, d, u, B, ldb, trans_b, work, nsplit, ct, mrows, xb, nexp);
+        if (d <= 16) return launch_xgrad_w<T, 16, P>(st, spec, hp, Xq, ldq, m, Z, ldz, n, d, u, B, ldb, trans_b, work, nsplit, ct, mrows, xb, nexp);
+        if (d <= 32) return launch_xgrad_w<T, 32, P>(st, spec, hp, Xq, ldq, m, Z, ldz, n, d, u, B, ldb, trans_b, work, nsplit, ct, mrows, xb, nexp);
+        return launch_xgrad_w<T, 64, P>(st, spec, hp, Xq, ldq, m, Z, ldz, n, d, u, B, ldb, trans_b, work, nsplit, ct, mrows, xb, nexp);
+    };
+    const int rc = prod ? go(std::true_type{}) : go(std::false_type{});
     if (rc) return rc;
     hipLaunchKernelGGL(pg_xgrad_reduce_kernel<T>, dim3((unsigned)(((long)m * d + 255) / 256), 2, nexp), dim3(256), 0, st, work, nsplit, m, d,
                        mrows, out_u, ldou, ou_stride, out_b, ldob, ob_stride, accumulate);

@@ -26,7 +26,7 @@ from torch import Tensor
 
 from . import _lib
 from ._ops import JITTER, get_ops, pad_to
-from .covar import Covar, layout, spec_of
+from .covar import Covar, layout, spec_of, terms
 
 _CHUNK = 8192  # test points per device batch
 # Experts of a batched model are factorised in ONE batched call (every launch covers all experts: pg_build_potrf_trtri_batched)
@@ -585,11 +585,19 @@ class Exact_GP(GPR):
 
     def _kss_diag(self, b: int) -> float:
         """diag of cov.kernel(params, xp): sum sigma_c^2 + sum sigma_n^2 (White_noise sees xp=None,
-        gpr.py:98), no jitter."""
-        _, offs, noise, _ = layout(self.cov, self._x.shape[-1])
+        gpr.py:98), no jitter.  A Product term contributes the product of its factors' sigma^2 (formed in list order, as the
+        batched prediction forms it on the device)."""
+        tms, noise, _ = terms(self.cov, self._x.shape[-1])
         hp = self._hp_rows()
         row = hp[b % hp.shape[0]]
-        return float(sum(row[o] ** 2 for o in offs) + sum(row[o] ** 2 for o in noise))
+
+        def prior(offs):
+            v = row[offs[0]] ** 2
+            for o in offs[1:]:
+                v = v * row[o] ** 2
+            return v
+
+        return float(sum(prior(offs) for _, _, offs in tms) + sum(row[o] ** 2 for o in noise))
 
     def _predict_expert(self, b, e, xpd, want):
         ops = get_ops()

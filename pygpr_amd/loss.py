@@ -18,7 +18,7 @@ from numpy import ndarray
 
 from . import _lib
 from ._ops import get_ops
-from .covar import layout, spec_of
+from .covar import spec_of, terms
 from .gpr import _BATCH_EAGER_N, _BATCH_MAX_N, GPR, _checked, _lin_alg_error
 
 
@@ -59,8 +59,9 @@ class _MemoLoss(Loss):
           * after a loss-only evaluation of a single model the FACTOR stays in the work buffers: a following grad(p) at
             the same p only adds L^-1, K^-1 and the contraction (no second covariance build / Cholesky)."""
         m = self.model      # the reference re-reads model.x / .y / .cov on every call: all three are part of the key
+        tms, noise, _ = terms(m.cov, m._x.shape[-1])      # (not layout(): Product([a, b]) and Compose([a, b]) flatten to the same lists)
         key = (np.asarray(params, dtype=np.float64).tobytes(), np.shape(params), id(m._x), m._x._version, id(m._y), m._y._version,
-               id(m.cov), tuple(map(tuple, layout(m.cov, m._x.shape[-1])[:3])))
+               id(m.cov), (tms, tuple(noise)))
         hit = self._memo if (self.memoize and self._memo is not None and self._memo[0] == key) else None
         if hit is not None and (hit[2] is not None or not want_grad):
             return hit[1].copy(), (hit[2].copy() if hit[2] is not None else None)

@@ -29,4 +29,13 @@ for d in (8, 16):
         tb = ev(lambda: ops.kernel_build(spec, hp, x, None, k, lower_only=True, jitter=1e-7))
         tf = ev(lambda: ops.kernel_build(spec, hp, x, None, k, jitter=1e-7))
         print(f"d={d} {name}: nlml_grad {t*1e3:.0f} us; kernel build lower-only {tb*1e3:.0f} us ({4.0*n*(n+64)/tb/1e6:.0f} GB/s), full {tf*1e3:.0f} us ({8.0*n*n/tf/1e6:.0f} GB/s)", flush=True)
+    # Product([se, per]) beside Compose([se, per]) of the same children: the product rule as a weight (the PROD contraction)
+    hp = torch.tensor([1.0] + [0.7] * d + [1.0] + [0.7] * d + [0.3] * d + [0.1], dtype=torch.float64).cuda()
+    for product, name in ((False, "se+per"), (True, "se*per")):
+        spec = make_spec([0, 8], [0, d + 1], [3 * d + 2], product=product)
+        grad = ops.zeros(3 * d + 3); work = ops.empty(ops.nlml_grad_worksize(n, 3 * d + 3))
+        t = ev(lambda: ops.nlml_grad(spec, hp, x, n, kinv, alpha, grad, work))
+        tb = ev(lambda: ops.kernel_build(spec, hp, x, None, k, lower_only=True, jitter=1e-7))
+        tf = ev(lambda: ops.kernel_build(spec, hp, x, None, k, jitter=1e-7))
+        print(f"d={d} {name}: nlml_grad {t*1e3:.0f} us; kernel build lower-only {tb*1e3:.0f} us, full {tf*1e3:.0f} us", flush=True)
     del kinv, k

@@ -22,3 +22,10 @@ for d in (8, 2, 16):
         tl = ev(lambda: ops.kernel_build(spec, hp, x, None, k, lower_only=True, jitter=1e-7))
         tf = ev(lambda: ops.kernel_build(spec, hp, x, None, k, jitter=1e-7))
         print(f"d={d:2d} {name:6s} lower {tl:.3f} ms {(4*n*(n+64)+8*n*d)/tl/1e6:.0f} GB/s   full(mirror) {tf:.3f} ms  {8*n*n/tf/1e6:.0f} GB/s", flush=True)
+    # Product([se, per]) beside Compose([se, per]) of the same children: what multiplying instead of adding costs (the PROD body)
+    hp = torch.tensor([1.0] * (d + 1) + [1.0] * (d + 1) + [0.3] * d + [0.1], dtype=torch.float64).cuda()
+    for product, name in ((False, "se+per"), (True, "se*per")):
+        spec = make_spec([0, 8], [0, d + 1], [3 * d + 2], product=product)
+        tl = ev(lambda: ops.kernel_build(spec, hp, x, None, k, lower_only=True, jitter=1e-7))
+        tf = ev(lambda: ops.kernel_build(spec, hp, x, None, k, jitter=1e-7))
+        print(f"d={d:2d} {name:6s} lower {tl:.3f} ms {(4*n*(n+64)+8*n*d)/tl/1e6:.0f} GB/s   full(mirror) {tf:.3f} ms  {8*n*n/tf/1e6:.0f} GB/s", flush=True)
