@@ -1,6 +1,7 @@
 """The frame helper (tests/framed.py) against NumPy stand-ins, no GPU: one correct "op" that passes every check, and deliberately
 wrong ones, each of which must be caught at the right place.  This is the proof that the framed GPU tests can fail.  Also the
-coverage check: every export of include/pygpr_hip.h that takes a device buffer has a case in tests/test_framed_gpu.py."""
+coverage check: every export of include/pygpr_hip.h that takes a device buffer has a case in tests/test_framed_gpu.py, every export
+that takes a covariance spec has one in tests/test_framed_kinds_gpu.py, and that file's model table holds every kind the library offers."""
 import ast
 import os
 
@@ -194,9 +195,9 @@ PROBES = {"pg_spin_probe", "pg_leaf_raw", "pg_rowstep_raw"}
 WORKSIZES = {n for n in NO_BUFFER if n.endswith("_worksize")}
 
 
-def _gpu_test_names():
-    """Every pg_* name that tests/test_framed_gpu.py calls through the library object (lib.pg_xxx)."""
-    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_framed_gpu.py")
+def _gpu_test_names(module="test_framed_gpu.py"):
+    """Every pg_* name that the test module (tests/test_framed_gpu.py) calls through the library object (lib.pg_xxx)."""
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), module)
     tree = ast.parse(open(path).read())
     return {n.attr for n in ast.walk(tree) if isinstance(n, ast.Attribute) and n.attr.startswith("pg_")}
 
@@ -210,3 +211,68 @@ def test_every_buffer_taking_export_has_a_framed_case():
     used = _gpu_test_names()
     assert sorted(need - used) == [], "exports with a device buffer and no framed case"
     assert sorted(WORKSIZES - used) == [], "worksize exports that no framed case sizes its workspace with"
+
+
+def test_every_spec_taking_export_is_framed_for_every_kind():
+    """The exports with a `const pg_covspec*` parameter are where a kind's block width and offsets are used: each is called in
+    tests/test_framed_kinds_gpu.py, whose models carry the kinds that tests/test_framed_gpu.py's table does not.  A new spec-taking
+    entry point therefore fails here until it has a framed case there."""
+    from pygpr_amd._lib import HEADER, parse_prototypes
+
+    takers = {name for name, (_, params) in parse_prototypes(open(HEADER).read()).items() if "const pg_covspec*" in params}
+    assert {"pg_kernel_build", "pg_kernel_grad_build", "pg_nlml_grad", "pg_kernel_xgrad", "pg_build_potrf_trtri"} <= takers, "the header's parse lost the known ones"
+    used = _gpu_test_names("test_framed_kinds_gpu.py")
+    assert sorted(takers - used) == [], "exports that take a covariance spec and have no framed case for the newer kinds"
+    assert {"pg_nlml_grad_worksize", "pg_kernel_xgrad_worksize", "pg_potrf_worksize"} <= used, "workspaces not sized by their worksize export"
+
+
+def test_framed_model_table_holds_every_kind():
+    """The model table of tests/test_framed_kinds_gpu.py, flattened: every PG_KIND_* of pygpr_amd/_lib.py except PG_KIND_SQDIST (which has
+    its own framed case, test_kernel_grad_build_sqdist_argmin_and_xgrad), at least one product and one model that needs more than one pass.
+    A new kind therefore fails here until a framed model carries it.  The module imports without a GPU."""
+    import product_ref as pr
+    import test_framed_kinds_gpu as fk
+    from pygpr_amd import _lib
+
+    offered = {v for k, v in vars(_lib).items() if k.startswith("PG_KIND_")} - {_lib.PG_KIND_SQDIST}
+    assert len(offered) >= 6
+    assert set(fk.KIND_OF.values()) == offered, "a kind of _lib.py has no part name in the framed model table"
+    held = {fk.KIND_OF[q] for model, _ in fk.MODELS.values() for q in pr.flat(model) if q != "wn"}
+    assert sorted(offered - held) == [], "kinds that no framed model carries"
+    assert any(isinstance(t, tuple) for model, _ in fk.MODELS.values() for t in model), "no product in the framed model table"
+    npass = {mid: len(fk.passes_of(mid)) for mid in fk.MODELS}
+    assert max(npass.values()) > 1, "no multi-pass model in the framed model table"
+    for mid in fk.MODELS:      # a product spec is flagged, its offsets are the library's own layout (asserted inside passes_of)
+        for sp, terms, idx in fk.passes_of(mid):
+            assert bool(sp.ncomp & _lib.PG_SPEC_PRODUCT) == any(isinstance(t, tuple) for t in terms)
+
+
+@pytest.mark.parametrize("mid,slip", [("P1", "period"), ("P2", "period"), ("X1", "period"), ("X2", "period"), ("R2", "width"), ("P2", "width"),
+                                      ("X2", "width")])
+def test_a_block_layout_slip_would_exceed_every_allowance(mid, slip):
+    """Not a test of the library but of the framed models' power, in NumPy on their own inputs (n = 37): the two layout slips that no
+    guard band can see, because they stay inside hp, change K by far more than the widest allowance any case grants (2.5e-5, the fp32
+    build of the three-factor product).  `period`: the periods read at off + d + k instead of off + d + 1 + k (period 1 becomes the
+    last length scale).  `width`: every component behind a block wider than d + 1 read one element early, as if that block were d + 1
+    wide.  (A leading dimension or an expert stride taken for the packed width needs no such argument: every framed operand has a gap
+    of at least one element that holds a quiet NaN, so the slip reads NaN into the arithmetic.)"""
+    import product_ref as pr
+    import test_framed_kinds_gpu as fk
+    from pygpr_amd import _lib
+
+    model, d = fk.MODELS[mid]
+    x, hp, ref = fk.sym_inputs(mid, 37)
+    worst = 0.0
+    for sp, terms, idx in fk.passes_of(mid):
+        bad = hp.copy()
+        nc = sp.ncomp & ~_lib.PG_SPEC_PRODUCT
+        comps = sorted((sp.off[c], sp.kind[c]) for c in range(nc))
+        for j, (o, kind) in enumerate(comps):
+            if slip == "period" and kind == _lib.PG_KIND_PERIODIC:
+                bad[o + d + 1: o + 2 * d + 1] = hp[o + d: o + 2 * d]
+            if slip == "width" and j > 0 and comps[j - 1][1] in (_lib.PG_KIND_RQ, _lib.PG_KIND_PERIODIC):
+                w = 2 * d + 1 if kind == _lib.PG_KIND_PERIODIC else (d + 2 if kind == _lib.PG_KIND_RQ else d + 1)
+                bad[o: o + w] = hp[o - 1: o - 1 + w]
+        if not np.array_equal(bad, hp):
+            worst = max(worst, float(np.abs(pr.kernel(terms, bad[idx], x[:37]) - pr.kernel(terms, hp[idx], x[:37])).max()))
+    assert worst > 100 * 2.5e-5, worst

@@ -13,7 +13,12 @@ exactly pg_*_worksize elements.  Per case and dtype:
 Exemptions from "same bits": none.  Gaps: the smallest legal one (2 fp64 / 4 fp32 elements), 132 (wider than a tile, not a
 multiple of one), and "mixed" (a different gap per operand, so that a swapped ld cannot cancel).  The scalar entry points also run
 with odd gaps (1, 3).  An overrun lands in guard rows the test owns (framed.ROW_GUARD = the tallest tile), so it is detected, not
-faulted on."""
+faulted on.
+
+The kinds of this file's tables are the squared exponential, the Matern family and PG_KIND_SQDIST, whose blocks are all d + 1 wide
+(make_spec below).  The kinds added since -- rational quadratic (d + 2), periodic (2 d + 1), product specs and a sum in two passes --
+are framed in tests/test_framed_kinds_gpu.py (370 tests on this file's harness, by import), through every export that takes a
+covariance spec; tests/test_framed_cpu.py holds that file to the header and to the kinds of pygpr_amd/_lib.py."""
 import ctypes as C
 import functools
 
