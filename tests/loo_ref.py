@@ -1,6 +1,6 @@
 """NumPy / SciPy restatement of leave-one-out cross-validation for an exact GP (Rasmussen & Williams, section 5.4.2), on the kernels of
-tests/matern_ref.py: the reference of the LOO tests.  K = k(x, x) + noise + JITTER I is the matrix Exact_GP.update() factors, so every
-quantity here is predictive for y_i (noise included).
+tests/kernel_ref.py (any model of its grammar): the reference of the LOO tests.  K = k(x, x) + noise + JITTER I is the matrix
+Exact_GP.update() factors, so every quantity here is predictive for y_i (noise included).
 
     closed forms   mu_i = y_i - alpha_i / c_i,  var_i = 1 / c_i,  c = diag(K^-1), alpha = K^-1 y               (5.10 - 5.12)
     brute force    n explicit refits on the other n - 1 points
@@ -11,14 +11,14 @@ quantity here is predictive for y_i (noise included).
 import numpy as np
 import scipy.linalg as sla
 
-import matern_ref as mr
+import kernel_ref as kr
 
 LOG2PI = float(np.log(2.0 * np.pi))
 
 
 def _kmat(parts, hp, x):
-    k = mr.kernel(parts, np.asarray(hp, dtype=np.float64), x)
-    k[np.diag_indices_from(k)] += mr.JITTER
+    k = kr.kernel(parts, np.asarray(hp, dtype=np.float64), x)
+    k[np.diag_indices_from(k)] += kr.JITTER
     return k
 
 
@@ -62,12 +62,17 @@ def loo_loss_and_grad(parts, hp, x, y):
     hp = np.asarray(hp, dtype=np.float64)
     kinv, alpha, c = _solve(parts, hp, x, y)
     loss = float(np.sum(-0.5 * np.log(c) + 0.5 * alpha * alpha / c) + 0.5 * y.shape[0] * LOG2PI)
-    g = np.zeros(hp.size)
-    for j, slab in mr._grad_terms(parts, hp, x):
+    return loss, grad_from(parts, hp, x, kinv, alpha, c)
+
+
+def grad_from(parts, hp, x, kinv, alpha, c):
+    """Eq. 5.13 on a caller's (K^-1, alpha, c): a test that forms K^-1 its own way keeps that route."""
+    g = np.zeros(np.size(hp))
+    for j, slab in kr.grad_terms(parts, hp, x):
         z = kinv @ slab
         zk_diag = np.einsum("ij,ji->i", z, kinv)
         g[j] = -float(np.sum((alpha * (z @ alpha) - 0.5 * (1.0 + alpha * alpha / c) * zk_diag) / c))
-    return loss, g
+    return g
 
 
 def gmatrix(kinv, alpha):
@@ -84,6 +89,6 @@ def grad_gmatrix(parts, hp, x, y):
     kinv, alpha, _ = _solve(parts, hp, x, y)
     g_mat = gmatrix(kinv, alpha)
     g = np.zeros(hp.size)
-    for j, slab in mr._grad_terms(parts, hp, x):
+    for j, slab in kr.grad_terms(parts, hp, x):
         g[j] = 0.5 * float(np.sum(g_mat * slab))
     return g

@@ -2,12 +2,17 @@
 every number produced by NumPy/SciPy (the oracle's arithmetic).  It exists so that the HOST logic --
 shapes, broadcasting, padding, error conventions, optimiser drivers, the multi-rank reductions -- can
 be exercised where there is no GPU.  It lives under tests/ and is never imported by the product; tests
-install it by monkeypatching `pygpr_amd._ops._OPS`."""
+install it by monkeypatching `pygpr_amd._ops._OPS`.  OracleOps knows the kinds the oracle package has;
+KindOracleOps (the `fake_ops` fixture) serves every kind and product specs from tests/kernel_ref.py."""
 import numpy as np
+import pytest
 import scipy.linalg as sla
 import torch
 
 from oracle import pygpr_oracle as orc
+from pygpr_amd import _lib, _ops
+
+import kernel_ref as kr
 
 NB = 128
 
@@ -313,3 +318,69 @@ class OracleOps:
             dist.copy_(torch.from_numpy(d2))
         if idx is not None:
             idx.copy_(torch.from_numpy(np.argmin(d2, axis=1).astype(np.int32)))
+
+
+# ---- every kind: the covariance calls through tests/kernel_ref.py ----------------------------------------------------------------------
+PART_OF_KIND = {0: "se", 1: "m52", 3: "m32", 4: "m12", 6: "rq", 8: "per"}
+
+
+class KindOracleOps(OracleOps):
+    """OracleOps whose covariance calls go through kernel_ref: a flagged spec is one product term, an unflagged one a sum."""
+
+    @staticmethod
+    def _model(spec, hp, d):
+        """(terms, hp) of a standalone model holding the passes' terms: their blocks in pass order, the noise terms behind."""
+        model, noise, index = [], [], []
+        for sp in _passes(spec):
+            parts = []
+            for c in range(sp.ncomp & 0xFF):
+                parts.append(PART_OF_KIND[sp.kind[c]])
+                index += list(range(sp.off[c], sp.off[c] + kr.width(parts[-1], d)))
+            model += [tuple(parts)] if sp.ncomp & _lib.PG_SPEC_PRODUCT else parts
+            noise += [sp.noise_off[i] for i in range(sp.nnoise)]
+        index += noise
+        return model + ["wn"] * len(noise), hp[index], index
+
+    def kernel_build(self, spec, hp, xr, xc, out, lower_only=False, jitter=0.0):
+        x = _np(xr).astype(np.float64)
+        model, h, _ = self._model(spec, _np(hp), x.shape[1])
+        o = _np(out)
+        if xc is None:
+            n = x.shape[0]
+            full = np.eye(o.shape[0])
+            full[:n, :n] = kr.kernel(model, h, x) + jitter * np.eye(n)
+            if lower_only:
+                mask = np.tril(np.ones_like(full, dtype=bool))
+                o[mask] = full[mask]
+            else:
+                o[...] = full
+        else:
+            xq = _np(xc).astype(np.float64)
+            o[...] = 0.0
+            o[: x.shape[0], : xq.shape[0]] = kr.kernel(model, h, xq, x)
+        return out
+
+    def kernel_grad_build(self, spec, hp, x, out):
+        xx = _np(x).astype(np.float64)
+        model, h, index = self._model(spec, _np(hp), xx.shape[1])
+        o = _np(out)
+        o[...] = 0.0
+        o[index] = kr.kernel_and_grad(model, h, xx)[1]
+        return out
+
+    def predict_mean_q_kt_batched(self, kt_all, minv_all, alpha_all, mean_all, var_all, spec, hp_all, work_all):
+        (sp,) = _passes(spec)
+        for e in range(kt_all.shape[0]):
+            h = _np(hp_all[e % hp_all.shape[0]])
+            sig2 = [h[sp.off[c]] ** 2 for c in range(sp.ncomp & 0xFF)]
+            kss = (np.prod(sig2) if sp.ncomp & _lib.PG_SPEC_PRODUCT else sum(sig2)) + sum(h[sp.noise_off[i]] ** 2 for i in range(sp.nnoise))
+            self.predict_mean_q_kt(kt_all[e], minv_all[e] if var_all is not None else None, alpha_all[e], mean_all[e],
+                                   var_all[e] if var_all is not None else None, kss, None)
+
+
+@pytest.fixture
+def fake_ops(monkeypatch, tmp_path):
+    ops = KindOracleOps()
+    monkeypatch.setattr(_ops, "_OPS", ops)
+    monkeypatch.chdir(tmp_path)
+    return ops

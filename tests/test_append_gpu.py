@@ -9,6 +9,7 @@ import pygpr_amd as pg
 from pygpr_amd._ops import JITTER
 
 import append_ref as ar
+from kind_tools import check
 
 pytestmark = pytest.mark.gpu
 
@@ -25,17 +26,6 @@ def ops():
     from pygpr_amd._ops import get_ops
 
     return get_ops()
-
-
-def rel(a, ref):
-    a, ref = torch.as_tensor(a).detach().cpu().double(), torch.as_tensor(ref).detach().cpu().double()
-    return float((a - ref).abs().max() / ref.abs().max().clamp_min(1e-300))
-
-
-def check(name, a, ref, tol):
-    e = rel(a, ref)
-    print("%-52s rel err %.2e (bound %.0e)" % (name, e, tol))
-    assert e <= tol, (name, e)
 
 
 def hp_for(parts, d, rng, noise=0.3):

@@ -230,14 +230,14 @@ def test_framed_model_table_holds_every_kind():
     """The model table of tests/test_framed_kinds_gpu.py, flattened: every PG_KIND_* of pygpr_amd/_lib.py except PG_KIND_SQDIST (which has
     its own framed case, test_kernel_grad_build_sqdist_argmin_and_xgrad), at least one product and one model that needs more than one pass.
     A new kind therefore fails here until a framed model carries it.  The module imports without a GPU."""
-    import product_ref as pr
+    import kernel_ref as kr
     import test_framed_kinds_gpu as fk
     from pygpr_amd import _lib
 
     offered = {v for k, v in vars(_lib).items() if k.startswith("PG_KIND_")} - {_lib.PG_KIND_SQDIST}
     assert len(offered) >= 6
     assert set(fk.KIND_OF.values()) == offered, "a kind of _lib.py has no part name in the framed model table"
-    held = {fk.KIND_OF[q] for model, _ in fk.MODELS.values() for q in pr.flat(model) if q != "wn"}
+    held = {fk.KIND_OF[q] for model, _ in fk.MODELS.values() for q in kr.flat(model) if q != "wn"}
     assert sorted(offered - held) == [], "kinds that no framed model carries"
     assert any(isinstance(t, tuple) for model, _ in fk.MODELS.values() for t in model), "no product in the framed model table"
     npass = {mid: len(fk.passes_of(mid)) for mid in fk.MODELS}
@@ -256,7 +256,7 @@ def test_a_block_layout_slip_would_exceed_every_allowance(mid, slip):
     last length scale).  `width`: every component behind a block wider than d + 1 read one element early, as if that block were d + 1
     wide.  (A leading dimension or an expert stride taken for the packed width needs no such argument: every framed operand has a gap
     of at least one element that holds a quiet NaN, so the slip reads NaN into the arithmetic.)"""
-    import product_ref as pr
+    import kernel_ref as kr
     import test_framed_kinds_gpu as fk
     from pygpr_amd import _lib
 
@@ -274,5 +274,5 @@ def test_a_block_layout_slip_would_exceed_every_allowance(mid, slip):
                 w = 2 * d + 1 if kind == _lib.PG_KIND_PERIODIC else (d + 2 if kind == _lib.PG_KIND_RQ else d + 1)
                 bad[o: o + w] = hp[o - 1: o - 1 + w]
         if not np.array_equal(bad, hp):
-            worst = max(worst, float(np.abs(pr.kernel(terms, bad[idx], x[:37]) - pr.kernel(terms, hp[idx], x[:37])).max()))
+            worst = max(worst, float(np.abs(kr.kernel(terms, bad[idx], x[:37]) - kr.kernel(terms, hp[idx], x[:37])).max()))
     assert worst > 100 * 2.5e-5, worst

@@ -3,7 +3,7 @@ the list against include/pygpr_hip.h).  Framed operands (tests/framed.py) are st
 (ld = width + gap, expert strides larger than minimal, base 16- but not 256-byte aligned) inside sentinel memory, workspaces of
 exactly pg_*_worksize elements.  Per case and dtype:
 
-  value      the logical region against NumPy / tests/matern_ref.py / tests/append_ref.py in fp64 (never another GPU call), at
+  value      the logical region against NumPy / tests/kernel_ref.py / tests/append_ref.py in fp64 (never another GPU call), at
              the tolerance of the existing test of that entry point (cited at each case)
   same bits  as the same call on packed, freshly allocated operands (tiling is by index, not by address)
   guards     every word outside the views still holds the sentinel; inputs bitwise unchanged (gaps included); outputs carry no
@@ -27,7 +27,7 @@ import pytest
 import torch
 
 import append_ref as ar
-import matern_ref as mr
+import kernel_ref as kr
 from framed import SENTINEL32, SENTINEL64, frame, min_gap
 
 pytestmark = pytest.mark.gpu
@@ -312,7 +312,7 @@ def test_kernel_build_symmetric(ops, parts, d, n, dtype, gapset):
     x, hp = rng.random((n + 3, d)), _hp(parts, d, rng)
     npad, tol = 512, _ktol(parts, d, dtype)
     ref = np.eye(npad)
-    ref[:n, :n] = mr.kernel(parts, hp, x[:n]) + 1e-7 * np.eye(n)
+    ref[:n, :n] = kr.kernel(parts, hp, x[:n]) + 1e-7 * np.eye(n)
     spec = make_spec(parts, d)
     pois = np.zeros((n + 3, d), bool)
     pois[n:] = True
@@ -340,7 +340,7 @@ def test_kernel_build_cross_and_accumulate(ops, parts, d, nr, nc, dtype, gapset)
     rp, cp = (512 if nr > 256 else 256), (512 if nc > 256 else 256)
     tol, spec = _ktol(parts, d, dtype), make_spec(parts, d)
     ref = np.zeros((rp, cp))
-    ref[:nr, :nc] = mr.kernel(parts, hp, xc, xr)
+    ref[:nr, :nc] = kr.kernel(parts, hp, xc, xr)
     real = np.zeros((rp, cp), bool)
     real[:nr, :nc] = True
 
@@ -407,7 +407,7 @@ def test_kernel_build_batched(ops, parts, d, dtype, gapset):
         if sym:
             ref = np.stack([np.eye(512)] * ne)
             for e in range(ne):
-                ref[e, :n, :n] = mr.kernel(parts, hps[e], xs[e]) + 1e-7 * np.eye(n)
+                ref[e, :n, :n] = kr.kernel(parts, hps[e], xs[e]) + 1e-7 * np.eye(n)
             k = bed.put("k", shape=(ne, 512, 512), role="out")
             ok(bed, bed.lib.pg_kernel_build_batched(bed.h, bed.code, C.byref(spec), p(hpd), hpd.ld, p(x), x.ld, x.estride, n, None, 0, 0, 0, d, 0,
                                                     1e-7, p(k), k.ld, k.estride, 512, 512, ne, bed.st()))
@@ -415,7 +415,7 @@ def test_kernel_build_batched(ops, parts, d, dtype, gapset):
             q = bed.put("xq", xq)
             ref = np.zeros((ne, 256, 512))
             for e in range(ne):
-                ref[e, :m, :n] = mr.kernel(parts, hps[e], xs[e], xq)
+                ref[e, :m, :n] = kr.kernel(parts, hps[e], xs[e], xq)
             k = bed.put("k", shape=(ne, 256, 512), role="out")
             ok(bed, bed.lib.pg_kernel_build_batched(bed.h, bed.code, C.byref(spec), p(hpd), hpd.ld, p(q), q.ld, 0, m, p(x), x.ld, x.estride, n, d, 0,
                                                     0.0, p(k), k.ld, k.estride, 256, 512, ne, bed.st()))
@@ -740,7 +740,7 @@ def kstate(n, n_pad, seed=0):
     rng = np.random.default_rng(50 + seed + n)
     x = rng.random((n, GD))
     hp = np.array([1.1 + 0.1 * seed, 0.9, 1.2, 0.7, 0.3])
-    K = mr.kernel(GPARTS, hp, x) + 1e-7 * np.eye(n)
+    K = kr.kernel(GPARTS, hp, x) + 1e-7 * np.eye(n)
     y = rng.standard_normal(n)
     L, invd, M, u, alpha = ar.padded_fit(K, y, n_pad, garbage=np.nan)
     yp = np.zeros(n_pad)
@@ -768,7 +768,7 @@ def test_factor_schedules(ops, entry, n, n_pad, mode, gapset, dtype):
     low, up = np.tril(np.ones((n_pad, n_pad), bool)), np.triu(np.ones((n_pad, n_pad), bool), 1)
     spec = make_spec(GPARTS, GD)
     Kp = np.eye(n_pad)
-    Kp[:n, :n] = mr.kernel(GPARTS, s["hp"], s["x"]) + 1e-7 * np.eye(n)
+    Kp[:n, :n] = kr.kernel(GPARTS, s["hp"], s["x"]) + 1e-7 * np.eye(n)
 
     def case(bed):
         ws = int(bed.lib.pg_potrf_worksize(bed.code, n_pad))
@@ -824,7 +824,7 @@ def test_factor_batched(ops, with_x, dtype, gapset):
     spec = make_spec(GPARTS, GD)
     Ks = np.stack([np.eye(n_pad)] * ne)
     for e, s in enumerate(ss):
-        Ks[e, :n, :n] = mr.kernel(GPARTS, s["hp"], s["x"]) + 1e-7 * np.eye(n)
+        Ks[e, :n, :n] = kr.kernel(GPARTS, s["hp"], s["x"]) + 1e-7 * np.eye(n)
 
     def case(bed):
         ws = int(bed.lib.pg_potrf_worksize(bed.code, n_pad))
@@ -915,13 +915,13 @@ def grad_case(pi, n, seed=0):
     parts, d = GRADS[pi]
     rng = np.random.default_rng(7 * n + pi + seed)
     x, hp = rng.random((n, d)), _hp(parts, d, rng)
-    K = mr.kernel(parts, hp, x) + 1e-7 * np.eye(n)
+    K = kr.kernel(parts, hp, x) + 1e-7 * np.eye(n)
     kinv = np.linalg.inv(K)
     kinv = 0.5 * (kinv + kinv.T)
     alpha = kinv @ rng.standard_normal(n)
     w = kinv - np.outer(alpha, alpha)
     g = np.zeros(hp.size)
-    for k, slab in mr._grad_terms(parts, hp, x):
+    for k, slab in kr.grad_terms(parts, hp, x):
         g[k] += 0.5 * (w * slab).sum()
     return x, hp, kinv, alpha, g
 
@@ -1154,7 +1154,7 @@ def test_kernel_grad_build_sqdist_argmin_and_xgrad(ops, dtype, gapset):
     x, hp = rng.random((n, d)), _hp(parts, d, rng)
     spec, nhp = make_spec(parts, d), hp.size
     dk = np.zeros((nhp, n, n))
-    for k, slab in mr._grad_terms(parts, hp, x):
+    for k, slab in kr.grad_terms(parts, hp, x):
         dk[k] += slab
 
     def kgrad(bed):

@@ -6,7 +6,7 @@ frame checks, same bits as the packed call (no exemption), values, and NaN where
 is a quiet NaN, so an over-read of hp, X, u or B that reaches the arithmetic fails the value check.  tests/test_framed_cpu.py checks the
 list of entry points against the header and the model table against the kinds of pygpr_amd/_lib.py.
 
-Reference: tests/product_ref.py in fp64, never another GPU call.  Specs come from pygpr_amd.covar.spec_of, so the block offsets are
+Reference: tests/kernel_ref.py in fp64, never another GPU call.  Specs come from pygpr_amd.covar.spec_of, so the block offsets are
 the library's own layout.  Data in [0, 1)^d; sigma 1.2, inverse length scales 0.4 .. 1.2, periods 0.7 .. 2.5 (a difference of up to
 1 against a period of 0.7: the phase is reduced by a period), alpha 0.8, noise 0.05 .. 0.15 (0.3 where a matrix is factored).
 
@@ -14,7 +14,7 @@ Allowances are those of the packed tests of the same entry point and kind (cited
 5e-6 max(1, |dK|), NLML gradient 1e-8 / 3 x 3e-3 of max|g|, pg_kernel_xgrad 1e-12 / 1e-4 of max|ref|, the factor of a built K
 1e-10 / 2e-5 cond(L); the fp32 build of a product of three or more factors takes the relative rule of
 test_product_gpu.py::test_entry_points_against_the_restatement (F x 4e-6 / 1.44 of max|K|).  Every element-wise allowance goes through
-test_product_gpu.allowance: product_ref's own fp64 error against its long-double evaluation, on at most 64 points (32 test points) of
+test_product_gpu.allowance: kernel_ref's own fp64 error against its long-double evaluation, on at most 64 points (32 test points) of
 the case's inputs, is printed beside it, and the allowance would be four times that error if a quarter of it did not cover the error."""
 import ctypes as C
 import functools
@@ -24,8 +24,9 @@ import pytest
 import torch
 
 import append_ref as ar
-import product_ref as pr
+import kernel_ref as kr
 from framed import min_gap
+from kind_tools import cov_of
 from pygpr_amd import _lib
 from test_framed_gpu import F32, F64, Bed, _ftol, _inv_tol, both, gaps, gaps_odd, kstate, ok, ops, p, ptr_at, run, tiles_low  # noqa: F401  (ops: the fixture)
 from test_product_gpu import allowance
@@ -34,7 +35,7 @@ pytestmark = pytest.mark.gpu
 
 KIND_OF = {"se": _lib.PG_KIND_RBF, "m52": _lib.PG_KIND_MATERN52, "m32": _lib.PG_KIND_MATERN32, "m12": _lib.PG_KIND_MATERN12,
            "rq": _lib.PG_KIND_RQ, "per": _lib.PG_KIND_PERIODIC}
-# id -> (terms, d); a term is a part name or a tuple of factors (tests/product_ref.py).  The route each takes:
+# id -> (terms, d); a term is a part name or a tuple of factors (tests/kernel_ref.py).  The route each takes:
 MODELS = {
     "R1": (["rq", "wn"], 13),                      # matrix-pipe build and gradient bodies (kmfma.hip); block d + 2
     "R2": (["rq", "se", "wn"], 31),                # VALU bodies; the component after a d + 2 block
@@ -49,28 +50,19 @@ SEVEN = ["R1", "R2", "P1", "P2", "X1", "X2", "C1"]
 NE = 3
 
 
-def cov_of(model):
-    import pygpr_amd as pg
-
-    cls = {"per": pg.Periodic, "rq": pg.Rational_quadratic, "se": pg.Squared_exponential, "m52": pg.Matern52, "m32": pg.Matern32,
-           "m12": pg.Matern12, "wn": pg.White_noise}
-    objs = [pg.Product([cls[q]() for q in t]) if isinstance(t, tuple) else cls[t]() for t in model]
-    return objs[0] if len(objs) == 1 else pg.Compose(objs)
-
-
 @functools.lru_cache(maxsize=None)
 def passes_of(mid):
     """[(pg_covspec, terms, idx)] of a model, in the order the library runs them: the spec of the pass, the terms it evaluates and the
-    indices of their parameters in hp (product_ref evaluates `terms` on hp[idx]).  One entry unless the sum holds a product beside a
+    indices of their parameters in hp (kernel_ref evaluates `terms` on hp[idx]).  One entry unless the sum holds a product beside a
     plain child (covar.spec_of: the plain children and the noise first, then one product pass per Product, without noise)."""
     from pygpr_amd.covar import spec_of
 
     model, d = MODELS[mid]
     specs, nhp = spec_of(cov_of(model), d)
-    assert nhp == pr.nhp_of(model, d)
+    assert nhp == kr.nhp_of(model, d)
     blocks, o = [], 0
     for t in model:
-        w = sum(pr.width(q, d) for q in pr.factors(t))
+        w = sum(kr.width(q, d) for q in kr.factors(t))
         blocks.append((t, np.arange(o, o + w)))
         o += w
     if len(specs) == 1:
@@ -83,9 +75,9 @@ def passes_of(mid):
     for sp, terms, idx in out:      # the spec's offsets are the starts of the blocks this pass owns
         nc = sp.ncomp & ~_lib.PG_SPEC_PRODUCT
         starts, o = [], 0
-        for q in pr.flat(terms):
+        for q in kr.flat(terms):
             starts.append(int(idx[o]))
-            o += pr.width(q, d)
+            o += kr.width(q, d)
         assert sorted(list(sp.off[:nc]) + list(sp.noise_off[:sp.nnoise])) == sorted(starts), (mid, terms)
         assert bool(sp.ncomp & _lib.PG_SPEC_PRODUCT) == any(isinstance(t, tuple) for t in terms)
     return out
@@ -99,7 +91,7 @@ def one_spec(mid):
 
 def hp_of(model, d, rng, noise=None):
     out = []
-    for q in pr.flat(model):
+    for q in kr.flat(model):
         if q == "wn":
             out.append([0.05 + 0.1 * rng.random() if noise is None else noise])
             continue
@@ -129,14 +121,14 @@ def k_tol(mid, dtype, ref, hp, x, xp=None):
     of max|K| (test_entry_points_against_the_restatement).  A sum evaluated in two passes rounds each pass to fp32 once and then adds
     them: one fp32 allowance per pass, the rule test_framed_gpu.test_kernel_build_cross_and_accumulate applies to its second pass."""
     model, d = MODELS[mid]
-    nf = max(len(pr.factors(t)) for t in model)
+    nf = max(len(kr.factors(t)) for t in model)
     if dtype == F64:
         tol = 1e-13
     else:
         tol = (nf * (4e-6 / 1.44) * float(np.abs(ref).max()) if nf >= 3 else 4e-6) * len(passes_of(mid))
     s, sp = x[:64], (None if xp is None else xp[:32])
-    tol, err = allowance(tol, pr.kernel(model, hp, s, sp), pr.kernel(model, hp, s, sp, dtype=np.longdouble))
-    print("%s %s K: allowance %.2e, product_ref's own error %.2e" % (mid, "f64" if dtype == F64 else "f32", tol, err))
+    tol, err = allowance(tol, kr.kernel(model, hp, s, sp), kr.kernel(model, hp, s, sp, dtype=np.longdouble))
+    print("%s %s K: allowance %.2e, kernel_ref's own error %.2e" % (mid, "f64" if dtype == F64 else "f32", tol, err))
     return tol
 
 
@@ -152,7 +144,7 @@ def sym_inputs(mid, n):
     rng = np.random.default_rng(1000 * n + d)
     x, hp = rng.random((n + 3, d)), hp_of(model, d, rng)
     ref = np.eye(512)
-    ref[:n, :n] = pr.kernel(model, hp, x[:n]) + 1e-7 * np.eye(n)
+    ref[:n, :n] = kr.kernel(model, hp, x[:n]) + 1e-7 * np.eye(n)
     return x, hp, ref
 
 
@@ -195,7 +187,7 @@ def cross_inputs(mid, nr, nc):
     model, d = MODELS[mid]
     rng = np.random.default_rng(100 * nr + nc + d)
     xr, xc, hp = rng.random((nr, d)), rng.random((nc, d)), hp_of(model, d, rng)
-    return xr, xc, hp, pr.kernel(model, hp, xc, xr)
+    return xr, xc, hp, kr.kernel(model, hp, xc, xr)
 
 
 def cross_case(mid, nr, nc, dtype, seen=None):
@@ -268,8 +260,8 @@ def test_kernel_build_batched(ops, mid, dtype, gapset):
     spec = one_spec(mid)
     rs, rc = np.stack([np.eye(512)] * NE), np.zeros((NE, 256, 512))
     for e in range(NE):
-        rs[e, :n, :n] = pr.kernel(model, hps[e], xs[e]) + 1e-7 * np.eye(n)
-        rc[e, :m, :n] = pr.kernel(model, hps[e], xs[e], xq)
+        rs[e, :n, :n] = kr.kernel(model, hps[e], xs[e]) + 1e-7 * np.eye(n)
+        rc[e, :m, :n] = kr.kernel(model, hps[e], xs[e], xq)
     tol = max(k_tol(mid, dtype, rs[0, :n, :n], hps[0], xs[0]), k_tol(mid, dtype, rc[0, :m, :n], hps[0], xs[0], xq))
 
     def case(bed, sym):
@@ -326,8 +318,8 @@ def dk_inputs(mid, n=70):
     model, d = MODELS[mid]
     rng = np.random.default_rng(12 + d)
     x, hp = rng.random((n, d)), hp_of(model, d, rng)
-    dk = pr.kernel_and_grad(model, hp, x)[1]
-    own = (pr.kernel_and_grad(model, hp, x[:64])[1], pr.kernel_and_grad(model, hp, x[:64], dtype=np.longdouble)[1])
+    dk = kr.kernel_and_grad(model, hp, x)[1]
+    own = (kr.kernel_and_grad(model, hp, x[:64])[1], kr.kernel_and_grad(model, hp, x[:64], dtype=np.longdouble)[1])
     return x, hp, dk, own
 
 
@@ -335,14 +327,14 @@ def dk_inputs(mid, n=70):
 @gaps_odd
 @pytest.mark.parametrize("mid", ["R2", "P2", "X1", "X2"])
 def test_kernel_grad_build(ops, mid, dtype, gapset):
-    """The whole dK stack (contiguous by contract: only X is strided, odd ldx included) against product_ref.kernel_and_grad.
+    """The whole dK stack (contiguous by contract: only X is strided, odd ldx included) against kernel_ref.kernel_and_grad.
     Allowances: 1e-12 (test_rq_gpu / test_periodic_gpu / test_product_gpu); fp32 5e-6 max(1, |dK|) (test_product_gpu)."""
     model, d = MODELS[mid]
     n = 70
     x, hp, dk, own = dk_inputs(mid)
     spec, nhp = one_spec(mid), hp.size
     tol, err = allowance(1e-12 if dtype == F64 else 5e-6 * max(1.0, float(np.abs(dk).max())), *own)
-    print("%s %s dK: allowance %.2e, product_ref's own error %.2e" % (mid, "f64" if dtype == F64 else "f32", tol, err))
+    print("%s %s dK: allowance %.2e, kernel_ref's own error %.2e" % (mid, "f64" if dtype == F64 else "f32", tol, err))
 
     def case(bed):
         xd, hpd = bed.put("x", x), bed.put("hp", hp, dtype=F64)
@@ -355,29 +347,29 @@ def test_kernel_grad_build(ops, mid, dtype, gapset):
 
 # ------------------------------------------------------------------------------------------- 5 / 6. pg_nlml_grad, pg_nlml_grad_batched
 @functools.lru_cache(maxsize=None)
-def grad_inputs(mid, n=333, seed=0):
-    """x, hp, K^-1, alpha, the gradient 1/2 sum (K^-1 - a a^T) o dK_k from product_ref's slabs (test_framed_gpu.grad_case), and the
+def gradient_inputs(mid, n=333, seed=0):
+    """x, hp, K^-1, alpha, the gradient 1/2 sum (K^-1 - a a^T) o dK_k from kernel_ref's slabs (test_framed_gpu.grad_case), and the
     reference's own error in that contraction on the first 64 points, relative to max|g| like the check."""
     model, d = MODELS[mid]
     rng = np.random.default_rng(7 * n + d + seed)
     x, hp = rng.random((n, d)), hp_of(model, d, rng)
-    kinv = np.linalg.inv(pr.kernel(model, hp, x) + 1e-7 * np.eye(n))
+    kinv = np.linalg.inv(kr.kernel(model, hp, x) + 1e-7 * np.eye(n))
     kinv = 0.5 * (kinv + kinv.T)
     alpha = kinv @ rng.standard_normal(n)
     w = kinv - np.outer(alpha, alpha)
     g = np.zeros(hp.size)
-    for k, slab in pr._grad_terms(model, hp, x):
+    for k, slab in kr.grad_terms(model, hp, x):
         g[k] += 0.5 * (w * slab).sum()
     ws = w[:64, :64]
-    g64 = 0.5 * np.einsum("ij,pij->p", ws, pr.kernel_and_grad(model, hp, x[:64])[1])
-    gld = 0.5 * np.einsum("ij,pij->p", ws.astype(np.longdouble), pr.kernel_and_grad(model, hp, x[:64], dtype=np.longdouble)[1])
+    g64 = 0.5 * np.einsum("ij,pij->p", ws, kr.kernel_and_grad(model, hp, x[:64])[1])
+    gld = 0.5 * np.einsum("ij,pij->p", ws.astype(np.longdouble), kr.kernel_and_grad(model, hp, x[:64], dtype=np.longdouble)[1])
     return x, hp, kinv, alpha, g, float(np.abs(g64 - gld).max() / np.abs(g64).max())
 
 
 def g_tol(mid, dtype, err):
     """test_product_gpu: 1e-8 of max|g| (or four times the reference's own error), fp32 3 x 3e-3; rtol = tol, atol = tol max|g|."""
     tol = max(1e-8, 4.0 * err) if dtype == F64 else 3 * 3e-3
-    print("%s %s gradient: allowance %.2e of max|g|, product_ref's own error %.2e" % (mid, "f64" if dtype == F64 else "f32", tol, err))
+    print("%s %s gradient: allowance %.2e of max|g|, kernel_ref's own error %.2e" % (mid, "f64" if dtype == F64 else "f32", tol, err))
     return tol
 
 
@@ -385,7 +377,7 @@ def grad_case(mid, dtype, i, seen=None):
     """Pass i of the model's gradient: it writes the entries of its own children and leaves the others' bits alone."""
     model, d = MODELS[mid]
     n, n_pad = 333, 512
-    x, hp, kinv, alpha, g, err = grad_inputs(mid)
+    x, hp, kinv, alpha, g, err = gradient_inputs(mid)
     kp, ap = np.eye(n_pad), np.zeros(n_pad)
     kp[:n, :n], ap[:n] = kinv, alpha
     sp, _, idx = passes_of(mid)[i]
@@ -440,7 +432,7 @@ def test_nlml_grad_batched(ops, mid, dtype, gapset):
     exactly nexp * pg_nlml_grad_worksize (test_framed_gpu.test_nlml_grad_batched_values)."""
     model, d = MODELS[mid]
     n, n_pad = 333, 512
-    cs = [grad_inputs(mid, n, e) for e in range(NE)]
+    cs = [gradient_inputs(mid, n, e) for e in range(NE)]
     spec, nhp = one_spec(mid), cs[0][1].size
     kp, ap = np.stack([np.eye(n_pad)] * NE), np.zeros((NE, n_pad))
     for e, c in enumerate(cs):
@@ -467,11 +459,11 @@ def test_nlml_grad_batched(ops, mid, dtype, gapset):
 # ------------------------------------------------------------------------------------------- 7. pg_build_potrf_trtri, _checked, _batched
 @functools.lru_cache(maxsize=None)
 def fit_state(mid, n, n_pad, seed=0):
-    """test_framed_gpu.kstate on a model of the table: noise 0.3, K = product_ref.kernel + 1e-7 I, its padded fit (append_ref.padded_fit)."""
+    """test_framed_gpu.kstate on a model of the table: noise 0.3, K = kernel_ref.kernel + 1e-7 I, its padded fit (append_ref.padded_fit)."""
     model, d = MODELS[mid]
     rng = np.random.default_rng(50 + seed + n + d)
     x, hp = rng.random((n, d)), hp_of(model, d, rng, noise=0.3)
-    K = pr.kernel(model, hp, x) + 1e-7 * np.eye(n)
+    K = kr.kernel(model, hp, x) + 1e-7 * np.eye(n)
     L, invd, M, u, alpha = ar.padded_fit(K, rng.standard_normal(n), n_pad, garbage=np.nan)
     return dict(x=x, hp=hp, L=np.nan_to_num(L), M=np.nan_to_num(M), invd=invd, condL=float(np.sqrt(np.linalg.cond(K))))
 
@@ -538,12 +530,12 @@ def xg_inputs(mid, m=37, n=70):
     us, bs = rng.standard_normal((NE, n)), rng.standard_normal((NE, m, n))
     ref_u, ref_b = np.zeros((NE, m, d)), np.zeros((NE, m, d))
     for e in range(NE):
-        dks = pr.kernel_xgrad(model, hps[e], zs[e], xq)                       # [d, m, n]
+        dks = kr.kernel_xgrad(model, hps[e], zs[e], xq)                       # [d, m, n]
         ref_u[e], ref_b[e] = np.einsum("kpi,i->pk", dks, us[e]), np.einsum("kpi,pi->pk", dks, bs[e])
     # the reference's own error in the contraction on 64 x 32 of expert 0's pairs, relative to the largest entry like the check
     b0 = bs[0][:32, :64]
-    s64 = np.einsum("kpi,pi->pk", pr.kernel_xgrad(model, hps[0], zs[0][:64], xq[:32]), b0)
-    sld = np.einsum("kpi,pi->pk", pr.kernel_xgrad(model, hps[0], zs[0][:64], xq[:32], dtype=np.longdouble), b0.astype(np.longdouble))
+    s64 = np.einsum("kpi,pi->pk", kr.kernel_xgrad(model, hps[0], zs[0][:64], xq[:32]), b0)
+    sld = np.einsum("kpi,pi->pk", kr.kernel_xgrad(model, hps[0], zs[0][:64], xq[:32], dtype=np.longdouble), b0.astype(np.longdouble))
     return xq, zs, hps, us, bs, ref_u, ref_b, float(np.abs(s64 - sld).max() / np.abs(s64).max())
 
 
@@ -561,7 +553,7 @@ def test_kernel_xgrad_batched(ops, mid, trans_b, dtype, gapset):
     xq, zs, hps, us, bs, ref_u, ref_b, err = xg_inputs(mid)
     spec = one_spec(mid)
     tol = max(1e-12, 4.0 * err) if dtype == F64 else 1e-4
-    print("%s %s xgrad: allowance %.2e of max|ref|, product_ref's own error %.2e" % (mid, "f64" if dtype == F64 else "f32", tol, err))
+    print("%s %s xgrad: allowance %.2e of max|ref|, kernel_ref's own error %.2e" % (mid, "f64" if dtype == F64 else "f32", tol, err))
     upad, umask = np.zeros((NE, n + 5)), np.zeros((NE, n + 5), bool)
     upad[:, :n], umask[:, n:] = us, True
     stored = bs.transpose(0, 2, 1) if trans_b else bs
@@ -600,7 +592,7 @@ def test_predict_batched_prior_variance(ops, mid, dtype, gapset):
     ss = [kstate(n, n_pad, e) for e in range(NE)]
     rng = np.random.default_rng(m + d)
     hps = np.stack([hp_of(model, d, rng) for _ in range(NE)])
-    kss = np.array([pr.kernel(model, hps[e], np.zeros((1, d)))[0, 0] for e in range(NE)])      # one point against itself: the prior variance
+    kss = np.array([kr.kernel(model, hps[e], np.zeros((1, d)))[0, 0] for e in range(NE)])      # one point against itself: the prior variance
     blk = tiles_low(n_pad, n_pad)
     kts = np.zeros((NE, m_pad, n_pad))
     kts[:, :m, :n] = rng.standard_normal((NE, m, n))

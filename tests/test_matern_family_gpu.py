@@ -1,5 +1,5 @@
 """GPU tier of the Matern family: Matern-1/2 and Matern-3/2 through every covariance path (C ABI entry points, the dK stack, the
-fused gradient, Exact_GP / MLE / batched experts / GRBCM / SK_WRAP) against the direct-difference restatement of tests/matern_ref.py.
+fused gradient, Exact_GP / MLE / batched experts / GRBCM / SK_WRAP) against the direct-difference restatement of tests/kernel_ref.py.
 Matern-3/2 takes the matrix-pipe bodies where Matern-5/2 does; Matern-1/2 never does (its K is 1 - r near r = 0, so the expansion's
 error in the squared distance would reach K as a square root): the near-duplicate test below is the one that says so."""
 import numpy as np
@@ -9,83 +9,10 @@ import torch
 import pygpr_amd as pg
 from oracle import pygpr_oracle as orc
 
-import matern_ref as mr
+import kernel_ref as kr
+from kind_tools import N, T, builds, compose, dev, grad_inputs, host, near_duplicates, one_spec, ops  # noqa: F401  (ops: the fixture)
 
 pytestmark = pytest.mark.gpu
-
-CLS = {"m12": pg.Matern12, "m32": pg.Matern32, "m52": pg.Matern52, "se": pg.Squared_exponential, "wn": pg.White_noise}
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from pygpr_amd._ops import get_ops
-
-    return get_ops()
-
-
-def dev(a, dtype=torch.float64):
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda", dtype)
-
-
-def host(t):
-    return t.detach().cpu().double().numpy()
-
-
-def T(a):
-    return torch.from_numpy(np.ascontiguousarray(a))
-
-
-def N(t):
-    return t.detach().cpu().numpy()
-
-
-def compose(parts):
-    return pg.Compose([CLS[p]() for p in parts])
-
-
-def _spec(parts, d):
-    from pygpr_amd.covar import spec_of
-
-    specs, _ = spec_of(compose(parts), d)
-    assert len(specs) == 1
-    return specs[0]
-
-
-def _grad_inputs(ops, parts, hp, x, y, dtype):
-    """K^-1 (lower) and alpha of the model on the device, in `dtype` (as tests/test_hip_kernels.py builds them)."""
-    from pygpr_amd._ops import pad_to
-
-    n, d = x.shape
-    npad = pad_to(n)
-    spec = _spec(parts, d)
-    hpd, xd = dev(hp), dev(x, dtype)
-    k = ops.empty(npad, npad, dtype=dtype)
-    invd = ops.potrf_workspace(npad, dtype)
-    info = torch.zeros(1, dtype=torch.int32, device="cuda")
-    minv = ops.zeros(npad, npad, dtype=dtype)
-    ops.build_factor(spec, hpd, xd, k, invd, info, minv)
-    assert int(info.item()) == 0
-    ypad = ops.zeros(npad, dtype=dtype)
-    ypad[:n] = dev(y, dtype)
-    u, alpha = ops.empty(npad, dtype=dtype), ops.empty(npad, dtype=dtype)
-    ops.trmv(minv, ypad, u, 0)
-    ops.trmv(minv, u, alpha, 1, ops.empty((npad // 256 + 1) * npad, dtype=dtype))
-    kinv = ops.zeros(npad, npad, dtype=dtype)
-    ops.lauum(minv, kinv)
-    return spec, hpd, xd, kinv, alpha
-
-
-def _builds(ops, spec, hp, x, xp, dtype):
-    from pygpr_amd._ops import pad_to
-
-    n, m = x.shape[0], xp.shape[0]
-    npad, mpad = pad_to(n), pad_to(m)
-    hpd, xd, xpd = dev(hp), dev(x, dtype), dev(xp, dtype)
-    full, low, cross = ops.empty(npad, npad, dtype=dtype), ops.zeros(npad, npad, dtype=dtype), ops.empty(mpad, npad, dtype=dtype)
-    ops.kernel_build(spec, hpd, xd, None, full, jitter=1e-7)
-    ops.kernel_build(spec, hpd, xd, None, low, lower_only=True, jitter=1e-7)
-    ops.kernel_build(spec, hpd, xpd, xd, cross)
-    return host(full), host(low), host(cross)
 
 
 # --------------------------------------------------------------------------- 1. entry points
@@ -102,14 +29,14 @@ def test_entry_points_against_the_restatement(ops, monkeypatch, part, d):
     xp = rng.random((m, d))
     parts = [part, "wn"]
     hp = np.concatenate([[1.2], 0.4 + 0.8 * rng.random(d), [0.1]])
-    spec, npad = _spec(parts, d), pad_to(n)
-    ref = mr.kernel(parts, hp, x) + 1e-7 * np.eye(n)
-    ref_x = mr.kernel(parts, hp, x, xp)
+    spec, npad = one_spec(parts, d), pad_to(n)
+    ref = kr.kernel(parts, hp, x) + 1e-7 * np.eye(n)
+    ref_x = kr.kernel(parts, hp, x, xp)
     for dtype, tol in ((torch.float64, 2e-14), (torch.float32, 4e-6)):
         out = {}
         for mode in ("2", "0"):
             monkeypatch.setenv("PG_KB_MFMA", mode)
-            out[mode] = _builds(ops, spec, hp, x, xp, dtype)
+            out[mode] = builds(ops, spec, hp, x, xp, dtype)
         monkeypatch.delenv("PG_KB_MFMA")
         full, low, cross = out["2"]
         np.testing.assert_allclose(full[:n, :n], ref, atol=tol, rtol=tol)
@@ -129,10 +56,10 @@ def test_entry_points_against_the_restatement(ops, monkeypatch, part, d):
         assert np.array_equal(low[tl], full[tl])                                  # lower-only == mirrored on the lower triangle
         dgv = np.float64(np.float32(1.2 ** 2 + 0.1 ** 2 + 1e-7)) if dtype == torch.float32 else 1.2 ** 2 + 0.1 ** 2 + 1e-7
         np.testing.assert_allclose(np.diag(full)[:n], dgv, rtol=2e-7 if dtype == torch.float32 else 1e-15)
-    _, grad_ref = mr.nlml_and_grad(parts, hp, x, y)
+    _, grad_ref = kr.nlml_and_grad(parts, hp, x, y)
     scale = np.abs(grad_ref).max()
     for dtype, rtol in ((torch.float64, 1e-9), (torch.float32, 3e-3)):
-        spec, hpd, xd, kinv, alpha = _grad_inputs(ops, parts, hp, x, y, dtype)
+        hpd, xd, kinv, alpha = grad_inputs(ops, spec, hp, x, y, dtype)
         work = ops.empty(ops.nlml_grad_worksize(n, hp.size))
         got = {}
         for mode in ("1", "0"):
@@ -152,17 +79,6 @@ def test_entry_points_against_the_restatement(ops, monkeypatch, part, d):
 
 
 # --------------------------------------------------------------------------- 2. near-duplicates
-def _near_duplicates(rng, d, l, offset):
-    """60 points, then five more at scaled distance r = 0, 1e-12, 1e-9, 1e-6, 1e-3 from points 3, 11, 19, 27, 35 (off-diagonal pairs)."""
-    x = rng.random((60, d))
-    extra = []
-    for s, i in zip((0.0, 1e-12, 1e-9, 1e-6, 1e-3), (3, 11, 19, 27, 35)):
-        u = rng.standard_normal(d)
-        extra.append(x[i] + s * (u / np.linalg.norm(u)) / l)
-    x = np.concatenate([x, np.array(extra)]) + offset
-    return x, np.sin(-x.sum(1)) + 0.1 * rng.standard_normal(x.shape[0])
-
-
 def test_matern12_near_duplicates_on_offset_data(ops, monkeypatch):
     """Near-duplicate pairs on data offset by 1e3.  Direct differences keep K to rounding (the matrix pipe's expansion would be off by
     ~sqrt(u) |x|: 1e-8 in fp64), and the gradient's factor 1/r stays bounded.  The inverse length scales are powers of two, so the
@@ -172,22 +88,22 @@ def test_matern12_near_duplicates_on_offset_data(ops, monkeypatch):
     l = np.array([0.5, 1.0, 2.0, 0.25, 1.0])
     hp = np.concatenate([[1.2], l, [0.1]])
     parts = ["m12", "wn"]
-    x, y = _near_duplicates(rng, d, l, 1.0e3)
+    x, y = near_duplicates(rng, d, l, 1.0e3)
     n = x.shape[0]
-    spec = _spec(parts, d)
+    spec = one_spec(parts, d)
     for mode in ("1", "2"):
         monkeypatch.setenv("PG_KB_MFMA", mode)
         monkeypatch.setenv("PG_GRAD_MFMA", mode)
         for dtype, tol in ((torch.float64, 1e-13), (torch.float32, 4e-6)):
             xt = x if dtype == torch.float64 else x.astype(np.float32).astype(np.float64)     # the fp32 run's own inputs
-            ref = mr.kernel(parts, hp, xt)
+            ref = kr.kernel(parts, hp, xt)
             k = ops.empty(256, 256, dtype=dtype)
             ops.kernel_build(spec, dev(hp), dev(xt, dtype), None, k)
             np.testing.assert_allclose(host(k)[:n, :n], ref, rtol=0, atol=tol)
             kx = ops.empty(128, 256, dtype=dtype)
             ops.kernel_build(spec, dev(hp), dev(xt[::-1].copy(), dtype), dev(xt, dtype), kx)     # a cross build meets the same pairs
-            np.testing.assert_allclose(host(kx)[:n, :n], mr.kernel(parts, hp, xt, xt[::-1].copy()), rtol=0, atol=tol)
-        loss_ref, grad_ref = mr.nlml_and_grad(parts, hp, x, y)
+            np.testing.assert_allclose(host(kx)[:n, :n], kr.kernel(parts, hp, xt, xt[::-1].copy()), rtol=0, atol=tol)
+        loss_ref, grad_ref = kr.nlml_and_grad(parts, hp, x, y)
         gp = pg.Exact_GP(T(x), T(y), compose(parts))
         loss, grad = pg.MLE(gp).loss_and_grad(hp.copy())
         assert np.isfinite(grad).all()
@@ -195,12 +111,12 @@ def test_matern12_near_duplicates_on_offset_data(ops, monkeypatch):
         np.testing.assert_allclose(grad, grad_ref, rtol=1e-9, atol=1e-9 * np.abs(grad_ref).max())
         _, dk = compose(parts).kernel_and_grad(T(hp), T(x))
         assert np.isfinite(N(dk)).all()
-        np.testing.assert_allclose(N(dk), mr.kernel_and_grad(parts, hp, x)[1], rtol=0, atol=1e-12)
+        np.testing.assert_allclose(N(dk), kr.kernel_and_grad(parts, hp, x)[1], rtol=0, atol=1e-12)
         # prediction AT the training points: every pair of the cross build is a near-duplicate or a duplicate
         gp = pg.Exact_GP(T(x), T(y), compose(parts))
         gp.set_params(T(hp))
         mu, var = gp.predict(T(x), var="diag")
-        mu_ref, var_ref = mr.predict(parts, hp, x, y, x)
+        mu_ref, var_ref = kr.predict(parts, hp, x, y, x)
         np.testing.assert_allclose(N(mu), mu_ref, rtol=0, atol=1e-10)
         np.testing.assert_allclose(N(var), var_ref, rtol=0, atol=1e-10)
 
@@ -214,14 +130,14 @@ def test_multi_component(parts):
     xp = rng.random((m, d))
     hp = np.concatenate([[1.1], 0.5 + rng.random(d), [0.8], 0.5 + rng.random(d), [0.1]])
     cov = compose(parts)
-    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x))), mr.kernel(parts, hp, x), rtol=0, atol=1e-13)
-    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x), T(xp))), mr.kernel(parts, hp, x, xp), rtol=0, atol=1e-13)
+    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x))), kr.kernel(parts, hp, x), rtol=0, atol=1e-13)
+    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x), T(xp))), kr.kernel(parts, hp, x, xp), rtol=0, atol=1e-13)
     k, dk = cov.kernel_and_grad(T(hp), T(x))
-    k_ref, dk_ref = mr.kernel_and_grad(parts, hp, x)
+    k_ref, dk_ref = kr.kernel_and_grad(parts, hp, x)
     np.testing.assert_allclose(N(k), k_ref, rtol=0, atol=1e-13)
     np.testing.assert_allclose(N(dk), dk_ref, rtol=0, atol=1e-12)
     loss, grad = pg.MLE(pg.Exact_GP(T(x), T(y), cov)).loss_and_grad(hp.copy())
-    loss_ref, grad_ref = mr.nlml_and_grad(parts, hp, x, y)
+    loss_ref, grad_ref = kr.nlml_and_grad(parts, hp, x, y)
     np.testing.assert_allclose(loss, loss_ref, rtol=1e-10)
     np.testing.assert_allclose(grad, grad_ref, rtol=1e-8, atol=1e-8 * np.abs(grad_ref).max())
 
@@ -238,7 +154,7 @@ def test_nan_coordinate_gives_a_nan_row_and_column(ops, monkeypatch, part):
         monkeypatch.setenv("PG_KB_MFMA", mode)
         for dt in (torch.float64, torch.float32):
             k = ops.empty(256, 256, dtype=dt)
-            ops.kernel_build(_spec([part, "wn"], d), dev(hp), dev(x, dt), None, k, jitter=1e-7)
+            ops.kernel_build(one_spec([part, "wn"], d), dev(hp), dev(x, dt), None, k, jitter=1e-7)
             got = host(k)
             assert np.isnan(got[23, :n]).all() and np.isnan(got[:n, 23]).all()
             assert np.isfinite(np.delete(np.delete(got[:n, :n], 23, 0), 23, 1)).all()
@@ -257,15 +173,15 @@ def test_exact_gp_and_mle(part):
     gp.set_params(T(hp))
     gp.update()
     mu, var = gp.predict(T(xp), var="diag")
-    mu_ref, var_ref = mr.predict(parts, hp, x, y, xp)
+    mu_ref, var_ref = kr.predict(parts, hp, x, y, xp)
     np.testing.assert_allclose(N(mu), mu_ref, rtol=0, atol=1e-10)
     np.testing.assert_allclose(N(var), var_ref, rtol=0, atol=1e-10)
     mu_f, cov_f = gp.predict(T(xp), var="full")
-    _, cov_ref = mr.predict(parts, hp, x, y, xp, var="full")
+    _, cov_ref = kr.predict(parts, hp, x, y, xp, var="full")
     np.testing.assert_allclose(N(mu_f), mu_ref, rtol=0, atol=1e-10)
     np.testing.assert_allclose(N(cov_f), cov_ref, rtol=0, atol=1e-10)
     loss, grad = pg.MLE(gp).loss_and_grad(hp.copy())
-    loss_ref, grad_ref = mr.nlml_and_grad(parts, hp, x, y)
+    loss_ref, grad_ref = kr.nlml_and_grad(parts, hp, x, y)
     np.testing.assert_allclose(loss, loss_ref, rtol=1e-10)
     np.testing.assert_allclose(grad, grad_ref, rtol=1e-8, atol=1e-8 * np.abs(grad_ref).max())
 
@@ -292,7 +208,7 @@ def test_batched_experts_match_their_loop(part):
         l1, g1 = pg.MLE(one).loss_and_grad(hp[c].copy())
         np.testing.assert_allclose(loss[c], l1, rtol=1e-11)
         np.testing.assert_allclose(grad[c], g1, rtol=1e-9, atol=1e-9 * np.abs(g1).max())
-        l_ref, g_ref = mr.nlml_and_grad(parts, hp[c], x[c], y[c])
+        l_ref, g_ref = kr.nlml_and_grad(parts, hp[c], x[c], y[c])
         np.testing.assert_allclose(l1, l_ref, rtol=1e-10)
         np.testing.assert_allclose(g1, g_ref, rtol=1e-8, atol=1e-8 * np.abs(g_ref).max())
 
@@ -309,7 +225,7 @@ def test_grbcm_with_matern32():
     model.gpg.set_params(T(hp_g))
     model.gpl.set_params(T(hp_l))
     mu, var = model.predict(T(xs), var="diag")
-    mu_ref, var_ref = mr.grbcm_predict(parts, hp_g, hp_l, xl, yl, xg, yg, xs)
+    mu_ref, var_ref = kr.grbcm_predict(parts, hp_g, hp_l, xl, yl, xg, yg, xs)
     np.testing.assert_allclose(N(mu), mu_ref, rtol=0, atol=1e-9)
     np.testing.assert_allclose(N(var).ravel(), var_ref, rtol=1e-9, atol=1e-11)
 
@@ -324,7 +240,7 @@ def test_sk_wrap_with_matern12():
     gp = pg.Exact_GP(T(x[:10]), T(y[:10]), compose(parts))
     gp.set_params(T(hp))
     sk = pg.SK_WRAP(gp).fit(T(x), T(y))
-    np.testing.assert_allclose(N(sk.predict(T(xp))), mr.predict(parts, hp, x, y, xp)[0], rtol=0, atol=1e-10)
+    np.testing.assert_allclose(N(sk.predict(T(xp))), kr.predict(parts, hp, x, y, xp)[0], rtol=0, atol=1e-10)
 
 
 # --------------------------------------------------------------------------- 6. at size
@@ -335,7 +251,7 @@ def test_nlml_and_gradient_at_n4096(part):
     parts = [part, "wn"]
     hp = np.concatenate([[1.0], np.linspace(0.6, 1.4, d), [0.1]])
     loss, grad = pg.MLE(pg.Exact_GP(T(x), T(y), compose(parts))).loss_and_grad(hp.copy())
-    loss_ref, grad_ref = mr.nlml_and_grad(parts, hp, x, y)
+    loss_ref, grad_ref = kr.nlml_and_grad(parts, hp, x, y)
     np.testing.assert_allclose(loss, loss_ref, rtol=1e-10)
     np.testing.assert_allclose(grad, grad_ref, rtol=1e-8, atol=1e-8 * np.abs(grad_ref).max())
 

@@ -1,4 +1,4 @@
-"""CPU tier of the periodic kernel: the NumPy restatement of tests/periodic_ref.py against central differences of itself, against
+"""CPU tier of the periodic kernel: the NumPy restatement of tests/kernel_ref.py against central differences of itself, against
 MacKay's form and against the properties the definition promises (even in p, periodic, positive definite); the Python and ctypes side of
 kind 8 (its 2 d + 1 wide block through layout / spec_of); and the public surface on a CPU double of the device ops backed by the
 restatement."""
@@ -14,12 +14,9 @@ import pygpr_amd as pg
 from pygpr_amd import _lib, _ops
 from oracle import pygpr_oracle as orc
 
-import periodic_ref as per
-import rq_ref as rq
-from oracle_ops import OracleOps, _np, _passes
-
-PART_OF_KIND = {0: "se", 1: "m52", 3: "m32", 4: "m12", 6: "rq", 8: "per"}
-CLS = {"per": pg.Periodic, "rq": pg.Rational_quadratic, "se": pg.Squared_exponential, "m32": pg.Matern32, "wn": pg.White_noise}
+import kernel_ref as kr
+from kind_tools import N, T, compose
+from oracle_ops import fake_ops  # noqa: F401  (fake_ops: the fixture)
 
 # Central differences with step h: truncation h^2 |f'''| / 6, rounding eps |f| / h.  sigma, l in [0.5, 1.5], periods in [0.7, 2.5]: a
 # derivative in p_k brings a factor pi D / p^2 each time, so the kernel test scales its points to |D| <= 2 (|f'''| <= ~1e4); h = 1e-6
@@ -41,37 +38,41 @@ def test_restatement_gradient_matches_central_differences():
     parts = ["per", "wn"]
     hp = np.append(hp, 0.3)
     d = x.shape[1]
-    k, dk = per.kernel_and_grad(parts, hp, x)
+    k, dk = kr.kernel_and_grad(parts, hp, x)
     assert dk.shape == (hp.size,) + k.shape and hp.size == 2 * d + 1 + 1 and np.isfinite(dk).all()
     for p in range(hp.size):
         e = np.zeros(hp.size)
         e[p] = H
-        fd = (per.kernel(parts, hp + e, x) - per.kernel(parts, hp - e, x)) / (2 * H)
+        fd = (kr.kernel(parts, hp + e, x) - kr.kernel(parts, hp - e, x)) / (2 * H)
         np.testing.assert_allclose(dk[p], fd, rtol=0, atol=FD_ATOL)
     for kk in range(d):                                          # the period slabs vanish where D = 0
         assert not np.diag(dk[d + 1 + kk]).any() and dk[d + 1 + kk][2, 5] == 0.0 and dk[d + 1 + kk].any()
-    dks = per.kernel_xgrad(parts, hp, x, xp)
+    dks = kr.kernel_xgrad(parts, hp, x, xp)
     for kk in range(d):
         e = np.zeros_like(xp)
         e[:, kk] = H
-        fd = (per.kernel(parts, hp, x, xp + e) - per.kernel(parts, hp, x, xp - e)) / (2 * H)
+        fd = (kr.kernel(parts, hp, x, xp + e) - kr.kernel(parts, hp, x, xp - e)) / (2 * H)
         np.testing.assert_allclose(dks[kk], fd, rtol=0, atol=FD_ATOL)
 
 
 def test_restatement_in_a_sum_delegates_to_the_other_kinds():
+    """A sum is its terms evaluated apart: K the sum of the sub-models' K, each dK slab the lone part's own slab at its offset, the
+    x*-gradient the sum of theirs -- whichever widths stand in front of a block."""
     x, xp, hp = _data()
     d = x.shape[1]
     parts = ["rq", "per", "se", "wn"]
     hp_rq, hp_se = np.concatenate([[0.9], 0.5 + np.arange(d) / d, [0.8]]), np.concatenate([[1.1], 0.6 + np.arange(d) / d])
     full = np.concatenate([hp_rq, hp, hp_se, [0.2]])
-    assert full.size == per.nhp_of(parts, d) == (d + 2) + (2 * d + 1) + (d + 1) + 1
-    k, dk = per.kernel_and_grad(parts, full, x)
-    k_rq, dk_rq = rq.kernel_and_grad(["rq", "se", "wn"], np.concatenate([hp_rq, hp_se, [0.2]]), x)
-    k_p, dk_p = per.kernel_and_grad(["per"], hp, x)
+    assert full.size == kr.nhp_of(parts, d) == (d + 2) + (2 * d + 1) + (d + 1) + 1
+    k, dk = kr.kernel_and_grad(parts, full, x)
+    k_rq, dk_rq = kr.kernel_and_grad(["rq", "se", "wn"], np.concatenate([hp_rq, hp_se, [0.2]]), x)
+    k_p, dk_p = kr.kernel_and_grad(["per"], hp, x)
     np.testing.assert_allclose(k, k_rq + k_p, rtol=0, atol=1e-15)
     assert np.array_equal(dk[: d + 2], dk_rq[: d + 2]) and np.array_equal(dk[d + 2: 3 * d + 3], dk_p) and np.array_equal(dk[3 * d + 3:], dk_rq[d + 2:])
-    np.testing.assert_allclose(per.kernel_xgrad(parts, full, x, xp),
-                               rq.kernel_xgrad(["rq", "se"], np.concatenate([hp_rq, hp_se]), x, xp) + per.kernel_xgrad(["per"], hp, x, xp),
+    singles = [kr.kernel_and_grad([q], h, x)[1] for q, h in (("rq", hp_rq), ("per", hp), ("se", hp_se), ("wn", np.array([0.2])))]
+    assert np.array_equal(dk, np.concatenate(singles))
+    np.testing.assert_allclose(kr.kernel_xgrad(parts, full, x, xp),
+                               kr.kernel_xgrad(["rq", "se"], np.concatenate([hp_rq, hp_se]), x, xp) + kr.kernel_xgrad(["per"], hp, x, xp),
                                rtol=0, atol=1e-14)
 
 
@@ -81,24 +82,24 @@ def test_restatement_nlml_and_prediction_derivatives_match_central_differences()
     xp = rng.random((5, 3))
     parts = ["per", "m32", "wn"]
     hp = np.concatenate([[1.1], 0.5 + rng.random(3), rng.uniform(0.7, 2.5, 3), [0.7], 0.5 + rng.random(3), [0.2]])
-    loss, g = per.nlml_and_grad(parts, hp, x, y)
-    np.testing.assert_allclose(loss, per.nlml(parts, hp, x, y), rtol=1e-14)
-    # the NLML of 40 points: |f| ~ 50 and K^-1 ~ 1 / sigma_n^2 = 25 in every derivative -- the step and bounds of matern_ref's own test
+    loss, g = kr.nlml_and_grad(parts, hp, x, y)
+    np.testing.assert_allclose(loss, kr.nlml(parts, hp, x, y), rtol=1e-14)
+    # the NLML of 40 points: |f| ~ 50 and K^-1 ~ 1 / sigma_n^2 = 25 in every derivative -- the step and bounds of the Matern family's own test
     h = 1e-6
     for p in range(hp.size):
         e = np.zeros(hp.size)
         e[p] = h
-        np.testing.assert_allclose(g[p], (per.nlml(parts, hp + e, x, y) - per.nlml(parts, hp - e, x, y)) / (2 * h), rtol=1e-5, atol=1e-6)
-    dmean, dvar = per.predict_grads(parts, hp, x, y, xp)
+        np.testing.assert_allclose(g[p], (kr.nlml(parts, hp + e, x, y) - kr.nlml(parts, hp - e, x, y)) / (2 * h), rtol=1e-5, atol=1e-6)
+    dmean, dvar = kr.predict_grads(parts, hp, x, y, xp)
     g_mu, g_f = rng.standard_normal(5), rng.standard_normal((5, 5))
-    vjp = per.predict_vjp(parts, hp, x, y, xp, "full", g_mu, g_f)
+    vjp = kr.predict_vjp(parts, hp, x, y, xp, "full", g_mu, g_f)
     for p in range(xp.shape[0]):
         for kk in range(3):
             e = np.zeros_like(xp)
             e[p, kk] = 1e-5
-            hi, lo = per.predict(parts, hp, x, y, xp + e), per.predict(parts, hp, x, y, xp - e)
+            hi, lo = kr.predict(parts, hp, x, y, xp + e), kr.predict(parts, hp, x, y, xp - e)
             assert abs((hi[0][p] - lo[0][p]) / 2e-5 - dmean[p, kk]) <= 1e-7 and abs((hi[1][p] - lo[1][p]) / 2e-5 - dvar[p, kk]) <= 1e-7
-            hi, lo = per.predict(parts, hp, x, y, xp + e, var="full"), per.predict(parts, hp, x, y, xp - e, var="full")
+            hi, lo = kr.predict(parts, hp, x, y, xp + e, var="full"), kr.predict(parts, hp, x, y, xp - e, var="full")
             fd = (g_mu @ (hi[0] - lo[0]) + np.sum(g_f * (hi[1] - lo[1]))) / 2e-5
             assert abs(fd - vjp[p, kk]) <= 1e-6
 
@@ -110,7 +111,7 @@ def test_mackay_correspondence():
     hp = np.array([1.0, np.sqrt(2.0) / ell, p])
     for q in (None, xp):
         dd = (x if q is None else q)[:, 0][:, None] - x[:, 0][None, :]
-        np.testing.assert_allclose(per.kernel(["per"], hp, x, q), np.exp(-2.0 * np.sin(np.pi * dd / p) ** 2 / ell ** 2), rtol=0, atol=4e-16)
+        np.testing.assert_allclose(kr.kernel(["per"], hp, x, q), np.exp(-2.0 * np.sin(np.pi * dd / p) ** 2 / ell ** 2), rtol=0, atol=4e-16)
 
 
 def test_even_in_the_period_and_periodic_in_the_input():
@@ -118,14 +119,14 @@ def test_even_in_the_period_and_periodic_in_the_input():
     d = x.shape[1]
     neg = hp.copy()
     neg[d + 1:] *= -1.0
-    assert np.array_equal(per.kernel(["per"], hp, x, xp), per.kernel(["per"], neg, x, xp))
+    assert np.array_equal(kr.kernel(["per"], hp, x, xp), kr.kernel(["per"], neg, x, xp))
     # K(x, x + p e_k) = K(x, x) = sigma^2 to rounding: the shifted point's phase is pi (D + p) / p, off pi by a few ulps of pi |D + p| / p
     for k in range(d):
         shifted = x.copy()
         shifted[:, k] += hp[d + 1 + k]
-        kd = np.diag(per.kernel(["per"], hp, x, shifted))
+        kd = np.diag(kr.kernel(["per"], hp, x, shifted))
         np.testing.assert_allclose(kd, hp[0] ** 2, rtol=0, atol=1e-15 * 9)
-        np.testing.assert_allclose(per.kernel(["per"], hp, x, shifted), per.kernel(["per"], hp, x, x), rtol=0, atol=1e-14)
+        np.testing.assert_allclose(kr.kernel(["per"], hp, x, shifted), kr.kernel(["per"], hp, x, x), rtol=0, atol=1e-14)
 
 
 def test_positive_definite_on_random_points():
@@ -133,7 +134,7 @@ def test_positive_definite_on_random_points():
         rng = np.random.default_rng(seed)
         x = rng.uniform(-3, 3, (120, d))
         hp = np.concatenate([[1.2], 0.3 + rng.random(d), rng.uniform(0.7, 2.5, d)])
-        k = per.kernel(["per"], hp, x)
+        k = kr.kernel(["per"], hp, x)
         assert np.array_equal(k, k.T) and (np.diag(k) == hp[0] ** 2).all()
         assert np.linalg.eigvalsh(k).min() >= -1e-13 * 120 * hp[0] ** 2      # (backward error of the symmetric eigensolver: eps n |K|)
         np.linalg.cholesky(k + 1e-10 * np.eye(120))
@@ -176,67 +177,6 @@ def test_kind_constant_struct_and_symbols():
 
 
 # ---- the public surface on a CPU double of the device ops, backed by the restatement ------------------------------------------------
-class PeriodicOracleOps(OracleOps):
-    """OracleOps whose covariance calls go through periodic_ref (every kind, the 2 d + 1 wide block included)."""
-
-    @staticmethod
-    def _model(spec, hp, d):
-        """(parts, hp) of a standalone model holding the spec's children: their blocks in spec order, the noise terms behind."""
-        parts, index = [], []
-        for sp in _passes(spec):
-            for c in range(sp.ncomp):
-                part = PART_OF_KIND[sp.kind[c]]
-                parts.append(part)
-                index += list(range(sp.off[c], sp.off[c] + per.width(part, d)))
-            for i in range(sp.nnoise):
-                parts.append("wn")
-                index.append(sp.noise_off[i])
-        return parts, hp[index], index
-
-    def kernel_build(self, spec, hp, xr, xc, out, lower_only=False, jitter=0.0):
-        x = _np(xr).astype(np.float64)
-        parts, h, _ = self._model(spec, _np(hp), x.shape[1])
-        o = _np(out)
-        if xc is None:
-            n = x.shape[0]
-            full = np.eye(o.shape[0])
-            full[:n, :n] = per.kernel(parts, h, x) + jitter * np.eye(n)
-            if lower_only:
-                mask = np.tril(np.ones_like(full, dtype=bool))
-                o[mask] = full[mask]
-            else:
-                o[...] = full
-        else:
-            xq = _np(xc).astype(np.float64)
-            o[...] = 0.0
-            o[: x.shape[0], : xq.shape[0]] = per.kernel(parts, h, xq, x)
-        return out
-
-    def kernel_grad_build(self, spec, hp, x, out):
-        xx = _np(x).astype(np.float64)
-        parts, h, index = self._model(spec, _np(hp), xx.shape[1])
-        o = _np(out)
-        o[...] = 0.0
-        o[index] = per.kernel_and_grad(parts, h, xx)[1]
-        return out
-
-
-@pytest.fixture
-def fake_ops(monkeypatch, tmp_path):
-    ops = PeriodicOracleOps()
-    monkeypatch.setattr(_ops, "_OPS", ops)
-    monkeypatch.chdir(tmp_path)
-    return ops
-
-
-def T(a):
-    return torch.from_numpy(np.ascontiguousarray(a))
-
-
-def N(t):
-    return t.detach().cpu().numpy()
-
-
 def _hp(parts, d, rng):
     blocks = []
     for p in parts:
@@ -255,22 +195,22 @@ def test_public_surface_on_the_cpu_double(fake_ops, parts):
     x, y = orc.synth(n, d, seed=4)
     xp = rng.random((m, d))
     hp = _hp(parts, d, rng)
-    cov = pg.Compose([CLS[p]() for p in parts])
-    assert hp.size == per.nhp_of(parts, d) == cov.get_params_shape(T(x))[0]
-    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x))), per.kernel(parts, hp, x), rtol=0, atol=1e-14)
-    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x), T(xp))), per.kernel(parts, hp, x, xp), rtol=0, atol=1e-14)
+    cov = compose(parts)
+    assert hp.size == kr.nhp_of(parts, d) == cov.get_params_shape(T(x))[0]
+    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x))), kr.kernel(parts, hp, x), rtol=0, atol=1e-14)
+    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x), T(xp))), kr.kernel(parts, hp, x, xp), rtol=0, atol=1e-14)
     k, dk = cov.kernel_and_grad(T(hp), T(x))
-    np.testing.assert_allclose(N(dk), per.kernel_and_grad(parts, hp, x)[1], rtol=0, atol=1e-14)
+    np.testing.assert_allclose(N(dk), kr.kernel_and_grad(parts, hp, x)[1], rtol=0, atol=1e-14)
     gp = pg.Exact_GP(T(x), T(y), cov)
     gp.set_params(T(hp))
     mu, var = gp.predict(T(xp), var="diag")
-    mu_ref, var_ref = per.predict(parts, hp, x, y, xp)
+    mu_ref, var_ref = kr.predict(parts, hp, x, y, xp)
     np.testing.assert_allclose(N(mu), mu_ref, rtol=0, atol=1e-10)
     np.testing.assert_allclose(N(var), var_ref, rtol=0, atol=1e-10)
     _, cov_f = gp.predict(T(xp), var="full")
-    np.testing.assert_allclose(N(cov_f), per.predict(parts, hp, x, y, xp, var="full")[1], rtol=0, atol=1e-10)
+    np.testing.assert_allclose(N(cov_f), kr.predict(parts, hp, x, y, xp, var="full")[1], rtol=0, atol=1e-10)
     loss, grad = pg.MLE(gp).loss_and_grad(hp.copy())
-    loss_ref, grad_ref = per.nlml_and_grad(parts, hp, x, y)
+    loss_ref, grad_ref = kr.nlml_and_grad(parts, hp, x, y)
     np.testing.assert_allclose(loss, loss_ref, rtol=1e-11)
     np.testing.assert_allclose(grad, grad_ref, rtol=1e-9, atol=1e-9 * np.abs(grad_ref).max())
     with pytest.raises(AssertionError):
@@ -285,15 +225,15 @@ def test_batched_experts_on_the_cpu_double(fake_ops):
     y = np.sin(-x.sum(-1)) + 0.1 * rng.standard_normal((nc, n))
     xp = rng.random((nc, m, d))
     hp = np.stack([_hp(parts, d, rng) for _ in range(nc)])
-    gp = pg.Exact_GP(T(x), T(y), pg.Compose([CLS[p]() for p in parts]))
+    gp = pg.Exact_GP(T(x), T(y), compose(parts))
     assert list(gp.cov.get_params_shape(T(x))) == [nc, 2 * d + 2]
     gp.set_params(T(hp))
     mu, var = gp.predict(T(xp), var="diag")
     loss, grad = pg.MLE(gp).loss_and_grad(hp.copy())
     for c in range(nc):
-        mu_ref, var_ref = per.predict(parts, hp[c], x[c], y[c], xp[c])
+        mu_ref, var_ref = kr.predict(parts, hp[c], x[c], y[c], xp[c])
         np.testing.assert_allclose(N(mu[c]), mu_ref, rtol=0, atol=1e-10)
         np.testing.assert_allclose(N(var[c]).ravel(), var_ref, rtol=0, atol=1e-10)
-        l_ref, g_ref = per.nlml_and_grad(parts, hp[c], x[c], y[c])
+        l_ref, g_ref = kr.nlml_and_grad(parts, hp[c], x[c], y[c])
         np.testing.assert_allclose(loss[c], l_ref, rtol=1e-11)
         np.testing.assert_allclose(grad[c], g_ref, rtol=1e-9, atol=1e-9 * np.abs(g_ref).max())

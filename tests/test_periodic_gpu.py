@@ -1,7 +1,7 @@
 """GPU tier of the periodic kernel: kind 8, whose block is 2 d + 1 wide and whose distance is not a function of the scaled squared
 distance, through every covariance path (C ABI entry points, the dK stack with its period slabs, the fused gradient with its period
 entries, Exact_GP / MLE / LOO / predict_grad / append / batched experts / GRBCM / SK_WRAP / sampler) against the direct-difference
-restatement of tests/periodic_ref.py.
+restatement of tests/kernel_ref.py.
 
 Shapes: n = 130 against m = 70 (two 64-tiles and a ragged edge: a diagonal tile, an interior tile, padding), d in {1, 3, 8, 17} (17 is past
 the matrix-pipe bound of 16 and must take the same route as 8), data in [-3, 3]^d with periods from 0.7 to 7 (rint reduces by up to four
@@ -13,48 +13,11 @@ import torch
 
 import pygpr_amd as pg
 
+import kernel_ref as kr
 import loo_ref
-import periodic_ref as per
+from kind_tools import N, T, builds, check, compose, dev, grad_inputs, host, one_spec, ops  # noqa: F401  (ops: the fixture)
 
 pytestmark = pytest.mark.gpu
-
-CLS = {"per": pg.Periodic, "rq": pg.Rational_quadratic, "m32": pg.Matern32, "m12": pg.Matern12, "se": pg.Squared_exponential,
-       "wn": pg.White_noise}
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from pygpr_amd._ops import get_ops
-
-    return get_ops()
-
-
-def dev(a, dtype=torch.float64):
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda", dtype)
-
-
-def host(t):
-    return t.detach().cpu().double().numpy()
-
-
-def T(a):
-    return torch.from_numpy(np.ascontiguousarray(a))
-
-
-def N(t):
-    return t.detach().cpu().numpy()
-
-
-def compose(parts):
-    return pg.Compose([CLS[p]() for p in parts])
-
-
-def _spec(parts, d):
-    from pygpr_amd.covar import spec_of
-
-    specs, _ = spec_of(compose(parts), d)
-    assert len(specs) == 1
-    return specs[0]
 
 
 def synth(n, d, seed, m=0):
@@ -83,54 +46,6 @@ def hp_of(parts, d, rng):
     return np.concatenate([block(p, d, rng) for p in parts])
 
 
-def _grad_inputs(ops, parts, hp, x, y, dtype):
-    """K^-1 (lower) and alpha of the model on the device, in `dtype` (as tests/test_rq_gpu.py builds them)."""
-    from pygpr_amd._ops import pad_to
-
-    n, d = x.shape
-    npad = pad_to(n)
-    spec = _spec(parts, d)
-    hpd, xd = dev(hp), dev(x, dtype)
-    k = ops.empty(npad, npad, dtype=dtype)
-    invd = ops.potrf_workspace(npad, dtype)
-    info = torch.zeros(1, dtype=torch.int32, device="cuda")
-    minv = ops.zeros(npad, npad, dtype=dtype)
-    ops.build_factor(spec, hpd, xd, k, invd, info, minv)
-    assert int(info.item()) == 0
-    ypad = ops.zeros(npad, dtype=dtype)
-    ypad[:n] = dev(y, dtype)
-    u, alpha = ops.empty(npad, dtype=dtype), ops.empty(npad, dtype=dtype)
-    ops.trmv(minv, ypad, u, 0)
-    ops.trmv(minv, u, alpha, 1, ops.empty((npad // 256 + 1) * npad, dtype=dtype))
-    kinv = ops.zeros(npad, npad, dtype=dtype)
-    ops.lauum(minv, kinv)
-    return spec, hpd, xd, kinv, alpha
-
-
-def _builds(ops, spec, hp, x, xp, dtype):
-    from pygpr_amd._ops import pad_to
-
-    n, m = x.shape[0], xp.shape[0]
-    npad, mpad = pad_to(n), pad_to(m)
-    hpd, xd, xpd = dev(hp), dev(x, dtype), dev(xp, dtype)
-    full, low, cross = ops.empty(npad, npad, dtype=dtype), ops.zeros(npad, npad, dtype=dtype), ops.empty(mpad, npad, dtype=dtype)
-    ops.kernel_build(spec, hpd, xd, None, full, jitter=1e-7)
-    ops.kernel_build(spec, hpd, xd, None, low, lower_only=True, jitter=1e-7)
-    ops.kernel_build(spec, hpd, xpd, xd, cross)
-    return host(full), host(low), host(cross)
-
-
-def rel(a, ref):
-    a, ref = torch.as_tensor(a).detach().cpu().double(), torch.as_tensor(ref).detach().cpu().double()
-    return float((a - ref).abs().max() / ref.abs().max().clamp_min(1e-300))
-
-
-def check(name, a, ref, tol):
-    e = rel(a, ref)
-    print("%-52s rel err %.2e (bound %.0e)" % (name, e, tol))
-    assert e <= tol, (name, e)
-
-
 # --------------------------------------------------------------------------- 1. entry points, symmetry, diagonal, routing
 @pytest.mark.parametrize("d", [1, 3, 8, 17])
 def test_entry_points_against_the_restatement(ops, monkeypatch, d):
@@ -145,14 +60,14 @@ def test_entry_points_against_the_restatement(ops, monkeypatch, d):
     x, y, xp = synth(n, d, seed=d, m=m)
     parts = ["per", "wn"]
     hp = np.concatenate([[1.2], (0.4 + 0.8 * rng.random(d)) / np.sqrt(d), periods(rng, d), [0.1]])
-    spec, npad = _spec(parts, d), pad_to(n)
-    ref = per.kernel(parts, hp, x) + 1e-7 * np.eye(n)
-    ref_x = per.kernel(parts, hp, x, xp)
+    spec, npad = one_spec(parts, d), pad_to(n)
+    ref = kr.kernel(parts, hp, x) + 1e-7 * np.eye(n)
+    ref_x = kr.kernel(parts, hp, x, xp)
     for dtype, tol in ((torch.float64, 1e-13), (torch.float32, 4e-6)):
         out = {}
         for mode in ("2", "0"):
             monkeypatch.setenv("PG_KB_MFMA", mode)
-            out[mode] = _builds(ops, spec, hp, x, xp, dtype)
+            out[mode] = builds(ops, spec, hp, x, xp, dtype)
         monkeypatch.delenv("PG_KB_MFMA")
         full, low, cross = out["2"]
         print("d=%d %s: K err %.2e, cross err %.2e (bound %.0e)" % (d, dtype, np.abs(full[:n, :n] - ref).max(), np.abs(cross[:m, :n] - ref_x).max(), tol))
@@ -172,17 +87,17 @@ def test_entry_points_against_the_restatement(ops, monkeypatch, d):
         else:
             dgv = np.float64(np.float32(1.2 ** 2) + np.float32(1e-7 + 0.1 ** 2))
         assert (np.diag(full)[:n] == dgv).all()                                       # exactly sigma^2 + (jitter + sigma_n^2)
-    k_ref, dk_ref = per.kernel_and_grad(parts, hp, x)
+    k_ref, dk_ref = kr.kernel_and_grad(parts, hp, x)
     k, dk = compose(parts).kernel_and_grad(T(hp), T(x))
     assert dk.shape == (2 * d + 2, n, n) and all(dk_ref[d + 1 + kk].any() for kk in range(d))
     print("d=%d: dK err %.2e (bound 1e-12), period slabs %.2e" % (d, np.abs(N(dk) - dk_ref).max(), np.abs(N(dk)[d + 1: 2 * d + 1] - dk_ref[d + 1: 2 * d + 1]).max()))
     np.testing.assert_allclose(N(k), k_ref, rtol=0, atol=1e-13)
     np.testing.assert_allclose(N(dk), dk_ref, rtol=0, atol=1e-12)
-    _, grad_ref = per.nlml_and_grad(parts, hp, x, y)
+    _, grad_ref = kr.nlml_and_grad(parts, hp, x, y)
     scale = np.abs(grad_ref).max()
     assert grad_ref[d + 1: 2 * d + 1].all()
     for dtype, tol in ((torch.float64, 1e-8), (torch.float32, 3 * 3e-3)):
-        spec, hpd, xd, kinv, alpha_v = _grad_inputs(ops, parts, hp, x, y, dtype)
+        hpd, xd, kinv, alpha_v = grad_inputs(ops, spec, hp, x, y, dtype)
         work = ops.empty(ops.nlml_grad_worksize(n, hp.size))
         got = {}
         for mode in ("1", "0"):
@@ -214,8 +129,8 @@ def test_offset_data_against_long_double():
     n = x.shape[0]
     parts = ["per", "wn"]
     hp = np.concatenate([[1.2], [0.9, 1.3, 0.6], [0.7, 1.0, 1.6], [0.1]])
-    k_ld, dk_ld = per.kernel_and_grad(parts, hp, x, dtype=np.longdouble)
-    k_np, dk_np = per.kernel_and_grad(parts, hp, x)
+    k_ld, dk_ld = kr.kernel_and_grad(parts, hp, x, dtype=np.longdouble)
+    k_np, dk_np = kr.kernel_and_grad(parts, hp, x)
     err_np = float(np.abs(k_np - k_ld).max())
     derr_np = float(np.abs(dk_np - dk_ld).max())
     k, dk = compose(parts).kernel_and_grad(T(hp), T(x))
@@ -230,7 +145,7 @@ def test_offset_data_against_long_double():
     assert derr <= 4 * derr_np
     xs = x[::-1].copy()
     kx = N(compose(parts).kernel(T(hp), T(x), T(xs)))                                 # a cross build meets the same pairs
-    errx = float(np.abs(kx - per.kernel(parts, hp, x, xs, dtype=np.longdouble)).max())
+    errx = float(np.abs(kx - kr.kernel(parts, hp, x, xs, dtype=np.longdouble)).max())
     print("offset data: cross K err %.2e" % errx)
     assert errx <= 4 * err_np
 
@@ -244,22 +159,22 @@ def test_dk_stack_and_compose(parts):
     x, y, xp = synth(n, d, seed=5, m=m)
     hp = hp_of(parts, d, rng)
     cov = compose(parts)
-    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x))), per.kernel(parts, hp, x), rtol=0, atol=1e-13)
-    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x), T(xp))), per.kernel(parts, hp, x, xp), rtol=0, atol=1e-13)
+    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x))), kr.kernel(parts, hp, x), rtol=0, atol=1e-13)
+    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x), T(xp))), kr.kernel(parts, hp, x, xp), rtol=0, atol=1e-13)
     k, dk = cov.kernel_and_grad(T(hp), T(x))
-    k_ref, dk_ref = per.kernel_and_grad(parts, hp, x)
-    assert dk.shape == (per.nhp_of(parts, d), n, n)
+    k_ref, dk_ref = kr.kernel_and_grad(parts, hp, x)
+    assert dk.shape == (kr.nhp_of(parts, d), n, n)
     assert np.array_equal(N(k), N(k).T)
     np.testing.assert_allclose(N(k), k_ref, rtol=0, atol=1e-13)
     np.testing.assert_allclose(N(dk), dk_ref, rtol=0, atol=1e-12)
     gp = pg.Exact_GP(T(x), T(y), cov)
     gp.set_params(T(hp))
     loss, grad = pg.MLE(gp).loss_and_grad(hp.copy())
-    loss_ref, grad_ref = per.nlml_and_grad(parts, hp, x, y)
+    loss_ref, grad_ref = kr.nlml_and_grad(parts, hp, x, y)
     np.testing.assert_allclose(loss, loss_ref, rtol=1e-10)
     np.testing.assert_allclose(grad, grad_ref, rtol=1e-8, atol=1e-8 * np.abs(grad_ref).max())
     mu, var = gp.predict(T(xp), var="diag")                                           # K** reads every child's sigma by its offset
-    mu_ref, var_ref = per.predict(parts, hp, x, y, xp)
+    mu_ref, var_ref = kr.predict(parts, hp, x, y, xp)
     np.testing.assert_allclose(N(mu), mu_ref, rtol=0, atol=1e-10)
     np.testing.assert_allclose(N(var), var_ref, rtol=0, atol=1e-10)
 
@@ -274,11 +189,11 @@ def test_compose_longer_than_one_pass():
     cov = compose(parts)
     from pygpr_amd.covar import spec_of
     assert len(spec_of(cov, d)[0]) == 2
-    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x))), per.kernel(parts, hp, x), rtol=0, atol=1e-13)
-    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x), T(xp))), per.kernel(parts, hp, x, xp), rtol=0, atol=1e-13)
-    np.testing.assert_allclose(N(cov.kernel_and_grad(T(hp), T(x))[1]), per.kernel_and_grad(parts, hp, x)[1], rtol=0, atol=1e-12)
+    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x))), kr.kernel(parts, hp, x), rtol=0, atol=1e-13)
+    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x), T(xp))), kr.kernel(parts, hp, x, xp), rtol=0, atol=1e-13)
+    np.testing.assert_allclose(N(cov.kernel_and_grad(T(hp), T(x))[1]), kr.kernel_and_grad(parts, hp, x)[1], rtol=0, atol=1e-12)
     loss, grad = pg.MLE(pg.Exact_GP(T(x), T(y), cov)).loss_and_grad(hp.copy())
-    loss_ref, grad_ref = per.nlml_and_grad(parts, hp, x, y)
+    loss_ref, grad_ref = kr.nlml_and_grad(parts, hp, x, y)
     np.testing.assert_allclose(loss, loss_ref, rtol=1e-10)
     np.testing.assert_allclose(grad, grad_ref, rtol=1e-8, atol=1e-8 * np.abs(grad_ref).max())
 
@@ -298,19 +213,19 @@ def test_nan_coordinate_and_nan_period(ops):
     pad = np.eye(128)[n:, :]
     for dt in (torch.float64, torch.float32):
         k = ops.empty(128, 128, dtype=dt)
-        ops.kernel_build(_spec(["per", "wn"], d), dev(hp), dev(xn, dt), None, k, jitter=1e-7)
+        ops.kernel_build(one_spec(["per", "wn"], d), dev(hp), dev(xn, dt), None, k, jitter=1e-7)
         got = host(k)
         assert np.isnan(got[23, :n]).all() and np.isnan(got[:n, 23]).all()
         assert np.isfinite(np.delete(np.delete(got[:n, :n], 23, 0), 23, 1)).all()
         assert np.array_equal(got[n:, :], pad) and np.array_equal(got[:, n:], pad.T)
-        ops.kernel_build(_spec(["per", "wn"], d), dev(hp_nan), dev(x, dt), None, k, jitter=1e-7)
+        ops.kernel_build(one_spec(["per", "wn"], d), dev(hp_nan), dev(x, dt), None, k, jitter=1e-7)
         got = host(k)
         assert np.isnan(got[:n, :n]).all()
         assert np.array_equal(got[n:, :], pad) and np.array_equal(got[:, n:], pad.T)
     # in a sum the other child's values do not rescue the pair, and do not suffer elsewhere
     hp2 = np.concatenate([hp[:-1], [0.9, 0.5, 0.6, 0.7], [0.1]])
     k = ops.empty(128, 128)
-    ops.kernel_build(_spec(["per", "se", "wn"], d), dev(hp2), dev(xn), None, k, jitter=1e-7)
+    ops.kernel_build(one_spec(["per", "se", "wn"], d), dev(hp2), dev(xn), None, k, jitter=1e-7)
     got = host(k)
     assert np.isnan(got[23, :n]).all() and np.isnan(got[:n, 23]).all()
     assert np.isfinite(np.delete(np.delete(got[:n, :n], 23, 0), 23, 1)).all()
@@ -331,35 +246,31 @@ def test_exact_gp_and_mle(n, d):
     gp.set_params(T(hp))
     gp.update()
     mu, var = gp.predict(T(xp), var="diag")
-    mu_ref, var_ref = per.predict(parts, hp, x, y, xp)
+    mu_ref, var_ref = kr.predict(parts, hp, x, y, xp)
     np.testing.assert_allclose(N(mu), mu_ref, rtol=0, atol=1e-10)
     np.testing.assert_allclose(N(var), var_ref, rtol=0, atol=1e-10)
     mu_f, cov_f = gp.predict(T(xp), var="full")
-    _, cov_ref = per.predict(parts, hp, x, y, xp, var="full")
+    _, cov_ref = kr.predict(parts, hp, x, y, xp, var="full")
     np.testing.assert_allclose(N(mu_f), mu_ref, rtol=0, atol=1e-10)
     np.testing.assert_allclose(N(cov_f), cov_ref, rtol=0, atol=1e-10)
     loss, grad = pg.MLE(gp).loss_and_grad(hp.copy())
-    loss_ref, grad_ref = per.nlml_and_grad(parts, hp, x, y)
+    loss_ref, grad_ref = kr.nlml_and_grad(parts, hp, x, y)
     np.testing.assert_allclose(loss, loss_ref, rtol=1e-10)
     np.testing.assert_allclose(grad, grad_ref, rtol=1e-8, atol=1e-8 * np.abs(grad_ref).max())
 
 
 def test_loo_loss_and_grad():
-    """LOO(model).loss_and_grad against loo_ref's closed forms (R&W 5.10 - 5.13) on periodic_ref's kernel and slabs."""
+    """LOO(model).loss_and_grad against loo_ref's closed forms (R&W 5.10 - 5.13) on kernel_ref's kernel and slabs."""
     parts = ["per", "wn"]
     n, d = 130, 3
     x, y = synth(n, d, seed=21)
     hp = np.concatenate([[1.1], np.linspace(0.5, 0.9, d), [0.9, 1.7, 7.0], [0.3]])
-    k = per.kernel(parts, hp, x) + per.JITTER * np.eye(n)
+    k = kr.kernel(parts, hp, x) + kr.JITTER * np.eye(n)
     kinv = np.linalg.inv(k)
     kinv = 0.5 * (kinv + kinv.T)
     alpha, c = kinv @ y, np.diag(kinv).copy()
     loss_ref = loo_ref.loss_from(y - alpha / c, 1.0 / c, y)
-    g_ref = np.zeros(hp.size)
-    for j, slab in per._grad_terms(parts, hp, x):
-        z = kinv @ slab
-        zk_diag = np.einsum("ij,ji->i", z, kinv)
-        g_ref[j] = -float(np.sum((alpha * (z @ alpha) - 0.5 * (1.0 + alpha * alpha / c) * zk_diag) / c))
+    g_ref = loo_ref.grad_from(parts, hp, x, kinv, alpha, c)
     gp = pg.Exact_GP(T(x), T(y), compose(parts))
     gp.set_params(T(hp))
     loss, grad = pg.LOO(gp).loss_and_grad(hp.copy())
@@ -370,7 +281,7 @@ def test_loo_loss_and_grad():
 
 @pytest.mark.parametrize("parts,d", [(["per", "wn"], 3), (["per", "wn"], 17), (["per", "m32", "wn"], 8)], ids=lambda p: "+".join(p) if isinstance(p, list) else str(p))
 def test_predict_grad_and_autograd(parts, d):
-    """predict_grad and autograd in xp against periodic_ref's x*-derivatives: 1e-9 relative to the largest entry, as tests/test_xgrad_gpu.py
+    """predict_grad and autograd in xp against kernel_ref's x*-derivatives: 1e-9 relative to the largest entry, as tests/test_xgrad_gpu.py
     and tests/test_rq_gpu.py ask of the same quantities.  d = 17 takes the kernel that walks the coordinates in passes of sixteen."""
     rng = np.random.default_rng(1)
     n, m = 130, 70
@@ -379,7 +290,7 @@ def test_predict_grad_and_autograd(parts, d):
     gp = pg.Exact_GP(T(x), T(y), compose(parts))
     gp.set_params(T(hp))
     mean, var, dmean, dvar = gp.predict_grad(T(xp), var="diag")
-    rdm, rdv = per.predict_grads(parts, hp, x, y, xp)
+    rdm, rdv = kr.predict_grads(parts, hp, x, y, xp)
     check("predict_grad %s dmean" % "+".join(parts), dmean, T(rdm), 1e-9)
     check("predict_grad %s dvar" % "+".join(parts), dvar, T(rdv), 1e-9)
     g_mu = rng.standard_normal(m)
@@ -389,7 +300,7 @@ def test_predict_grad_and_autograd(parts, d):
         out = gp.predict(xq, var=var_kind)
         loss = (dev(g_mu) * out[0]).sum() + ((dev(g_2) * out[1]).sum() if var_kind != "none" else 0.0)
         loss.backward()
-        check("autograd %s %s" % ("+".join(parts), var_kind), xq.grad, T(per.predict_vjp(parts, hp, x, y, xp, var_kind, g_mu, g_2)), 1e-9)
+        check("autograd %s %s" % ("+".join(parts), var_kind), xq.grad, T(kr.predict_vjp(parts, hp, x, y, xp, var_kind, g_mu, g_2)), 1e-9)
 
 
 def test_batched_experts_match_their_loop():
@@ -416,13 +327,13 @@ def test_batched_experts_match_their_loop():
         l1, g1 = pg.MLE(one).loss_and_grad(hp[c].copy())
         np.testing.assert_allclose(loss[c], l1, rtol=1e-11)
         np.testing.assert_allclose(grad[c], g1, rtol=1e-9, atol=1e-9 * np.abs(g1).max())
-        l_ref, g_ref = per.nlml_and_grad(parts, hp[c], x[c], y[c])
+        l_ref, g_ref = kr.nlml_and_grad(parts, hp[c], x[c], y[c])
         np.testing.assert_allclose(l1, l_ref, rtol=1e-10)
         np.testing.assert_allclose(g1, g_ref, rtol=1e-8, atol=1e-8 * np.abs(g_ref).max())
-        mu_ref, var_ref = per.predict(parts, hp[c], x[c], y[c], xp[c])
+        mu_ref, var_ref = kr.predict(parts, hp[c], x[c], y[c], xp[c])
         np.testing.assert_allclose(N(mu1), mu_ref, rtol=0, atol=1e-10)
         np.testing.assert_allclose(N(var1).ravel(), var_ref, rtol=0, atol=1e-10)
-        rdm, rdv = per.predict_grads(parts, hp[c], x[c], y[c], xp[c])
+        rdm, rdv = kr.predict_grads(parts, hp[c], x[c], y[c], xp[c])
         check("predict_grad batched expert %d dmean" % c, dmean[c], T(rdm), 1e-9)
         check("predict_grad batched expert %d dvar" % c, dvar[c], T(rdv), 1e-9)
 
@@ -455,7 +366,7 @@ def test_append_equals_fresh_fit():
     lr, grr = pg.MLE(ref).loss_and_grad(hp.numpy().copy())
     check("MLE loss", torch.tensor([float(la)]), torch.tensor([float(lr)]), tol)
     check("MLE grad", torch.from_numpy(ga), torch.from_numpy(grr), tol * 10)
-    mu_ref, _ = per.predict(parts, hp.numpy(), xa, ya, xpa)
+    mu_ref, _ = kr.predict(parts, hp.numpy(), xa, ya, xpa)
     np.testing.assert_allclose(N(mu), mu_ref, rtol=0, atol=1e-9)
 
 
@@ -472,7 +383,7 @@ def test_grbcm():
     model.gpg.set_params(T(hp_g))
     model.gpl.set_params(T(hp_l))
     mu, var = model.predict(T(xs), var="diag")
-    mu_ref, var_ref = per.grbcm_predict(parts, hp_g, hp_l, xl, yl, xg, yg, xs)
+    mu_ref, var_ref = kr.grbcm_predict(parts, hp_g, hp_l, xl, yl, xg, yg, xs)
     np.testing.assert_allclose(N(mu), mu_ref, rtol=0, atol=1e-9)
     np.testing.assert_allclose(N(var).ravel(), var_ref, rtol=1e-9, atol=1e-11)
 
@@ -486,7 +397,7 @@ def test_sk_wrap():
     gp = pg.Exact_GP(T(x[:10]), T(y[:10]), compose(parts))
     gp.set_params(T(hp))
     sk = pg.SK_WRAP(gp).fit(T(x), T(y))
-    np.testing.assert_allclose(N(sk.predict(T(xp))), per.predict(parts, hp, x, y, xp)[0], rtol=0, atol=1e-10)
+    np.testing.assert_allclose(N(sk.predict(T(xp))), kr.predict(parts, hp, x, y, xp)[0], rtol=0, atol=1e-10)
 
 
 def test_sampler_mean_and_factor():
@@ -506,7 +417,7 @@ def test_sampler_mean_and_factor():
     err = np.abs(L @ L.T - (c + 1e-7 * np.eye(m))).max() / np.abs(c).max()
     print("sampler factor err %.2e (bound 1e-12)" % err)
     assert err <= 1e-12
-    mu_ref, cov_ref = per.predict(parts, hp, x, y, xp, var="full")
+    mu_ref, cov_ref = kr.predict(parts, hp, x, y, xp, var="full")
     np.testing.assert_allclose(N(pm), mu_ref, rtol=0, atol=1e-10)
     np.testing.assert_allclose(c, cov_ref, rtol=0, atol=1e-10)
 

@@ -1,4 +1,4 @@
-"""CPU tier of Product: the NumPy restatement of tests/product_ref.py against central differences of itself; the Python and ctypes side
+"""CPU tier of Product: the NumPy restatement of tests/kernel_ref.py against central differences of itself; the Python and ctypes side
 of a product spec (PG_SPEC_PRODUCT in ncomp, the pass plan of spec_of, the refusals, the memo key); and the public surface on a CPU
 double of the device ops backed by the restatement."""
 import ctypes
@@ -14,12 +14,9 @@ from pygpr_amd import _lib, _ops
 from pygpr_amd.covar import layout, spec_of, terms
 from oracle import pygpr_oracle as orc
 
-import product_ref as pr
-from oracle_ops import OracleOps, _np, _passes
-
-PART_OF_KIND = {0: "se", 1: "m52", 3: "m32", 4: "m12", 6: "rq", 8: "per"}
-CLS = {"per": pg.Periodic, "rq": pg.Rational_quadratic, "se": pg.Squared_exponential, "m52": pg.Matern52, "m32": pg.Matern32,
-       "m12": pg.Matern12, "wn": pg.White_noise}
+import kernel_ref as kr
+from kind_tools import N, T, cov_of
+from oracle_ops import fake_ops  # noqa: F401  (fake_ops: the fixture)
 
 # Central differences with step h: truncation h^2 |f'''| / 6, rounding eps |f| / h.  The step and the bound are those of
 # tests/test_periodic_cpu.py (|D| <= 2, periods in [0.7, 2.5]: |f'''| <= ~1e4 for the periodic factor, 2e-9 of truncation and 3e-10 of
@@ -28,15 +25,9 @@ CLS = {"per": pg.Periodic, "rq": pg.Rational_quadratic, "se": pg.Squared_exponen
 H, FD_ATOL = 1.0e-6, 1.0e-8
 
 
-def cov_of(model):
-    """The covariance object of a term list: a tuple becomes a Product, a list of more than one term a Compose."""
-    objs = [pg.Product([CLS[p]() for p in t]) if isinstance(t, tuple) else CLS[t]() for t in model]
-    return objs[0] if len(objs) == 1 else pg.Compose(objs)
-
-
 def hp_of(model, d, rng, sigma=(0.7, 1.0)):
     blocks = []
-    for p in pr.flat(model):
+    for p in kr.flat(model):
         if p == "wn":
             blocks.append([0.2])
         else:
@@ -61,37 +52,39 @@ def test_restatement_gradient_matches_central_differences(model):
     x, xp, rng = _data()
     d = x.shape[1]
     hp = hp_of(model, d, rng)
-    k, dk = pr.kernel_and_grad(model, hp, x)
-    assert dk.shape == (hp.size,) + k.shape and hp.size == pr.nhp_of(model, d) and np.isfinite(dk).all()
-    assert np.array_equal(k, pr.kernel(model, hp, x))
+    k, dk = kr.kernel_and_grad(model, hp, x)
+    assert dk.shape == (hp.size,) + k.shape and hp.size == kr.nhp_of(model, d) and np.isfinite(dk).all()
+    assert np.array_equal(k, kr.kernel(model, hp, x))
     for p in range(hp.size):
         e = np.zeros(hp.size)
         e[p] = H
-        fd = (pr.kernel(model, hp + e, x) - pr.kernel(model, hp - e, x)) / (2 * H)
+        fd = (kr.kernel(model, hp + e, x) - kr.kernel(model, hp - e, x)) / (2 * H)
         np.testing.assert_allclose(dk[p], fd, rtol=0, atol=FD_ATOL)
-    dks = pr.kernel_xgrad(model, hp, x, xp)
+    dks = kr.kernel_xgrad(model, hp, x, xp)
     for kk in range(d):
         e = np.zeros_like(xp)
         e[:, kk] = H
-        fd = (pr.kernel(model, hp, x, xp + e) - pr.kernel(model, hp, x, xp - e)) / (2 * H)
+        fd = (kr.kernel(model, hp, x, xp + e) - kr.kernel(model, hp, x, xp - e)) / (2 * H)
         np.testing.assert_allclose(dks[kk], fd, rtol=0, atol=FD_ATOL)
 
 
 def test_restatement_is_the_product_of_the_parts():
-    import periodic_ref as per
-
     x, xp, rng = _data()
     d = x.shape[1]
     hp = hp_of([("se", "per"), "m32", "wn"], d, rng)
     a, b, c = d + 1, 3 * d + 2, 4 * d + 3
     for q in (None, xp):
-        want = per.kernel(["se"], hp[:a], x, q) * per.kernel(["per"], hp[a:b], x, q) + per.kernel(["m32", "wn"], hp[b:], x, q)
-        assert np.array_equal(pr.kernel([("se", "per"), "m32", "wn"], hp, x, q), want)
-    # a product of one factor is the factor; a list without tuples is periodic_ref's sum
-    assert np.array_equal(pr.kernel([("per",)], hp[a:b], x), per.kernel(["per"], hp[a:b], x))
-    assert np.array_equal(pr.kernel_and_grad(["se", "per", "m32", "wn"], hp, x)[1], per.kernel_and_grad(["se", "per", "m32", "wn"], hp, x)[1])
+        want = kr.kernel(["se"], hp[:a], x, q) * kr.kernel(["per"], hp[a:b], x, q) + kr.kernel(["m32", "wn"], hp[b:], x, q)
+        assert np.array_equal(kr.kernel([("se", "per"), "m32", "wn"], hp, x, q), want)
+        assert np.array_equal(want, kr.stationary("se", hp[:a], x, q) * kr.stationary("per", hp[a:b], x, q)
+                              + (kr.stationary("m32", hp[b:c], x, q) + (hp[c] ** 2 * np.eye(x.shape[0]) if q is None else 0.0)))
+    # a product of one factor is the factor; the dK stack of a list without tuples is the lone parts' slabs at their offsets
+    assert np.array_equal(kr.kernel([("per",)], hp[a:b], x), kr.kernel(["per"], hp[a:b], x))
+    assert np.array_equal(kr.kernel_and_grad([("per",)], hp[a:b], x)[1], kr.kernel_and_grad(["per"], hp[a:b], x)[1])
+    singles = [kr.kernel_and_grad([p], hp[i:j], x)[1] for p, i, j in (("se", 0, a), ("per", a, b), ("m32", b, c), ("wn", c, c + 1))]
+    assert np.array_equal(kr.kernel_and_grad(["se", "per", "m32", "wn"], hp, x)[1], np.concatenate(singles))
     # the same formulas in extended precision agree with themselves to a few float64 ulps of the values (|K| <= 1.3)
-    k64, k80 = pr.kernel([("se", "per"), "m32", "wn"], hp, x), pr.kernel([("se", "per"), "m32", "wn"], hp, x, dtype=np.longdouble)
+    k64, k80 = kr.kernel([("se", "per"), "m32", "wn"], hp, x), kr.kernel([("se", "per"), "m32", "wn"], hp, x, dtype=np.longdouble)
     assert k80.dtype == np.longdouble and np.abs(k64 - k80).max() <= 32 * np.finfo(np.float64).eps
 
 
@@ -101,24 +94,24 @@ def test_restatement_nlml_and_prediction_derivatives_match_central_differences()
     xp = rng.random((5, 3))
     model = [("se", "per"), "m32", "wn"]
     hp = hp_of(model, 3, rng)
-    loss, g = pr.nlml_and_grad(model, hp, x, y)
-    np.testing.assert_allclose(loss, pr.nlml(model, hp, x, y), rtol=1e-14)
-    # the NLML of 40 points: |f| ~ 50 and K^-1 ~ 1 / sigma_n^2 = 25 in every derivative -- the step and bounds of periodic_ref's own test
+    loss, g = kr.nlml_and_grad(model, hp, x, y)
+    np.testing.assert_allclose(loss, kr.nlml(model, hp, x, y), rtol=1e-14)
+    # the NLML of 40 points: |f| ~ 50 and K^-1 ~ 1 / sigma_n^2 = 25 in every derivative -- the step and bounds of the periodic kernel's own test
     h = 1e-6
     for p in range(hp.size):
         e = np.zeros(hp.size)
         e[p] = h
-        np.testing.assert_allclose(g[p], (pr.nlml(model, hp + e, x, y) - pr.nlml(model, hp - e, x, y)) / (2 * h), rtol=1e-5, atol=1e-6)
-    dmean, dvar = pr.predict_grads(model, hp, x, y, xp)
+        np.testing.assert_allclose(g[p], (kr.nlml(model, hp + e, x, y) - kr.nlml(model, hp - e, x, y)) / (2 * h), rtol=1e-5, atol=1e-6)
+    dmean, dvar = kr.predict_grads(model, hp, x, y, xp)
     g_mu, g_f = rng.standard_normal(5), rng.standard_normal((5, 5))
-    vjp = pr.predict_vjp(model, hp, x, y, xp, "full", g_mu, g_f)
+    vjp = kr.predict_vjp(model, hp, x, y, xp, "full", g_mu, g_f)
     for p in range(xp.shape[0]):
         for kk in range(3):
             e = np.zeros_like(xp)
             e[p, kk] = 1e-5
-            hi, lo = pr.predict(model, hp, x, y, xp + e), pr.predict(model, hp, x, y, xp - e)
+            hi, lo = kr.predict(model, hp, x, y, xp + e), kr.predict(model, hp, x, y, xp - e)
             assert abs((hi[0][p] - lo[0][p]) / 2e-5 - dmean[p, kk]) <= 1e-7 and abs((hi[1][p] - lo[1][p]) / 2e-5 - dvar[p, kk]) <= 1e-7
-            hi, lo = pr.predict(model, hp, x, y, xp + e, var="full"), pr.predict(model, hp, x, y, xp - e, var="full")
+            hi, lo = kr.predict(model, hp, x, y, xp + e, var="full"), kr.predict(model, hp, x, y, xp - e, var="full")
             fd = (g_mu @ (hi[0] - lo[0]) + np.sum(g_f * (hi[1] - lo[1]))) / 2e-5
             assert abs(fd - vjp[p, kk]) <= 1e-6
 
@@ -195,76 +188,6 @@ def test_refusals_at_construction():
 
 
 # ---- the public surface on a CPU double of the device ops, backed by the restatement ------------------------------------------------
-class ProductOracleOps(OracleOps):
-    """OracleOps whose covariance calls go through product_ref: a flagged spec is one product term, an unflagged one a sum."""
-
-    @staticmethod
-    def _model(spec, hp, d):
-        """(terms, hp) of a standalone model holding the passes' terms: their blocks in pass order, the noise terms behind."""
-        model, noise, index = [], [], []
-        for sp in _passes(spec):
-            parts = []
-            for c in range(sp.ncomp & 0xFF):
-                parts.append(PART_OF_KIND[sp.kind[c]])
-                index += list(range(sp.off[c], sp.off[c] + pr.width(parts[-1], d)))
-            model += [tuple(parts)] if sp.ncomp & _lib.PG_SPEC_PRODUCT else parts
-            noise += [sp.noise_off[i] for i in range(sp.nnoise)]
-        index += noise
-        return model + ["wn"] * len(noise), hp[index], index
-
-    def kernel_build(self, spec, hp, xr, xc, out, lower_only=False, jitter=0.0):
-        x = _np(xr).astype(np.float64)
-        model, h, _ = self._model(spec, _np(hp), x.shape[1])
-        o = _np(out)
-        if xc is None:
-            n = x.shape[0]
-            full = np.eye(o.shape[0])
-            full[:n, :n] = pr.kernel(model, h, x) + jitter * np.eye(n)
-            if lower_only:
-                mask = np.tril(np.ones_like(full, dtype=bool))
-                o[mask] = full[mask]
-            else:
-                o[...] = full
-        else:
-            xq = _np(xc).astype(np.float64)
-            o[...] = 0.0
-            o[: x.shape[0], : xq.shape[0]] = pr.kernel(model, h, xq, x)
-        return out
-
-    def kernel_grad_build(self, spec, hp, x, out):
-        xx = _np(x).astype(np.float64)
-        model, h, index = self._model(spec, _np(hp), xx.shape[1])
-        o = _np(out)
-        o[...] = 0.0
-        o[index] = pr.kernel_and_grad(model, h, xx)[1]
-        return out
-
-    def predict_mean_q_kt_batched(self, kt_all, minv_all, alpha_all, mean_all, var_all, spec, hp_all, work_all):
-        (sp,) = _passes(spec)
-        for e in range(kt_all.shape[0]):
-            h = _np(hp_all[e % hp_all.shape[0]])
-            sig2 = [h[sp.off[c]] ** 2 for c in range(sp.ncomp & 0xFF)]
-            kss = (np.prod(sig2) if sp.ncomp & _lib.PG_SPEC_PRODUCT else sum(sig2)) + sum(h[sp.noise_off[i]] ** 2 for i in range(sp.nnoise))
-            self.predict_mean_q_kt(kt_all[e], minv_all[e] if var_all is not None else None, alpha_all[e], mean_all[e],
-                                   var_all[e] if var_all is not None else None, kss, None)
-
-
-@pytest.fixture
-def fake_ops(monkeypatch, tmp_path):
-    ops = ProductOracleOps()
-    monkeypatch.setattr(_ops, "_OPS", ops)
-    monkeypatch.chdir(tmp_path)
-    return ops
-
-
-def T(a):
-    return torch.from_numpy(np.ascontiguousarray(a))
-
-
-def N(t):
-    return t.detach().cpu().numpy()
-
-
 @pytest.mark.parametrize("model", [[("se", "per")], [("se", "per"), "wn"], ["wn", ("rq", "per"), "m32"], [("m52", "per"), ("se", "m32"), "wn"]], ids=str)
 def test_public_surface_on_the_cpu_double(fake_ops, model):
     """Every block is read by its offset: a product in front of, behind and between plain children and the noise."""
@@ -274,24 +197,24 @@ def test_public_surface_on_the_cpu_double(fake_ops, model):
     xp = rng.random((m, d))
     hp = hp_of(model, d, rng, sigma=(0.7, 1.3))
     cov = cov_of(model)
-    assert hp.size == pr.nhp_of(model, d) == cov.get_params_shape(T(x))[0]
-    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x))), pr.kernel(model, hp, x), rtol=0, atol=1e-14)
-    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x), T(xp))), pr.kernel(model, hp, x, xp), rtol=0, atol=1e-14)
+    assert hp.size == kr.nhp_of(model, d) == cov.get_params_shape(T(x))[0]
+    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x))), kr.kernel(model, hp, x), rtol=0, atol=1e-14)
+    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x), T(xp))), kr.kernel(model, hp, x, xp), rtol=0, atol=1e-14)
     k, dk = cov.kernel_and_grad(T(hp), T(x))
     assert k.shape == (n, n) and dk.shape == (hp.size, n, n)
-    np.testing.assert_allclose(N(dk), pr.kernel_and_grad(model, hp, x)[1], rtol=0, atol=1e-14)
+    np.testing.assert_allclose(N(dk), kr.kernel_and_grad(model, hp, x)[1], rtol=0, atol=1e-14)
     if "wn" not in model:
         return                                                  # (a noise-free model on 50 clustered points is not a fit to rely on)
     gp = pg.Exact_GP(T(x), T(y), cov)
     gp.set_params(T(hp))
     mu, var = gp.predict(T(xp), var="diag")
-    mu_ref, var_ref = pr.predict(model, hp, x, y, xp)
+    mu_ref, var_ref = kr.predict(model, hp, x, y, xp)
     np.testing.assert_allclose(N(mu), mu_ref, rtol=0, atol=1e-10)
     np.testing.assert_allclose(N(var), var_ref, rtol=0, atol=1e-10)      # the prior variance of a product term is prod sigma_c^2
     _, cov_f = gp.predict(T(xp), var="full")
-    np.testing.assert_allclose(N(cov_f), pr.predict(model, hp, x, y, xp, var="full")[1], rtol=0, atol=1e-10)
+    np.testing.assert_allclose(N(cov_f), kr.predict(model, hp, x, y, xp, var="full")[1], rtol=0, atol=1e-10)
     loss, grad = pg.MLE(gp).loss_and_grad(hp.copy())
-    loss_ref, grad_ref = pr.nlml_and_grad(model, hp, x, y)
+    loss_ref, grad_ref = kr.nlml_and_grad(model, hp, x, y)
     np.testing.assert_allclose(loss, loss_ref, rtol=1e-11)
     np.testing.assert_allclose(grad, grad_ref, rtol=1e-9, atol=1e-9 * np.abs(grad_ref).max())
     with pytest.raises(AssertionError):
@@ -317,8 +240,8 @@ def test_memo_key_tells_a_product_from_a_sum(fake_ops):
     l_prod = mle.loss(hp.copy())
     # apart from id(cov), only the terms differ (same kinds, offsets and noise: the layouts are the same)
     assert len(keys) == 2 and keys[0][:-2] == keys[1][:-2] and keys[0][-1] != keys[1][-1] and keys[0][-1][1] == keys[1][-1][1]
-    np.testing.assert_allclose(l_sum, pr.nlml(["se", "per", "wn"], hp, x, y), rtol=1e-11)
-    np.testing.assert_allclose(l_prod, pr.nlml([("se", "per"), "wn"], hp, x, y), rtol=1e-11)
+    np.testing.assert_allclose(l_sum, kr.nlml(["se", "per", "wn"], hp, x, y), rtol=1e-11)
+    np.testing.assert_allclose(l_prod, kr.nlml([("se", "per"), "wn"], hp, x, y), rtol=1e-11)
 
 
 def test_batched_experts_on_the_cpu_double(fake_ops):
@@ -335,9 +258,9 @@ def test_batched_experts_on_the_cpu_double(fake_ops):
     mu, var = gp.predict(T(xp), var="diag")
     loss, grad = pg.MLE(gp).loss_and_grad(hp.copy())
     for c in range(nc):
-        mu_ref, var_ref = pr.predict(model, hp[c], x[c], y[c], xp[c])
+        mu_ref, var_ref = kr.predict(model, hp[c], x[c], y[c], xp[c])
         np.testing.assert_allclose(N(mu[c]), mu_ref, rtol=0, atol=1e-10)
         np.testing.assert_allclose(N(var[c]).ravel(), var_ref, rtol=0, atol=1e-10)
-        l_ref, g_ref = pr.nlml_and_grad(model, hp[c], x[c], y[c])
+        l_ref, g_ref = kr.nlml_and_grad(model, hp[c], x[c], y[c])
         np.testing.assert_allclose(loss[c], l_ref, rtol=1e-11)
         np.testing.assert_allclose(grad[c], g_ref, rtol=1e-9, atol=1e-9 * np.abs(g_ref).max())

@@ -1,12 +1,12 @@
 """GPU tier of Product: a product spec (PG_SPEC_PRODUCT in pg_covspec.ncomp) through every covariance path -- the C ABI entry points,
-the multi-pass plans of a Compose that holds products, and the model layer -- against the restatement of tests/product_ref.py.
+the multi-pass plans of a Compose that holds products, and the model layer -- against the restatement of tests/kernel_ref.py.
 
 Shapes: n = 130 (d = 1, 8) or 330 (d = 3, 17: six 64-tiles, a second strip of the gradient's four-tile strips, a ragged edge) against m = 70;
 d = 17 is past the d <= 16 boundary of the DMAX instantiations.  Data in [-3, 3]^d, sigmas in [0.7, 1.3].  Allowances are the project's own
 for these entry points (tests/test_periodic_gpu.py, tests/test_xgrad_gpu.py, tests/test_framed_gpu.py): K 1e-13 and dK 1e-12 absolute,
 pg_kernel_xgrad 1e-12 of the largest entry, NLML 1e-10 relative, its gradient 1e-8 of its largest entry, predictions 1e-10, batched against the
 loop 1e-11; fp32: K 4e-6, dK 5e-6 max(1, |dK|), the gradient 3 x 3e-3, pg_kernel_xgrad 1e-4.  The element-wise allowances (K, dK, xgrad) are first
-held against the restatement's OWN rounding error, product_ref in float64 against itself in long double: where a quarter of the allowance
+held against the restatement's OWN rounding error, kernel_ref in float64 against itself in long double: where a quarter of the allowance
 does not cover it the allowance is four times that error, the rule of test_periodic_gpu.py::test_offset_data_against_long_double.  K and the
 cross kernel are compared on the whole of the inputs.  The dK stack, the x*-contraction and the NLML gradient (the long-double dK stack
 contracted with the float64 weights W = K^-1 - a a^T) are compared on the pairs among the first 64 points and 32 test points of the same
@@ -22,56 +22,15 @@ import torch
 import pygpr_amd as pg
 from pygpr_amd import _lib
 
+import kernel_ref as kr
 import loo_ref
-import product_ref as pr
+from kind_tools import N, T, builds, cov_of, dev, grad_inputs, host, one_spec, ops, rel, specs_of  # noqa: F401  (ops: the fixture)
 
 pytestmark = pytest.mark.gpu
 
-CLS = {"per": pg.Periodic, "rq": pg.Rational_quadratic, "se": pg.Squared_exponential, "m52": pg.Matern52, "m32": pg.Matern32,
-       "m12": pg.Matern12, "wn": pg.White_noise}
 FACTORS = [("se", "per"), ("m52", "per"), ("se", "m32"), ("rq", "m12", "per"), ("se", "m32", "rq", "per")]
 N_OF_D = {1: 130, 3: 330, 8: 130, 17: 330}
 M = 70
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from pygpr_amd._ops import get_ops
-
-    return get_ops()
-
-
-def dev(a, dtype=torch.float64):
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda", dtype)
-
-
-def host(t):
-    return t.detach().cpu().double().numpy()
-
-
-def T(a):
-    return torch.from_numpy(np.ascontiguousarray(a))
-
-
-def N(t):
-    return t.detach().cpu().numpy()
-
-
-def cov_of(model):
-    objs = [pg.Product([CLS[p]() for p in t]) if isinstance(t, tuple) else CLS[t]() for t in model]
-    return objs[0] if len(objs) == 1 else pg.Compose(objs)
-
-
-def specs_of(model, d):
-    from pygpr_amd.covar import spec_of
-
-    return spec_of(cov_of(model), d)[0]
-
-
-def one_spec(model, d):
-    specs = specs_of(model, d)
-    assert len(specs) == 1 and specs[0].ncomp & _lib.PG_SPEC_PRODUCT
-    return specs[0]
 
 
 def synth(n, d, seed, m=0):
@@ -93,7 +52,7 @@ def block(part, d, rng):
 
 
 def hp_of(model, d, rng):
-    return np.concatenate([block(p, d, rng) for p in pr.flat(model)])
+    return np.concatenate([block(p, d, rng) for p in kr.flat(model)])
 
 
 def allowance(tol, ref64, ref_ld, scale=1.0):
@@ -101,47 +60,6 @@ def allowance(tol, ref64, ref_ld, scale=1.0):
     against its long-double evaluation, is more than a quarter of it -- then four times that error."""
     err = float(np.abs(ref64 - ref_ld).max())
     return max(tol * scale, 4.0 * err), err
-
-
-def rel(a, ref):
-    a, ref = np.asarray(a, np.float64), np.asarray(ref, np.float64)
-    return float(np.abs(a - ref).max() / max(np.abs(ref).max(), 1e-300))
-
-
-def _grad_inputs(ops, spec, hp, x, y, dtype):
-    """K^-1 (lower) and alpha of the model on the device, in `dtype` (as tests/test_periodic_gpu.py builds them)."""
-    from pygpr_amd._ops import pad_to
-
-    n = x.shape[0]
-    npad = pad_to(n)
-    hpd, xd = dev(hp), dev(x, dtype)
-    k = ops.empty(npad, npad, dtype=dtype)
-    invd = ops.potrf_workspace(npad, dtype)
-    info = torch.zeros(1, dtype=torch.int32, device="cuda")
-    minv = ops.zeros(npad, npad, dtype=dtype)
-    ops.build_factor(spec, hpd, xd, k, invd, info, minv)
-    assert int(info.item()) == 0
-    ypad = ops.zeros(npad, dtype=dtype)
-    ypad[:n] = dev(y, dtype)
-    u, alpha = ops.empty(npad, dtype=dtype), ops.empty(npad, dtype=dtype)
-    ops.trmv(minv, ypad, u, 0)
-    ops.trmv(minv, u, alpha, 1, ops.empty((npad // 256 + 1) * npad, dtype=dtype))
-    kinv = ops.zeros(npad, npad, dtype=dtype)
-    ops.lauum(minv, kinv)
-    return hpd, xd, kinv, alpha
-
-
-def _builds(ops, spec, hp, x, xp, dtype):
-    from pygpr_amd._ops import pad_to
-
-    n, m = x.shape[0], xp.shape[0]
-    npad, mpad = pad_to(n), pad_to(m)
-    hpd, xd, xpd = dev(hp), dev(x, dtype), dev(xp, dtype)
-    full, low, cross = ops.empty(npad, npad, dtype=dtype), ops.zeros(npad, npad, dtype=dtype), ops.empty(mpad, npad, dtype=dtype)
-    ops.kernel_build(spec, hpd, xd, None, full, jitter=1e-7)
-    ops.kernel_build(spec, hpd, xd, None, low, lower_only=True, jitter=1e-7)
-    ops.kernel_build(spec, hpd, xpd, xd, cross)
-    return host(full), host(low), host(cross)
 
 
 # --------------------------------------------------------------------------- 1-3. entry points, symmetry, diagonal, routing
@@ -163,13 +81,13 @@ def test_entry_points_against_the_restatement(ops, monkeypatch, factors, d):
     x, y, xp = synth(n, d, seed=d, m=m)
     model = [factors, "wn"]
     hp = hp_of(model, d, rng)
-    spec, npad, mpad = one_spec(model, d), pad_to(n), pad_to(m)
+    spec, npad, mpad = one_spec(model, d, product=True), pad_to(n), pad_to(m)
     assert spec.ncomp == len(factors) | 0x100
-    ref = pr.kernel(model, hp, x) + 1e-7 * np.eye(n)
-    ref_x = pr.kernel(model, hp, x, xp)
+    ref = kr.kernel(model, hp, x) + 1e-7 * np.eye(n)
+    ref_x = kr.kernel(model, hp, x, xp)
     sub, subq = slice(0, 64), slice(0, 32)                       # the pairs of the long-double yardstick
-    tol_k, err_k = allowance(1e-13, ref, pr.kernel(model, hp, x, dtype=np.longdouble) + np.longdouble(1e-7) * np.eye(n))
-    tol_x, err_x = allowance(1e-13, ref_x, pr.kernel(model, hp, x, xp, dtype=np.longdouble))
+    tol_k, err_k = allowance(1e-13, ref, kr.kernel(model, hp, x, dtype=np.longdouble) + np.longdouble(1e-7) * np.eye(n))
+    tol_x, err_x = allowance(1e-13, ref_x, kr.kernel(model, hp, x, xp, dtype=np.longdouble))
     tol_k = max(tol_k, tol_x)
     sig = [hp[o] for o in spec.off[: len(factors)]]
     f32 = len(factors) == 2
@@ -182,7 +100,7 @@ def test_entry_points_against_the_restatement(ops, monkeypatch, factors, d):
         out = {}
         for mode in ("2", "0"):
             monkeypatch.setenv("PG_KB_MFMA", mode)
-            out[mode] = _builds(ops, spec, hp, x, xp, dtype)
+            out[mode] = builds(ops, spec, hp, x, xp, dtype)
         monkeypatch.delenv("PG_KB_MFMA")
         full, low, cross = out["2"]
         print("%s d=%d %s: K err %.2e, cross err %.2e (bound %.1e; restatement's own %.1e / %.1e)" % (
@@ -228,25 +146,25 @@ def test_entry_points_against_the_restatement(ops, monkeypatch, factors, d):
             ops.kernel_build(spec, dev(hps[e]), dev(xs[e], dtype), None, one, jitter=1e-7)
             assert torch.equal(outb[e], one)
     # ---- the dK stack
-    dk_ref = pr.kernel_and_grad(model, hp, x)[1]
-    tol_dk, err_dk = allowance(1e-12, pr.kernel_and_grad(model, hp, x[sub])[1], pr.kernel_and_grad(model, hp, x[sub], dtype=np.longdouble)[1])
+    dk_ref = kr.kernel_and_grad(model, hp, x)[1]
+    tol_dk, err_dk = allowance(1e-12, kr.kernel_and_grad(model, hp, x[sub])[1], kr.kernel_and_grad(model, hp, x[sub], dtype=np.longdouble)[1])
     for dtype, tol in dtypes(tol_dk, 5e-6 * max(1.0, np.abs(dk_ref).max())):
         dk = ops.kernel_grad_build(spec, dev(hp), dev(x, dtype), ops.empty(hp.size, n, n, dtype=dtype))
         print("%s d=%d %s: dK err %.2e (bound %.1e; restatement's own %.1e)" % ("x".join(factors), d, dtype, np.abs(host(dk) - dk_ref).max(), tol, err_dk))
         np.testing.assert_allclose(host(dk), dk_ref, rtol=0, atol=tol)
     # ---- the fused gradient, single and batched
-    _, grad_ref = pr.nlml_and_grad(model, hp, x, y)
+    _, grad_ref = kr.nlml_and_grad(model, hp, x, y)
     scale = np.abs(grad_ref).max()
     # (the restatement's own error: its float64 and long-double dK stacks on the yardstick's pairs, each contracted with the float64 weights)
     kinv_ref = np.linalg.inv(ref)
     a_ref = kinv_ref @ y
     w_sub = (kinv_ref - np.outer(a_ref, a_ref))[sub, sub]
-    g_64 = 0.5 * np.einsum("ij,pij->p", w_sub, pr.kernel_and_grad(model, hp, x[sub])[1])
-    g_ld = 0.5 * np.einsum("ij,pij->p", w_sub.astype(np.longdouble), pr.kernel_and_grad(model, hp, x[sub], dtype=np.longdouble)[1])
+    g_64 = 0.5 * np.einsum("ij,pij->p", w_sub, kr.kernel_and_grad(model, hp, x[sub])[1])
+    g_ld = 0.5 * np.einsum("ij,pij->p", w_sub.astype(np.longdouble), kr.kernel_and_grad(model, hp, x[sub], dtype=np.longdouble)[1])
     err_g = float(np.abs(g_64 - g_ld).max() / np.abs(g_64).max())
     print("%s d=%d: the restatement's own gradient error / max %.1e" % ("x".join(factors), d, err_g))
     for dtype, tol in dtypes(max(1e-8, 4 * err_g), 3 * 3e-3):
-        hpd, xd, kinv, alpha_v = _grad_inputs(ops, spec, hp, x, y, dtype)
+        hpd, xd, kinv, alpha_v = grad_inputs(ops, spec, hp, x, y, dtype)
         work = ops.empty(ops.nlml_grad_worksize(n, hp.size))
         got = {}
         for mode in ("1", "0"):
@@ -264,12 +182,12 @@ def test_entry_points_against_the_restatement(ops, monkeypatch, factors, d):
                               ops.empty(2 * ops.nlml_grad_worksize(n, hp.size)))
         assert np.array_equal(host(gb[0]), got["1"]) and np.array_equal(host(gb[1]), got["1"])
     # ---- derivatives in the test points
-    dks = pr.kernel_xgrad(model, hp, x, xp)                                           # [d, m, n]
+    dks = kr.kernel_xgrad(model, hp, x, xp)                                           # [d, m, n]
     u, b = rng.standard_normal(n), rng.standard_normal((m, n))
     ref_u, ref_b = np.einsum("kpi,i->pk", dks, u), np.einsum("kpi,pi->pk", dks, b)
     # (the restatement's own error in the contraction, on the yardstick's pairs: relative to the largest entry like the check itself)
-    sub_64 = np.einsum("kpi,pi->pk", pr.kernel_xgrad(model, hp, x[sub], xp[subq]), b[subq, sub])
-    sub_ld = np.einsum("kpi,pi->pk", pr.kernel_xgrad(model, hp, x[sub], xp[subq], dtype=np.longdouble), b[subq, sub].astype(np.longdouble))
+    sub_64 = np.einsum("kpi,pi->pk", kr.kernel_xgrad(model, hp, x[sub], xp[subq]), b[subq, sub])
+    sub_ld = np.einsum("kpi,pi->pk", kr.kernel_xgrad(model, hp, x[sub], xp[subq], dtype=np.longdouble), b[subq, sub].astype(np.longdouble))
     err_xg = float(np.abs(sub_64 - sub_ld).max() / np.abs(sub_64).max())
     for dtype, tol in dtypes(max(1e-12, 4 * err_xg), 1e-4):
         for trans_b in (False, True):
@@ -316,8 +234,8 @@ def test_underflowing_factor_gives_zero_not_nan(ops):
     far[:65, 65:] = far[65:, :65] = True
     k, dk = cov_of(model).kernel_and_grad(T(hp), T(x))
     k, dk = N(k), N(dk)
-    k_ref, dk_ref = pr.kernel_and_grad(model, hp, x)
-    assert not k_ref[far].any() and (pr.kernel([("per",)], hp[d + 1: 3 * d + 2], x)[far] > 0).all()
+    k_ref, dk_ref = kr.kernel_and_grad(model, hp, x)
+    assert not k_ref[far].any() and (kr.kernel([("per",)], hp[d + 1: 3 * d + 2], x)[far] > 0).all()
     assert np.isfinite(k).all() and np.isfinite(dk).all()
     assert not k[far].any() and not dk[:, far].any()
     np.testing.assert_allclose(k, k_ref, rtol=0, atol=1e-13)
@@ -325,13 +243,13 @@ def test_underflowing_factor_gives_zero_not_nan(ops):
     gp = pg.Exact_GP(T(x), T(y), cov_of(model))
     gp.set_params(T(hp))
     loss, grad = pg.MLE(gp).loss_and_grad(hp.copy())
-    loss_ref, grad_ref = pr.nlml_and_grad(model, hp, x, y)
+    loss_ref, grad_ref = kr.nlml_and_grad(model, hp, x, y)
     assert np.isfinite(grad).all()
     np.testing.assert_allclose(loss, loss_ref, rtol=1e-10)
     np.testing.assert_allclose(grad, grad_ref, rtol=1e-8, atol=1e-8 * np.abs(grad_ref).max())
     xp = x[:M] + 0.01
     _, _, dmean, dvar = gp.predict_grad(T(xp), var="diag")
-    rdm, rdv = pr.predict_grads(model, hp, x, y, xp)
+    rdm, rdv = kr.predict_grads(model, hp, x, y, xp)
     assert np.isfinite(N(dmean)).all() and rel(N(dmean), rdm) <= 1e-9 and rel(N(dvar), rdv) <= 1e-9
 
 
@@ -347,11 +265,11 @@ def test_nan_coordinate_and_nan_period(ops):
     hp = hp_of(model, d, rng)
     hp_nan = hp.copy()
     hp_nan[2 * d + 3] = np.nan                                   # a period
-    spec = one_spec(model, d)
+    spec = one_spec(model, d, product=True)
     pad = np.eye(128)[n:, :]
     with np.errstate(invalid="ignore"):
         for xx, hh in ((xn, hp), (x, hp_nan)):
-            k_ref, dk_ref = pr.kernel_and_grad(model, hh, xx)
+            k_ref, dk_ref = kr.kernel_and_grad(model, hh, xx)
             assert np.isnan(k_ref).any() and (np.isfinite(k_ref).any() or hh is hp_nan)
             for dt in (torch.float64, torch.float32):
                 k = ops.empty(128, 128, dtype=dt)
@@ -378,21 +296,21 @@ def test_products_inside_a_longer_sum(model):
     specs = specs_of(model, d)
     assert len(specs) == len([t for t in model if isinstance(t, tuple)]) + 1 and specs[0].nnoise == 1 and not specs[0].ncomp & 0x100
     assert all(sp.ncomp & 0x100 and sp.nnoise == 0 for sp in specs[1:])
-    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x))), pr.kernel(model, hp, x), rtol=0, atol=1e-13)
-    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x), T(xp))), pr.kernel(model, hp, x, xp), rtol=0, atol=1e-13)
-    np.testing.assert_allclose(N(cov.kernel_and_grad(T(hp), T(x))[1]), pr.kernel_and_grad(model, hp, x)[1], rtol=0, atol=1e-12)
+    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x))), kr.kernel(model, hp, x), rtol=0, atol=1e-13)
+    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x), T(xp))), kr.kernel(model, hp, x, xp), rtol=0, atol=1e-13)
+    np.testing.assert_allclose(N(cov.kernel_and_grad(T(hp), T(x))[1]), kr.kernel_and_grad(model, hp, x)[1], rtol=0, atol=1e-12)
     gp = pg.Exact_GP(T(x), T(y), cov)
     gp.set_params(T(hp))
     loss, grad = pg.MLE(gp).loss_and_grad(hp.copy())
-    loss_ref, grad_ref = pr.nlml_and_grad(model, hp, x, y)
+    loss_ref, grad_ref = kr.nlml_and_grad(model, hp, x, y)
     np.testing.assert_allclose(loss, loss_ref, rtol=1e-10)
     np.testing.assert_allclose(grad, grad_ref, rtol=1e-8, atol=1e-8 * np.abs(grad_ref).max())
     mu, var = gp.predict(T(xp), var="diag")
-    mu_ref, var_ref = pr.predict(model, hp, x, y, xp)
+    mu_ref, var_ref = kr.predict(model, hp, x, y, xp)
     np.testing.assert_allclose(N(mu), mu_ref, rtol=0, atol=1e-10)
     np.testing.assert_allclose(N(var), var_ref, rtol=0, atol=1e-10)
     _, _, dmean, dvar = gp.predict_grad(T(xp), var="diag")
-    rdm, rdv = pr.predict_grads(model, hp, x, y, xp)
+    rdm, rdv = kr.predict_grads(model, hp, x, y, xp)
     assert rel(N(dmean), rdm) <= 1e-9 and rel(N(dvar), rdv) <= 1e-9
 
 
@@ -416,14 +334,14 @@ def lp():
 def test_exact_gp_and_mle(lp):
     x, y, xp, hp, gp = (lp[k] for k in ("x", "y", "xp", "hp", "gp"))
     mu, var = gp.predict(T(xp), var="diag")
-    mu_ref, var_ref = pr.predict(LP, hp, x, y, xp)
+    mu_ref, var_ref = kr.predict(LP, hp, x, y, xp)
     np.testing.assert_allclose(N(mu), mu_ref, rtol=0, atol=1e-10)
     np.testing.assert_allclose(N(var), var_ref, rtol=0, atol=1e-10)
     mu_f, cov_f = gp.predict(T(xp), var="full")
     np.testing.assert_allclose(N(mu_f), mu_ref, rtol=0, atol=1e-10)
-    np.testing.assert_allclose(N(cov_f), pr.predict(LP, hp, x, y, xp, var="full")[1], rtol=0, atol=1e-10)
+    np.testing.assert_allclose(N(cov_f), kr.predict(LP, hp, x, y, xp, var="full")[1], rtol=0, atol=1e-10)
     mle = pg.MLE(gp)
-    loss_ref, grad_ref = pr.nlml_and_grad(LP, hp, x, y)
+    loss_ref, grad_ref = kr.nlml_and_grad(LP, hp, x, y)
     np.testing.assert_allclose(mle.loss(hp.copy()), loss_ref, rtol=1e-10)
     np.testing.assert_allclose(mle.grad(hp.copy()), grad_ref, rtol=1e-8, atol=1e-8 * np.abs(grad_ref).max())
     loss, grad = pg.MLE(gp).loss_and_grad(hp.copy())
@@ -434,7 +352,7 @@ def test_exact_gp_and_mle(lp):
 def test_predict_grad_and_autograd(lp):
     x, y, xp, hp, gp, rng = (lp[k] for k in ("x", "y", "xp", "hp", "gp", "rng"))
     mean, var, dmean, dvar = gp.predict_grad(T(xp), var="diag")
-    rdm, rdv = pr.predict_grads(LP, hp, x, y, xp)
+    rdm, rdv = kr.predict_grads(LP, hp, x, y, xp)
     assert rel(N(dmean), rdm) <= 1e-9 and rel(N(dvar), rdv) <= 1e-9
     g_mu = rng.standard_normal(M)
     for var_kind in ("none", "diag", "full"):
@@ -443,7 +361,7 @@ def test_predict_grad_and_autograd(lp):
         out = gp.predict(xq, var=var_kind)
         loss = (dev(g_mu) * out[0]).sum() + ((dev(g_2) * out[1]).sum() if var_kind != "none" else 0.0)
         loss.backward()
-        assert rel(N(xq.grad), pr.predict_vjp(LP, hp, x, y, xp, var_kind, g_mu, g_2)) <= 1e-9, var_kind
+        assert rel(N(xq.grad), kr.predict_vjp(LP, hp, x, y, xp, var_kind, g_mu, g_2)) <= 1e-9, var_kind
 
 
 def test_append_equals_fresh_fit(lp):
@@ -466,21 +384,17 @@ def test_append_equals_fresh_fit(lp):
 
 
 def test_loo(lp):
-    """loo_predict and LOO(model).loss_and_grad against loo_ref's closed forms (R&W 5.10 - 5.13) on product_ref's kernel and slabs."""
+    """loo_predict and LOO(model).loss_and_grad against loo_ref's closed forms (R&W 5.10 - 5.13) on kernel_ref's kernel and slabs."""
     x, y, hp, gp = (lp[k] for k in ("x", "y", "hp", "gp"))
     n = x.shape[0]
-    kinv = np.linalg.inv(pr.kernel(LP, hp, x) + pr.JITTER * np.eye(n))
+    kinv = np.linalg.inv(kr.kernel(LP, hp, x) + kr.JITTER * np.eye(n))
     kinv = 0.5 * (kinv + kinv.T)
     alpha, c = kinv @ y, np.diag(kinv).copy()
     mu, var = gp.loo_predict()
     np.testing.assert_allclose(N(mu), y - alpha / c, rtol=0, atol=1e-10)
     np.testing.assert_allclose(N(var), 1.0 / c, rtol=0, atol=1e-10)
     loss_ref = loo_ref.loss_from(y - alpha / c, 1.0 / c, y)
-    g_ref = np.zeros(hp.size)
-    for j, slab in pr._grad_terms(LP, hp, x):
-        z = kinv @ slab
-        zk_diag = np.einsum("ij,ji->i", z, kinv)
-        g_ref[j] = -float(np.sum((alpha * (z @ alpha) - 0.5 * (1.0 + alpha * alpha / c) * zk_diag) / c))
+    g_ref = loo_ref.grad_from(LP, hp, x, kinv, alpha, c)
     loss, grad = pg.LOO(gp).loss_and_grad(hp.copy())
     np.testing.assert_allclose(loss, loss_ref, rtol=1e-10)
     np.testing.assert_allclose(grad, g_ref, rtol=1e-8, atol=1e-8 * np.abs(g_ref).max())
@@ -495,11 +409,11 @@ def test_sampler_mean_and_factor(lp):
     assert torch.equal(smp.mean, pm)
     L, c = smp.chol.double().numpy(), N(pc)
     assert np.abs(L @ L.T - (c + 1e-7 * np.eye(M))).max() / np.abs(c).max() <= 1e-12
-    np.testing.assert_allclose(c, pr.predict(LP, hp, x, y, xp, var="full")[1], rtol=0, atol=1e-10)
+    np.testing.assert_allclose(c, kr.predict(LP, hp, x, y, xp, var="full")[1], rtol=0, atol=1e-10)
     prior = gp.sampler(T(xp), noise=False, jitter=1e-7, prior=True)
     assert not prior.mean.any()
     L = prior.chol.double().numpy()
-    kpp = pr.kernel(LP[:1], hp[:-1], xp) + 1e-7 * np.eye(M)      # noise=False: the latent function
+    kpp = kr.kernel(LP[:1], hp[:-1], xp) + 1e-7 * np.eye(M)      # noise=False: the latent function
     assert np.abs(L @ L.T - kpp).max() / np.abs(kpp).max() <= 1e-12
 
 
@@ -527,13 +441,13 @@ def test_batched_experts_match_their_loop():
         l1, g1 = pg.MLE(one).loss_and_grad(hp[c].copy())
         np.testing.assert_allclose(loss[c], l1, rtol=1e-11)
         np.testing.assert_allclose(grad[c], g1, rtol=1e-9, atol=1e-9 * np.abs(g1).max())
-        l_ref, g_ref = pr.nlml_and_grad(LP, hp[c], x[c], y[c])
+        l_ref, g_ref = kr.nlml_and_grad(LP, hp[c], x[c], y[c])
         np.testing.assert_allclose(l1, l_ref, rtol=1e-10)
         np.testing.assert_allclose(g1, g_ref, rtol=1e-8, atol=1e-8 * np.abs(g_ref).max())
-        mu_ref, var_ref = pr.predict(LP, hp[c], x[c], y[c], xp[c])
+        mu_ref, var_ref = kr.predict(LP, hp[c], x[c], y[c], xp[c])
         np.testing.assert_allclose(N(mu1), mu_ref, rtol=0, atol=1e-10)
         np.testing.assert_allclose(N(var1).ravel(), var_ref, rtol=0, atol=1e-10)      # the device forms prod sigma^2 for the batch
-        rdm, rdv = pr.predict_grads(LP, hp[c], x[c], y[c], xp[c])
+        rdm, rdv = kr.predict_grads(LP, hp[c], x[c], y[c], xp[c])
         assert rel(N(dmean[c]), rdm) <= 1e-9 and rel(N(dvar[c]), rdv) <= 1e-9
 
 
@@ -549,7 +463,7 @@ def test_grbcm():
     model.gpg.set_params(T(hp_g))
     model.gpl.set_params(T(hp_l))
     mu, var = model.predict(T(xs), var="diag")
-    mu_ref, var_ref = pr.grbcm_predict(LP, hp_g, hp_l, xl, yl, xg, yg, xs)
+    mu_ref, var_ref = kr.grbcm_predict(LP, hp_g, hp_l, xl, yl, xg, yg, xs)
     np.testing.assert_allclose(N(mu), mu_ref, rtol=0, atol=1e-9)
     np.testing.assert_allclose(N(var).ravel(), var_ref, rtol=1e-9, atol=1e-11)
 
@@ -559,7 +473,7 @@ def test_sk_wrap(lp):
     gp = pg.Exact_GP(T(x[:10]), T(y[:10]), cov_of(LP))
     gp.set_params(T(hp))
     sk = pg.SK_WRAP(gp).fit(T(x), T(y))
-    np.testing.assert_allclose(N(sk.predict(T(xp))), pr.predict(LP, hp, x, y, xp)[0], rtol=0, atol=1e-10)
+    np.testing.assert_allclose(N(sk.predict(T(xp))), kr.predict(LP, hp, x, y, xp)[0], rtol=0, atol=1e-10)
 
 
 # --------------------------------------------------------------------------- 9. refusals

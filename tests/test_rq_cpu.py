@@ -1,4 +1,4 @@
-"""CPU tier of the rational quadratic: the NumPy restatement of tests/rq_ref.py against central differences of itself and against the
+"""CPU tier of the rational quadratic: the NumPy restatement of tests/kernel_ref.py against central differences of itself and against the
 squared exponential it tends to, the Python side of the new kind (its d + 2 wide block through layout / spec_of), and the public surface
 on a CPU double of the device ops backed by the restatement."""
 import os
@@ -9,15 +9,12 @@ import pytest
 import torch
 
 import pygpr_amd as pg
-from pygpr_amd import _lib, _ops
+from pygpr_amd import _lib
 from oracle import pygpr_oracle as orc
 
-import matern_ref as mr
-import rq_ref as rq
-from oracle_ops import OracleOps, _np, _passes
-
-PART_OF_KIND = {0: "se", 1: "m52", 3: "m32", 4: "m12", 6: "rq"}
-CLS = {"rq": pg.Rational_quadratic, "se": pg.Squared_exponential, "m32": pg.Matern32, "wn": pg.White_noise}
+import kernel_ref as kr
+from kind_tools import N, T, compose
+from oracle_ops import fake_ops  # noqa: F401  (fake_ops: the fixture)
 
 # Central differences with step h: truncation h^2 |f'''| / 6, rounding eps |f| / h.  The kernel and its derivatives of every order are
 # O(1) here (sigma, l, alpha in [0.5, 1.5], points in the unit cube, |f'''| <= ~60 from the chain rule through the squares):
@@ -38,21 +35,21 @@ def test_restatement_gradient_matches_central_differences(alpha):
     x, xp, hp = _data(alpha=alpha)
     parts = ["rq", "wn"]
     hp = np.append(hp, 0.3)
-    k, dk = rq.kernel_and_grad(parts, hp, x)
+    k, dk = kr.kernel_and_grad(parts, hp, x)
     assert dk.shape == (hp.size,) + k.shape and hp.size == 3 + 2 + 1 and np.isfinite(dk).all()
     for p in range(hp.size):
         e = np.zeros(hp.size)
         e[p] = H
-        fd = (rq.kernel(parts, hp + e, x) - rq.kernel(parts, hp - e, x)) / (2 * H)
+        fd = (kr.kernel(parts, hp + e, x) - kr.kernel(parts, hp - e, x)) / (2 * H)
         np.testing.assert_allclose(dk[p], fd, rtol=0, atol=FD_ATOL)
     shape = dk[3 + 1]
     assert not np.diag(shape).any() and shape[2, 5] == 0.0 and (shape <= 0.0).all()      # 0 at sq = 0; t/(1+t) <= log1p(t)
     # x*-derivative of the cross kernel
-    dks = rq.kernel_xgrad(parts, hp, x, xp)
+    dks = kr.kernel_xgrad(parts, hp, x, xp)
     for kk in range(x.shape[1]):
         e = np.zeros_like(xp)
         e[:, kk] = H
-        fd = (rq.kernel(parts, hp, x, xp + e) - rq.kernel(parts, hp, x, xp - e)) / (2 * H)
+        fd = (kr.kernel(parts, hp, x, xp + e) - kr.kernel(parts, hp, x, xp - e)) / (2 * H)
         np.testing.assert_allclose(dks[kk], fd, rtol=0, atol=FD_ATOL)
 
 
@@ -64,10 +61,10 @@ def test_restatement_prediction_derivatives_match_central_differences():
     rng = np.random.default_rng(1)
     m = xp.shape[0]
     g_mu, g_d, g_f = rng.standard_normal(m), rng.standard_normal(m), rng.standard_normal((m, m))
-    dmean, dvar = rq.predict_grads(parts, hp, x, y, xp)
+    dmean, dvar = kr.predict_grads(parts, hp, x, y, xp)
 
     def loss(q, var, g2):
-        mu, v = rq.predict(parts, hp, x, y, q, var=var)
+        mu, v = kr.predict(parts, hp, x, y, q, var=var)
         return float(g_mu @ mu + np.sum(g2 * v))
 
     # (K^-1 multiplies the rounding term: 1 / (sigma_n^2 + jitter) ~ 11, so ten times the kernel's bound)
@@ -75,12 +72,12 @@ def test_restatement_prediction_derivatives_match_central_differences():
         for kk in range(x.shape[1]):
             e = np.zeros_like(xp)
             e[p, kk] = H
-            fd_mu = (rq.predict(parts, hp, x, y, xp + e)[0][p] - rq.predict(parts, hp, x, y, xp - e)[0][p]) / (2 * H)
-            fd_v = (rq.predict(parts, hp, x, y, xp + e)[1][p] - rq.predict(parts, hp, x, y, xp - e)[1][p]) / (2 * H)
+            fd_mu = (kr.predict(parts, hp, x, y, xp + e)[0][p] - kr.predict(parts, hp, x, y, xp - e)[0][p]) / (2 * H)
+            fd_v = (kr.predict(parts, hp, x, y, xp + e)[1][p] - kr.predict(parts, hp, x, y, xp - e)[1][p]) / (2 * H)
             assert abs(fd_mu - dmean[p, kk]) <= 10 * FD_ATOL and abs(fd_v - dvar[p, kk]) <= 10 * FD_ATOL
             for var, g2 in (("diag", g_d), ("full", g_f)):
                 fd = (loss(xp + e, var, g2) - loss(xp - e, var, g2)) / (2 * H)
-                assert abs(fd - rq.predict_vjp(parts, hp, x, y, xp, var, g_mu, g2)[p, kk]) <= 100 * FD_ATOL
+                assert abs(fd - kr.predict_vjp(parts, hp, x, y, xp, var, g_mu, g2)[p, kk]) <= 100 * FD_ATOL
 
 
 def test_restatement_nlml_gradient_matches_central_differences():
@@ -88,19 +85,19 @@ def test_restatement_nlml_gradient_matches_central_differences():
     x, y = orc.synth(40, 3, seed=2)
     parts = ["rq", "m32", "wn"]
     hp = np.concatenate([[1.1], 0.5 + rng.random(3), [0.7], [0.7], 0.5 + rng.random(3), [0.2]])
-    loss, g = rq.nlml_and_grad(parts, hp, x, y)
-    k, dk = rq.kernel_and_grad(parts, hp, x)
-    k[np.diag_indices_from(k)] += rq.JITTER
+    loss, g = kr.nlml_and_grad(parts, hp, x, y)
+    k, dk = kr.kernel_and_grad(parts, hp, x)
+    k[np.diag_indices_from(k)] += kr.JITTER
     kinv = np.linalg.inv(k)
     a = kinv @ y
     np.testing.assert_allclose(g, -0.5 * (np.einsum("i,kij,j->k", a, dk, a) - np.einsum("ij,kji->k", kinv, dk)), rtol=1e-9, atol=1e-11)
-    np.testing.assert_allclose(loss, rq.nlml(parts, hp, x, y), rtol=1e-14)
-    # the NLML of 40 points: |f| ~ 50 and K^-1 ~ 1 / sigma_n^2 = 25 in every derivative -- the step and bounds of matern_ref's own test
+    np.testing.assert_allclose(loss, kr.nlml(parts, hp, x, y), rtol=1e-14)
+    # the NLML of 40 points: |f| ~ 50 and K^-1 ~ 1 / sigma_n^2 = 25 in every derivative -- the step and bounds of the Matern family's own test
     h = 1e-6
     for p in range(hp.size):
         e = np.zeros(hp.size)
         e[p] = h
-        np.testing.assert_allclose(g[p], (rq.nlml(parts, hp + e, x, y) - rq.nlml(parts, hp - e, x, y)) / (2 * h), rtol=1e-5, atol=1e-6)
+        np.testing.assert_allclose(g[p], (kr.nlml(parts, hp + e, x, y) - kr.nlml(parts, hp - e, x, y)) / (2 * h), rtol=1e-5, atol=1e-6)
 
 
 def test_se_limit():
@@ -109,12 +106,12 @@ def test_se_limit():
     x, xp, hp = _data()
     hp[-1] = 1.0e4
     for q in (None, xp):
-        k_rq = rq.kernel(["rq"], hp, x, q)
-        k_se = mr.kernel(["se"], hp[:-1], x, q)
-        sq = mr._sq(hp, x, q)
+        k_rq = kr.kernel(["rq"], hp, x, q)
+        k_se = kr.kernel(["se"], hp[:-1], x, q)
+        sq = kr.sqdist(hp, x, q)
         assert (k_rq - k_se >= -4 * np.finfo(float).eps * k_se).all()
         assert (k_rq - k_se <= k_se * np.expm1(sq * sq / 2.0e8) + 4 * np.finfo(float).eps * k_se).all()
-    assert (rq.kernel(["rq"], hp, x) - mr.kernel(["se"], hp[:-1], x)).max() > 0.0
+    assert (kr.kernel(["rq"], hp, x) - kr.kernel(["se"], hp[:-1], x)).max() > 0.0
 
 
 def test_layout_of_the_new_kind():
@@ -145,67 +142,6 @@ def test_kind_constant_matches_the_header():
 
 
 # ---- the public surface on a CPU double of the device ops, backed by the restatement ------------------------------------------------
-class RqOracleOps(OracleOps):
-    """OracleOps whose covariance calls go through rq_ref (every kind, the d + 2 wide block included)."""
-
-    @staticmethod
-    def _model(spec, hp, d):
-        """(parts, hp) of a standalone model holding the spec's children: their blocks in spec order, the noise terms behind."""
-        parts, vals, index = [], [], []
-        for sp in _passes(spec):
-            for c in range(sp.ncomp):
-                part = PART_OF_KIND[sp.kind[c]]
-                parts.append(part)
-                index += list(range(sp.off[c], sp.off[c] + rq.width(part, d)))
-            for i in range(sp.nnoise):
-                parts.append("wn")
-                index.append(sp.noise_off[i])
-        return parts, hp[index], index
-
-    def kernel_build(self, spec, hp, xr, xc, out, lower_only=False, jitter=0.0):
-        x = _np(xr).astype(np.float64)
-        parts, h, _ = self._model(spec, _np(hp), x.shape[1])
-        o = _np(out)
-        if xc is None:
-            n = x.shape[0]
-            full = np.eye(o.shape[0])
-            full[:n, :n] = rq.kernel(parts, h, x) + jitter * np.eye(n)
-            if lower_only:
-                mask = np.tril(np.ones_like(full, dtype=bool))
-                o[mask] = full[mask]
-            else:
-                o[...] = full
-        else:
-            xq = _np(xc).astype(np.float64)
-            o[...] = 0.0
-            o[: x.shape[0], : xq.shape[0]] = rq.kernel(parts, h, xq, x)
-        return out
-
-    def kernel_grad_build(self, spec, hp, x, out):
-        xx = _np(x).astype(np.float64)
-        parts, h, index = self._model(spec, _np(hp), xx.shape[1])
-        o = _np(out)
-        o[...] = 0.0
-        o[index] = rq.kernel_and_grad(parts, h, xx)[1]
-        return out
-
-
-@pytest.fixture
-def fake_ops(monkeypatch, tmp_path):
-    ops = RqOracleOps()
-    monkeypatch.setattr(_ops, "_OPS", ops)
-    monkeypatch.chdir(tmp_path)
-    return ops
-
-
-def T(a):
-    return torch.from_numpy(np.ascontiguousarray(a))
-
-
-def N(t):
-    return t.detach().cpu().numpy()
-
-
 @pytest.mark.parametrize("parts", [["rq", "wn"], ["wn", "rq", "m32"]], ids=lambda p: "+".join(p))
 def test_public_surface_on_the_cpu_double(fake_ops, parts):
     rng = np.random.default_rng(7)
@@ -213,22 +149,22 @@ def test_public_surface_on_the_cpu_double(fake_ops, parts):
     x, y = orc.synth(n, d, seed=4)
     xp = rng.random((m, d))
     hp = np.concatenate([[0.2] if p == "wn" else np.concatenate([[1.1], 0.5 + rng.random(d), [0.8] if p == "rq" else []]) for p in parts])
-    cov = pg.Compose([CLS[p]() for p in parts])
-    assert hp.size == rq.nhp_of(parts, d) == cov.get_params_shape(T(x))[0]
-    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x))), rq.kernel(parts, hp, x), rtol=0, atol=1e-14)
-    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x), T(xp))), rq.kernel(parts, hp, x, xp), rtol=0, atol=1e-14)
+    cov = compose(parts)
+    assert hp.size == kr.nhp_of(parts, d) == cov.get_params_shape(T(x))[0]
+    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x))), kr.kernel(parts, hp, x), rtol=0, atol=1e-14)
+    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x), T(xp))), kr.kernel(parts, hp, x, xp), rtol=0, atol=1e-14)
     k, dk = cov.kernel_and_grad(T(hp), T(x))
-    np.testing.assert_allclose(N(dk), rq.kernel_and_grad(parts, hp, x)[1], rtol=0, atol=1e-14)
+    np.testing.assert_allclose(N(dk), kr.kernel_and_grad(parts, hp, x)[1], rtol=0, atol=1e-14)
     gp = pg.Exact_GP(T(x), T(y), cov)
     gp.set_params(T(hp))
     mu, var = gp.predict(T(xp), var="diag")
-    mu_ref, var_ref = rq.predict(parts, hp, x, y, xp)
+    mu_ref, var_ref = kr.predict(parts, hp, x, y, xp)
     np.testing.assert_allclose(N(mu), mu_ref, rtol=0, atol=1e-10)
     np.testing.assert_allclose(N(var), var_ref, rtol=0, atol=1e-10)
     _, cov_f = gp.predict(T(xp), var="full")
-    np.testing.assert_allclose(N(cov_f), rq.predict(parts, hp, x, y, xp, var="full")[1], rtol=0, atol=1e-10)
+    np.testing.assert_allclose(N(cov_f), kr.predict(parts, hp, x, y, xp, var="full")[1], rtol=0, atol=1e-10)
     loss, grad = pg.MLE(gp).loss_and_grad(hp.copy())
-    loss_ref, grad_ref = rq.nlml_and_grad(parts, hp, x, y)
+    loss_ref, grad_ref = kr.nlml_and_grad(parts, hp, x, y)
     np.testing.assert_allclose(loss, loss_ref, rtol=1e-11)
     np.testing.assert_allclose(grad, grad_ref, rtol=1e-9, atol=1e-9 * np.abs(grad_ref).max())
     with pytest.raises(AssertionError):
@@ -243,15 +179,15 @@ def test_batched_experts_on_the_cpu_double(fake_ops):
     y = np.sin(-x.sum(-1)) + 0.1 * rng.standard_normal((nc, n))
     xp = rng.random((nc, m, d))
     hp = np.concatenate([0.8 + 0.4 * rng.random((nc, 1)), 0.5 + rng.random((nc, d)), 0.6 + rng.random((nc, 1)), np.full((nc, 1), 0.2)], axis=1)
-    gp = pg.Exact_GP(T(x), T(y), pg.Compose([CLS[p]() for p in parts]))
+    gp = pg.Exact_GP(T(x), T(y), compose(parts))
     assert list(gp.cov.get_params_shape(T(x))) == [nc, d + 3]
     gp.set_params(T(hp))
     mu, var = gp.predict(T(xp), var="diag")
     loss, grad = pg.MLE(gp).loss_and_grad(hp.copy())
     for c in range(nc):
-        mu_ref, var_ref = rq.predict(parts, hp[c], x[c], y[c], xp[c])
+        mu_ref, var_ref = kr.predict(parts, hp[c], x[c], y[c], xp[c])
         np.testing.assert_allclose(N(mu[c]), mu_ref, rtol=0, atol=1e-10)
         np.testing.assert_allclose(N(var[c]).ravel(), var_ref, rtol=0, atol=1e-10)
-        l_ref, g_ref = rq.nlml_and_grad(parts, hp[c], x[c], y[c])
+        l_ref, g_ref = kr.nlml_and_grad(parts, hp[c], x[c], y[c])
         np.testing.assert_allclose(loss[c], l_ref, rtol=1e-11)
         np.testing.assert_allclose(grad[c], g_ref, rtol=1e-9, atol=1e-9 * np.abs(g_ref).max())

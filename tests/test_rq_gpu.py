@@ -1,6 +1,6 @@
 """GPU tier of the rational quadratic: the kind whose block is d + 2 wide through every covariance path (C ABI entry points, the dK stack
 with its shape slab, the fused gradient with its shape entry, Exact_GP / MLE / LOO / predict_grad / append / batched experts / GRBCM /
-SK_WRAP) against the direct-difference restatement of tests/rq_ref.py.  K is smooth in the squared distance (|dK/dsq| <= sigma^2), so the
+SK_WRAP) against the direct-difference restatement of tests/kernel_ref.py.  K is smooth in the squared distance (|dK/dsq| <= sigma^2), so the
 kind takes the matrix-pipe bodies where Matern-3/2 does; the tolerances are those tests/test_matern_family_gpu.py uses for the same
 quantities."""
 import numpy as np
@@ -10,96 +10,11 @@ import torch
 import pygpr_amd as pg
 from oracle import pygpr_oracle as orc
 
+import kernel_ref as kr
 import loo_ref
-import matern_ref as mr
-import rq_ref as rq
+from kind_tools import N, T, builds, check, compose, dev, grad_inputs, host, near_duplicates, one_spec, ops  # noqa: F401  (ops: the fixture)
 
 pytestmark = pytest.mark.gpu
-
-CLS = {"rq": pg.Rational_quadratic, "m32": pg.Matern32, "se": pg.Squared_exponential, "wn": pg.White_noise}
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from pygpr_amd._ops import get_ops
-
-    return get_ops()
-
-
-def dev(a, dtype=torch.float64):
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda", dtype)
-
-
-def host(t):
-    return t.detach().cpu().double().numpy()
-
-
-def T(a):
-    return torch.from_numpy(np.ascontiguousarray(a))
-
-
-def N(t):
-    return t.detach().cpu().numpy()
-
-
-def compose(parts):
-    return pg.Compose([CLS[p]() for p in parts])
-
-
-def _spec(parts, d):
-    from pygpr_amd.covar import spec_of
-
-    specs, _ = spec_of(compose(parts), d)
-    assert len(specs) == 1
-    return specs[0]
-
-
-def _grad_inputs(ops, parts, hp, x, y, dtype):
-    """K^-1 (lower) and alpha of the model on the device, in `dtype` (as tests/test_matern_family_gpu.py builds them)."""
-    from pygpr_amd._ops import pad_to
-
-    n, d = x.shape
-    npad = pad_to(n)
-    spec = _spec(parts, d)
-    hpd, xd = dev(hp), dev(x, dtype)
-    k = ops.empty(npad, npad, dtype=dtype)
-    invd = ops.potrf_workspace(npad, dtype)
-    info = torch.zeros(1, dtype=torch.int32, device="cuda")
-    minv = ops.zeros(npad, npad, dtype=dtype)
-    ops.build_factor(spec, hpd, xd, k, invd, info, minv)
-    assert int(info.item()) == 0
-    ypad = ops.zeros(npad, dtype=dtype)
-    ypad[:n] = dev(y, dtype)
-    u, alpha = ops.empty(npad, dtype=dtype), ops.empty(npad, dtype=dtype)
-    ops.trmv(minv, ypad, u, 0)
-    ops.trmv(minv, u, alpha, 1, ops.empty((npad // 256 + 1) * npad, dtype=dtype))
-    kinv = ops.zeros(npad, npad, dtype=dtype)
-    ops.lauum(minv, kinv)
-    return spec, hpd, xd, kinv, alpha
-
-
-def _builds(ops, spec, hp, x, xp, dtype):
-    from pygpr_amd._ops import pad_to
-
-    n, m = x.shape[0], xp.shape[0]
-    npad, mpad = pad_to(n), pad_to(m)
-    hpd, xd, xpd = dev(hp), dev(x, dtype), dev(xp, dtype)
-    full, low, cross = ops.empty(npad, npad, dtype=dtype), ops.zeros(npad, npad, dtype=dtype), ops.empty(mpad, npad, dtype=dtype)
-    ops.kernel_build(spec, hpd, xd, None, full, jitter=1e-7)
-    ops.kernel_build(spec, hpd, xd, None, low, lower_only=True, jitter=1e-7)
-    ops.kernel_build(spec, hpd, xpd, xd, cross)
-    return host(full), host(low), host(cross)
-
-
-def rel(a, ref):
-    a, ref = torch.as_tensor(a).detach().cpu().double(), torch.as_tensor(ref).detach().cpu().double()
-    return float((a - ref).abs().max() / ref.abs().max().clamp_min(1e-300))
-
-
-def check(name, a, ref, tol):
-    e = rel(a, ref)
-    print("%-52s rel err %.2e (bound %.0e)" % (name, e, tol))
-    assert e <= tol, (name, e)
 
 
 # --------------------------------------------------------------------------- 1. entry points
@@ -116,14 +31,14 @@ def test_entry_points_against_the_restatement(ops, monkeypatch, d, alpha):
     xp = rng.random((m, d))
     parts = ["rq", "wn"]
     hp = np.concatenate([[1.2], 0.4 + 0.8 * rng.random(d), [alpha], [0.1]])
-    spec, npad = _spec(parts, d), pad_to(n)
-    ref = rq.kernel(parts, hp, x) + 1e-7 * np.eye(n)
-    ref_x = rq.kernel(parts, hp, x, xp)
+    spec, npad = one_spec(parts, d), pad_to(n)
+    ref = kr.kernel(parts, hp, x) + 1e-7 * np.eye(n)
+    ref_x = kr.kernel(parts, hp, x, xp)
     for dtype, tol in ((torch.float64, 2e-14), (torch.float32, 4e-6)):
         out = {}
         for mode in ("2", "0"):
             monkeypatch.setenv("PG_KB_MFMA", mode)
-            out[mode] = _builds(ops, spec, hp, x, xp, dtype)
+            out[mode] = builds(ops, spec, hp, x, xp, dtype)
         monkeypatch.delenv("PG_KB_MFMA")
         for mode in ("2", "0"):
             full, low, cross = out[mode]
@@ -149,11 +64,11 @@ def test_entry_points_against_the_restatement(ops, monkeypatch, d, alpha):
         else:
             np.testing.assert_allclose(full, out["0"][0], atol=tol, rtol=tol)
             np.testing.assert_allclose(cross, out["0"][2], atol=tol, rtol=tol)
-    _, grad_ref = rq.nlml_and_grad(parts, hp, x, y)
+    _, grad_ref = kr.nlml_and_grad(parts, hp, x, y)
     scale = np.abs(grad_ref).max()
     assert grad_ref[d + 1] != 0.0
     for dtype, rtol in ((torch.float64, 1e-9), (torch.float32, 3e-3)):
-        spec, hpd, xd, kinv, alpha_v = _grad_inputs(ops, parts, hp, x, y, dtype)
+        hpd, xd, kinv, alpha_v = grad_inputs(ops, spec, hp, x, y, dtype)
         work = ops.empty(ops.nlml_grad_worksize(n, hp.size))
         got = {}
         for mode in ("1", "0"):
@@ -177,18 +92,6 @@ def test_entry_points_against_the_restatement(ops, monkeypatch, d, alpha):
 
 
 # --------------------------------------------------------------------------- 2. near-duplicates
-def _near_duplicates(rng, d, l, offset):
-    """60 points, then five more at scaled distance r = 0, 1e-12, 1e-9, 1e-6, 1e-3 from points 3, 11, 19, 27, 35 (off-diagonal pairs):
-    the construction of tests/test_matern_family_gpu.py."""
-    x = rng.random((60, d))
-    extra = []
-    for s, i in zip((0.0, 1e-12, 1e-9, 1e-6, 1e-3), (3, 11, 19, 27, 35)):
-        u = rng.standard_normal(d)
-        extra.append(x[i] + s * (u / np.linalg.norm(u)) / l)
-    x = np.concatenate([x, np.array(extra)]) + offset
-    return x, np.sin(-x.sum(1)) + 0.1 * rng.standard_normal(x.shape[0])
-
-
 def test_near_duplicates_on_offset_data(ops, monkeypatch):
     """Near-duplicate pairs on data offset by 1e3.  VALU path (direct differences): K, the dK stack and the shape slab to the Matern
     test's absolute bounds (1e-13 / 4e-6 on K, 1e-12 on dK; the inverse length scales are powers of two, so the staged coordinates are
@@ -200,12 +103,12 @@ def test_near_duplicates_on_offset_data(ops, monkeypatch):
     hp = np.concatenate([[1.2], l, [0.7], [0.1]])
     hp_m = np.concatenate([[1.2], l, [0.1]])
     parts = ["rq", "wn"]
-    x, y = _near_duplicates(rng, d, l, 1.0e3)
+    x, y = near_duplicates(rng, d, l, 1.0e3)
     n = x.shape[0]
-    spec, spec_m = _spec(parts, d), _spec(["m32", "wn"], d)
+    spec, spec_m = one_spec(parts, d), one_spec(["m32", "wn"], d)
     for dtype, tol in ((torch.float64, 1e-13), (torch.float32, 4e-6)):
         xt = x if dtype == torch.float64 else x.astype(np.float32).astype(np.float64)     # the fp32 run's own inputs
-        ref, ref_m = rq.kernel(parts, hp, xt), mr.kernel(["m32", "wn"], hp_m, xt)
+        ref, ref_m = kr.kernel(parts, hp, xt), kr.kernel(["m32", "wn"], hp_m, xt)
         err = {}
         for mode in ("0", "2"):
             monkeypatch.setenv("PG_KB_MFMA", mode)
@@ -216,19 +119,19 @@ def test_near_duplicates_on_offset_data(ops, monkeypatch):
             err[mode] = (np.abs(host(k)[:n, :n] - ref).max(), np.abs(host(km)[:n, :n] - ref_m).max())
             kx = ops.empty(128, 256, dtype=dtype)
             ops.kernel_build(spec, dev(hp), dev(xt[::-1].copy(), dtype), dev(xt, dtype), kx)     # a cross build meets the same pairs
-            errx = np.abs(host(kx)[:n, :n] - rq.kernel(parts, hp, xt, xt[::-1].copy())).max()
+            errx = np.abs(host(kx)[:n, :n] - kr.kernel(parts, hp, xt, xt[::-1].copy())).max()
             print("%s PG_KB_MFMA=%s: K err rq %.2e, Matern-3/2 %.2e; cross rq %.2e" % (dtype, mode, err[mode][0], err[mode][1], errx))
             if mode == "0":
                 assert err[mode][0] <= tol and errx <= tol
             else:
                 assert err[mode][0] <= 2 * err[mode][1] and errx <= 2 * err[mode][1]
         monkeypatch.delenv("PG_KB_MFMA")
-    k_ref, dk_ref = rq.kernel_and_grad(parts, hp, x)
+    k_ref, dk_ref = kr.kernel_and_grad(parts, hp, x)
     _, dk = compose(parts).kernel_and_grad(T(hp), T(x))
     assert np.isfinite(N(dk)).all()
     np.testing.assert_allclose(N(dk), dk_ref, rtol=0, atol=1e-12)                        # (the shape slab is dk[d + 1])
-    loss_ref, grad_ref = rq.nlml_and_grad(parts, hp, x, y)
-    _, gm_ref = mr.nlml_and_grad(["m32", "wn"], hp_m, x, y)
+    loss_ref, grad_ref = kr.nlml_and_grad(parts, hp, x, y)
+    _, gm_ref = kr.nlml_and_grad(["m32", "wn"], hp_m, x, y)
     errs = {}
     for mode in ("0", "1"):
         monkeypatch.setenv("PG_KB_MFMA", mode)
@@ -252,15 +155,15 @@ def test_dk_stack_and_compose(parts):
     xp = rng.random((m, d))
     hp = np.concatenate([[0.1] if p == "wn" else np.concatenate([[1.1], 0.5 + rng.random(d), [0.6] if p == "rq" else []]) for p in parts])
     cov = compose(parts)
-    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x))), rq.kernel(parts, hp, x), rtol=0, atol=1e-13)
-    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x), T(xp))), rq.kernel(parts, hp, x, xp), rtol=0, atol=1e-13)
+    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x))), kr.kernel(parts, hp, x), rtol=0, atol=1e-13)
+    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x), T(xp))), kr.kernel(parts, hp, x, xp), rtol=0, atol=1e-13)
     k, dk = cov.kernel_and_grad(T(hp), T(x))
-    k_ref, dk_ref = rq.kernel_and_grad(parts, hp, x)
-    assert dk.shape == (rq.nhp_of(parts, d), n, n) and dk_ref[d + 1].any()
+    k_ref, dk_ref = kr.kernel_and_grad(parts, hp, x)
+    assert dk.shape == (kr.nhp_of(parts, d), n, n) and dk_ref[d + 1].any()
     np.testing.assert_allclose(N(k), k_ref, rtol=0, atol=1e-13)
     np.testing.assert_allclose(N(dk), dk_ref, rtol=0, atol=1e-12)
     loss, grad = pg.MLE(pg.Exact_GP(T(x), T(y), cov)).loss_and_grad(hp.copy())
-    loss_ref, grad_ref = rq.nlml_and_grad(parts, hp, x, y)
+    loss_ref, grad_ref = kr.nlml_and_grad(parts, hp, x, y)
     np.testing.assert_allclose(loss, loss_ref, rtol=1e-10)
     np.testing.assert_allclose(grad, grad_ref, rtol=1e-8, atol=1e-8 * np.abs(grad_ref).max())
 
@@ -276,11 +179,11 @@ def test_compose_longer_than_one_pass():
     cov = compose(parts)
     from pygpr_amd.covar import spec_of
     assert len(spec_of(cov, d)[0]) == 2
-    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x))), rq.kernel(parts, hp, x), rtol=0, atol=1e-13)
-    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x), T(xp))), rq.kernel(parts, hp, x, xp), rtol=0, atol=1e-13)
-    np.testing.assert_allclose(N(cov.kernel_and_grad(T(hp), T(x))[1]), rq.kernel_and_grad(parts, hp, x)[1], rtol=0, atol=1e-12)
+    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x))), kr.kernel(parts, hp, x), rtol=0, atol=1e-13)
+    np.testing.assert_allclose(N(cov.kernel(T(hp), T(x), T(xp))), kr.kernel(parts, hp, x, xp), rtol=0, atol=1e-13)
+    np.testing.assert_allclose(N(cov.kernel_and_grad(T(hp), T(x))[1]), kr.kernel_and_grad(parts, hp, x)[1], rtol=0, atol=1e-12)
     loss, grad = pg.MLE(pg.Exact_GP(T(x), T(y), cov)).loss_and_grad(hp.copy())
-    loss_ref, grad_ref = rq.nlml_and_grad(parts, hp, x, y)
+    loss_ref, grad_ref = kr.nlml_and_grad(parts, hp, x, y)
     np.testing.assert_allclose(loss, loss_ref, rtol=1e-10)
     np.testing.assert_allclose(grad, grad_ref, rtol=1e-8, atol=1e-8 * np.abs(grad_ref).max())
 
@@ -299,11 +202,11 @@ def test_nan_coordinate_and_nan_shape(ops, monkeypatch):
         monkeypatch.setenv("PG_KB_MFMA", mode)
         for dt in (torch.float64, torch.float32):
             k = ops.empty(256, 256, dtype=dt)
-            ops.kernel_build(_spec(["rq", "wn"], d), dev(hp), dev(xn, dt), None, k, jitter=1e-7)
+            ops.kernel_build(one_spec(["rq", "wn"], d), dev(hp), dev(xn, dt), None, k, jitter=1e-7)
             got = host(k)
             assert np.isnan(got[23, :n]).all() and np.isnan(got[:n, 23]).all()
             assert np.isfinite(np.delete(np.delete(got[:n, :n], 23, 0), 23, 1)).all()
-            ops.kernel_build(_spec(["rq", "wn"], d), dev(hp_nan), dev(x, dt), None, k, jitter=1e-7)
+            ops.kernel_build(one_spec(["rq", "wn"], d), dev(hp_nan), dev(x, dt), None, k, jitter=1e-7)
             assert np.isnan(host(k)[:n, :n]).all()                                     # a NaN shape: every entry
 
 
@@ -321,36 +224,32 @@ def test_exact_gp_and_mle(n, d):
     gp.set_params(T(hp))
     gp.update()
     mu, var = gp.predict(T(xp), var="diag")
-    mu_ref, var_ref = rq.predict(parts, hp, x, y, xp)
+    mu_ref, var_ref = kr.predict(parts, hp, x, y, xp)
     np.testing.assert_allclose(N(mu), mu_ref, rtol=0, atol=1e-10)
     np.testing.assert_allclose(N(var), var_ref, rtol=0, atol=1e-10)
     mu_f, cov_f = gp.predict(T(xp), var="full")
-    _, cov_ref = rq.predict(parts, hp, x, y, xp, var="full")
+    _, cov_ref = kr.predict(parts, hp, x, y, xp, var="full")
     np.testing.assert_allclose(N(mu_f), mu_ref, rtol=0, atol=1e-10)
     np.testing.assert_allclose(N(cov_f), cov_ref, rtol=0, atol=1e-10)
     loss, grad = pg.MLE(gp).loss_and_grad(hp.copy())
-    loss_ref, grad_ref = rq.nlml_and_grad(parts, hp, x, y)
+    loss_ref, grad_ref = kr.nlml_and_grad(parts, hp, x, y)
     np.testing.assert_allclose(loss, loss_ref, rtol=1e-10)
     np.testing.assert_allclose(grad, grad_ref, rtol=1e-8, atol=1e-8 * np.abs(grad_ref).max())
 
 
 def test_loo_loss_and_grad():
-    """LOO(model).loss_and_grad against loo_ref's closed forms (R&W 5.10 - 5.13) on rq_ref's kernel and slabs; the relative bounds of
+    """LOO(model).loss_and_grad against loo_ref's closed forms (R&W 5.10 - 5.13) on kernel_ref's kernel and slabs; the relative bounds of
     tests/test_loo_gpu.py's own comparison are not assumed: loss 1e-10 and gradient 1e-8 of its largest entry, as for the NLML above."""
     parts = ["rq", "wn"]
     n, d = 300, 4
     x, y = orc.synth(n, d, seed=21)
     hp = np.concatenate([[1.1], np.linspace(0.6, 1.2, d), [0.7], [0.3]])
-    k = rq.kernel(parts, hp, x) + rq.JITTER * np.eye(n)
+    k = kr.kernel(parts, hp, x) + kr.JITTER * np.eye(n)
     kinv = np.linalg.inv(k)
     kinv = 0.5 * (kinv + kinv.T)
     alpha, c = kinv @ y, np.diag(kinv).copy()
     loss_ref = loo_ref.loss_from(y - alpha / c, 1.0 / c, y)
-    g_ref = np.zeros(hp.size)
-    for j, slab in rq._grad_terms(parts, hp, x):
-        z = kinv @ slab
-        zk_diag = np.einsum("ij,ji->i", z, kinv)
-        g_ref[j] = -float(np.sum((alpha * (z @ alpha) - 0.5 * (1.0 + alpha * alpha / c) * zk_diag) / c))
+    g_ref = loo_ref.grad_from(parts, hp, x, kinv, alpha, c)
     gp = pg.Exact_GP(T(x), T(y), compose(parts))
     gp.set_params(T(hp))
     loss, grad = pg.LOO(gp).loss_and_grad(hp.copy())
@@ -364,7 +263,7 @@ def test_loo_loss_and_grad():
 
 @pytest.mark.parametrize("parts", [["rq", "wn"], ["rq", "m32", "wn"]], ids=lambda p: "+".join(p))
 def test_predict_grad_and_autograd(parts):
-    """predict_grad and autograd in xp against rq_ref's x*-derivatives: 1e-9 relative to the largest entry, tests/test_xgrad_gpu.py."""
+    """predict_grad and autograd in xp against kernel_ref's x*-derivatives: 1e-9 relative to the largest entry, tests/test_xgrad_gpu.py."""
     rng = np.random.default_rng(1)
     n, m, d = 300, 45, 5
     x = rng.random((n, d))
@@ -375,7 +274,7 @@ def test_predict_grad_and_autograd(parts):
     gp = pg.Exact_GP(T(x), T(y), compose(parts))
     gp.set_params(T(hp))
     mean, var, dmean, dvar = gp.predict_grad(T(xp), var="diag")
-    rdm, rdv = rq.predict_grads(parts, hp, x, y, xp)
+    rdm, rdv = kr.predict_grads(parts, hp, x, y, xp)
     check("predict_grad %s dmean" % "+".join(parts), dmean, T(rdm), 1e-9)
     check("predict_grad %s dvar" % "+".join(parts), dvar, T(rdv), 1e-9)
     g_mu = rng.standard_normal(m)
@@ -385,7 +284,7 @@ def test_predict_grad_and_autograd(parts):
         out = gp.predict(xq, var=var_kind)
         loss = (dev(g_mu) * out[0]).sum() + ((dev(g_2) * out[1]).sum() if var_kind != "none" else 0.0)
         loss.backward()
-        check("autograd %s %s" % ("+".join(parts), var_kind), xq.grad, T(rq.predict_vjp(parts, hp, x, y, xp, var_kind, g_mu, g_2)), 1e-9)
+        check("autograd %s %s" % ("+".join(parts), var_kind), xq.grad, T(kr.predict_vjp(parts, hp, x, y, xp, var_kind, g_mu, g_2)), 1e-9)
 
 
 def test_predict_grad_batched_experts():
@@ -402,7 +301,7 @@ def test_predict_grad_batched_experts():
     mean, var, dmean, dvar = gp.predict_grad(T(xp), var="diag")
     assert dmean.shape == (nc, m, d)
     for c in range(nc):
-        rdm, rdv = rq.predict_grads(parts, hps[c], x[c], y[c], xp)
+        rdm, rdv = kr.predict_grads(parts, hps[c], x[c], y[c], xp)
         check("predict_grad batched expert %d dmean" % c, dmean[c], T(rdm), 1e-9)
         check("predict_grad batched expert %d dvar" % c, dvar[c], T(rdv), 1e-9)
 
@@ -436,7 +335,7 @@ def test_append_equals_fresh_fit():
     lr, grr = pg.MLE(ref).loss_and_grad(hp.numpy().copy())
     check("MLE loss", torch.tensor([float(la)]), torch.tensor([float(lr)]), tol)
     check("MLE grad", torch.from_numpy(ga), torch.from_numpy(grr), tol * 10)
-    mu_ref, _ = rq.predict(parts, hp.numpy(), x.numpy(), y.numpy(), xp.numpy())
+    mu_ref, _ = kr.predict(parts, hp.numpy(), x.numpy(), y.numpy(), xp.numpy())
     np.testing.assert_allclose(N(mu), mu_ref, rtol=0, atol=1e-9)
 
 
@@ -464,10 +363,10 @@ def test_batched_experts_match_their_loop():
         l1, g1 = pg.MLE(one).loss_and_grad(hp[c].copy())
         np.testing.assert_allclose(loss[c], l1, rtol=1e-11)
         np.testing.assert_allclose(grad[c], g1, rtol=1e-9, atol=1e-9 * np.abs(g1).max())
-        l_ref, g_ref = rq.nlml_and_grad(parts, hp[c], x[c], y[c])
+        l_ref, g_ref = kr.nlml_and_grad(parts, hp[c], x[c], y[c])
         np.testing.assert_allclose(l1, l_ref, rtol=1e-10)
         np.testing.assert_allclose(g1, g_ref, rtol=1e-8, atol=1e-8 * np.abs(g_ref).max())
-        mu_ref, var_ref = rq.predict(parts, hp[c], x[c], y[c], xp[c])
+        mu_ref, var_ref = kr.predict(parts, hp[c], x[c], y[c], xp[c])
         np.testing.assert_allclose(N(mu1), mu_ref, rtol=0, atol=1e-10)
         np.testing.assert_allclose(N(var1).ravel(), var_ref, rtol=0, atol=1e-10)
 
@@ -485,7 +384,7 @@ def test_grbcm():
     model.gpg.set_params(T(hp_g))
     model.gpl.set_params(T(hp_l))
     mu, var = model.predict(T(xs), var="diag")
-    mu_ref, var_ref = rq.grbcm_predict(parts, hp_g, hp_l, xl, yl, xg, yg, xs)
+    mu_ref, var_ref = kr.grbcm_predict(parts, hp_g, hp_l, xl, yl, xg, yg, xs)
     np.testing.assert_allclose(N(mu), mu_ref, rtol=0, atol=1e-9)
     np.testing.assert_allclose(N(var).ravel(), var_ref, rtol=1e-9, atol=1e-11)
 
@@ -500,7 +399,7 @@ def test_sk_wrap():
     gp = pg.Exact_GP(T(x[:10]), T(y[:10]), compose(parts))
     gp.set_params(T(hp))
     sk = pg.SK_WRAP(gp).fit(T(x), T(y))
-    np.testing.assert_allclose(N(sk.predict(T(xp))), rq.predict(parts, hp, x, y, xp)[0], rtol=0, atol=1e-10)
+    np.testing.assert_allclose(N(sk.predict(T(xp))), kr.predict(parts, hp, x, y, xp)[0], rtol=0, atol=1e-10)
 
 
 # --------------------------------------------------------------------------- 6. the SE limit
@@ -512,12 +411,12 @@ def test_se_limit_on_the_device(ops, monkeypatch):
     x = rng.random((n, d))
     hp_se = np.concatenate([[1.2], 0.4 + 0.8 * rng.random(d), [0.1]])
     hp = np.concatenate([hp_se[:-1], [1.0e4], [0.1]])
-    sq = mr._sq(hp_se, x)
+    sq = kr.sqdist(hp_se, x)
     for mode in ("2", "0"):
         monkeypatch.setenv("PG_KB_MFMA", mode)
         k, ks = ops.empty(256, 256), ops.empty(256, 256)
-        ops.kernel_build(_spec(["rq", "wn"], d), dev(hp), dev(x), None, k)
-        ops.kernel_build(_spec(["se", "wn"], d), dev(hp_se), dev(x), None, ks)
+        ops.kernel_build(one_spec(["rq", "wn"], d), dev(hp), dev(x), None, k)
+        ops.kernel_build(one_spec(["se", "wn"], d), dev(hp_se), dev(x), None, ks)
         diff, k_se = (host(k) - host(ks))[:n, :n], host(ks)[:n, :n] - 0.01 * np.eye(n)
         print("PG_KB_MFMA=%s: K_RQ - K_SE in [%.2e, %.2e], bound's largest entry %.2e" % (mode, diff.min(), diff.max(), (k_se * np.expm1(sq * sq / 2e8)).max()))
         assert (diff >= -2e-14).all()

@@ -1,11 +1,11 @@
 """CPU tier of the derivatives in the test points: tests/xgrad_ref.py (the torch restatement whose autograd gradients are the GPU tier's
-reference) against central finite differences of tests/matern_ref.predict, for every kind, Compose, the diagonal variance and the full
+reference) against central finite differences of tests/kernel_ref.predict, for every kind, Compose, the diagonal variance and the full
 covariance; the Matern-1/2 convention at r = 0; and the C ABI / Python surface of the new entry points (no GPU needed)."""
 import numpy as np
 import pytest
 import torch
 
-import matern_ref as mr
+import kernel_ref as kr
 import xgrad_ref as xr
 
 KINDS = ["se", "m52", "m32", "m12"]
@@ -41,11 +41,11 @@ def test_reference_diag_against_finite_differences(parts):
     x, y, xp, hp = _problem(parts)
     T = torch.from_numpy
     mean, var, dmean, dvar = xr.predict_grads(parts, T(hp), T(x), T(y), T(xp))
-    m0, v0 = mr.predict(parts, hp, x, y, xp, "diag")
+    m0, v0 = kr.predict(parts, hp, x, y, xp, "diag")
     np.testing.assert_allclose(mean.numpy(), m0, rtol=1e-9, atol=1e-10)
     np.testing.assert_allclose(var.numpy(), v0, rtol=1e-7, atol=1e-9)
-    fm = _fd(lambda a: mr.predict(parts, hp, x, y, a, "diag")[0], xp)      # [m, d, m]
-    fv = _fd(lambda a: mr.predict(parts, hp, x, y, a, "diag")[1], xp)
+    fm = _fd(lambda a: kr.predict(parts, hp, x, y, a, "diag")[0], xp)      # [m, d, m]
+    fv = _fd(lambda a: kr.predict(parts, hp, x, y, a, "diag")[1], xp)
     idx = np.arange(xp.shape[0])
     np.testing.assert_allclose(dmean.numpy(), fm[idx, :, idx], atol=1e-6 * max(1.0, np.abs(fm).max()))
     np.testing.assert_allclose(dvar.numpy(), fv[idx, :, idx], atol=1e-6 * max(1.0, np.abs(fv).max()))
@@ -64,7 +64,7 @@ def test_reference_full_vjp_against_finite_differences(parts):
     g = xr.vjp(parts, T(hp), T(x), T(y), T(xp), "full", T(g_mu), T(g_cov)).numpy()
 
     def loss(a):
-        mean, cov = mr.predict(parts, hp, x, y, a, "full")
+        mean, cov = kr.predict(parts, hp, x, y, a, "full")
         return np.array(g_mu @ mean + np.sum(g_cov * cov))
 
     fd = _fd(loss, xp)
@@ -72,16 +72,16 @@ def test_reference_full_vjp_against_finite_differences(parts):
 
 
 def test_reference_contraction_is_the_weighted_kernel_derivative():
-    """contraction() against the closed form dk/dx*_pk = 2 c base l_k^2 D_k of matern_ref (COEF = 2 c), every kind."""
+    """contraction() against the closed form dk/dx*_pk = 2 c base l_k^2 D_k of kernel_ref (COEF = 2 c), every kind."""
     rng = np.random.default_rng(3)
     d = 4
     xq, z = rng.random((5, d)), rng.random((9, d))
     u, b = rng.standard_normal(9), rng.standard_normal((5, 9))
     for part in KINDS:
         hpc = np.concatenate([[1.2], rng.uniform(0.5, 2.0, d)])
-        sq = mr._sq(hpc, z, xq)
-        _, base = mr._radial(part, hpc[0] ** 2, sq)
-        dk = mr.COEF[part] * base[:, :, None] * hpc[1:] ** 2 * (xq[:, None, :] - z[None, :, :])     # [m, n, d]
+        sq = kr.sqdist(hpc, z, xq)
+        base = kr.radial(part, hpc, sq)[1]
+        dk = kr.COEF[part] * base[:, :, None] * hpc[1:] ** 2 * (xq[:, None, :] - z[None, :, :])     # [m, n, d]
         ou, ob = xr.contraction([part], torch.from_numpy(hpc), torch.from_numpy(xq), torch.from_numpy(z), torch.from_numpy(u),
                                 torch.from_numpy(b))
         np.testing.assert_allclose(ou.numpy(), np.einsum("i,pik->pk", u, dk), rtol=1e-12, atol=1e-14)

@@ -9,6 +9,7 @@ import pygpr_amd as pg
 from pygpr_amd._lib import PG_MAX_COMP
 
 import xgrad_ref as xr
+from kind_tools import rel
 
 pytestmark = pytest.mark.gpu
 
@@ -28,12 +29,7 @@ def compose(parts):
     return pg.Compose([CLS[p]() for p in parts])
 
 
-def rel(a, ref):
-    a, ref = a.detach().cpu().double(), ref.detach().cpu().double()
-    return float((a - ref).abs().max() / ref.abs().max().clamp_min(1e-300))
-
-
-def check(name, a, ref, tol):
+def check(name, a, ref, tol):      # (kind_tools.check with a name column of 48: the printed lines stay what they were)
     e = rel(a, ref)
     print("%-48s rel err %.2e (bound %.0e)" % (name, e, tol))
     assert e <= tol, (name, e)

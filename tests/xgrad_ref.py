@@ -1,7 +1,7 @@
 """Plain torch fp64 restatement of the predictive mean, diagonal variance and full covariance of an Exact_GP for the squared exponential,
 Matern-5/2 / -3/2 / -1/2 and white noise in any Compose, written with out-of-place operations only so that torch.autograd differentiates
 it in the test points: its gradients are the reference of the library's derivatives in x* (pg_kernel_xgrad, Exact_GP.predict_grad and
-the autograd backward of Exact_GP.predict).  Same parameter layout as tests/matern_ref.py: a model is a list of names ("se", "m52",
+the autograd backward of Exact_GP.predict).  Same parameter layout as tests/kernel_ref.py: a model is a list of names ("se", "m52",
 "m32", "m12", "wn"), hp their parameters concatenated, [sigma, l_1..l_d] per stationary child (l are inverse length scales).
 
 r = 0 (a test point on a training point, or on itself in K**): the radial distance goes through a double `where`, so that its
