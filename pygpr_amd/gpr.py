@@ -313,21 +313,41 @@ class Exact_GP(GPR):
                 "alpha": ops.empty(nb, n_pad, dtype=self.dtype),
                 "info": torch.zeros(nb, dtype=torch.int32, device=ops.device),
                 "hp": ops.empty(nb, self.params.shape[-1], dtype=torch.float64),
-                "minv": None, "work": None,
+                "minv": None, "u": None, "work": None,
             }
             for b, e in enumerate(experts):
                 e.chol, e.invd, e.alpha, e.info, e.hp = bat["chol"][b], bat["invd"][b], bat["alpha"][b], bat["info"][b: b + 1], bat["hp"][b]
             self._bat = bat
         self._bat["eager"] = self.eager_inverse or n_pad <= _BATCH_EAGER_N
-        if self._bat["eager"] and self._bat["minv"] is None:
-            ops = get_ops()
-            nb = len(experts)
-            self._bat["minv"] = ops.empty(nb, n_pad, n_pad, dtype=self.dtype)
-            self._bat["u"] = ops.empty(nb, n_pad, dtype=self.dtype)
-            self._bat["work"] = ops.empty(nb, (n_pad // 256) * n_pad, dtype=self.dtype)
-            for b, e in enumerate(experts):
-                e.minv = self._bat["minv"][b]
+        if self._bat["eager"]:
+            self._batch_inverse(weights=True)
         return self._bat
+
+    def _batch_inverse(self, weights=False):
+        """The stack of the experts' L^-1 in `_bat` and, with `weights`, the scratch of the eager weights (u, work): each is allocated
+        when IT is missing, whoever asked first -- a prediction of a lazy model forms the stack long before `eager_inverse` may be
+        switched on.  A new stack holds nothing yet: the experts' views of it are marked invalid."""
+        ops = get_ops()
+        bat, experts = self._bat, self._experts
+        nb, n_pad = len(experts), experts[0].n_pad
+        if bat["minv"] is None:
+            bat["minv"] = ops.empty(nb, n_pad, n_pad, dtype=self.dtype)
+            for b, e in enumerate(experts):
+                e.minv, e.minv_valid = bat["minv"][b], False
+        if weights and bat["u"] is None:
+            bat["u"] = ops.empty(nb, n_pad, dtype=self.dtype)
+            bat["work"] = ops.empty(nb, (n_pad // 256) * n_pad, dtype=self.dtype)
+        return bat["minv"]
+
+    def _expert_inverse(self, e, weights=False):
+        """The same for one expert outside a stack: e.minv and, with `weights`, e.work."""
+        ops = get_ops()
+        if e.minv is None:
+            e.minv = ops.empty(e.n_pad, e.n_pad, dtype=self.dtype)
+            e.minv_valid = False
+        if weights and e.work is None:
+            e.work = ops.empty((e.n_pad // 256 + 1) * e.n_pad, dtype=self.dtype)
+        return e.minv
 
     def _hp_rows(self):
         nhp = self.params.shape[-1]
@@ -367,9 +387,7 @@ class Exact_GP(GPR):
                         e.alpha = ops.empty(e.n_pad, dtype=self.dtype)
                         e.info = torch.zeros(1, dtype=torch.int32, device=ops.device)
                     if self.eager_inverse:
-                        if e.minv is None:
-                            e.minv = ops.empty(e.n_pad, e.n_pad, dtype=self.dtype)
-                            e.work = ops.empty((e.n_pad // 256 + 1) * e.n_pad, dtype=self.dtype)
+                        self._expert_inverse(e, weights=True)
                         ops.build_factor(spec, e.hp, e.x, e.chol, e.invd, e.info, e.minv)
                         u = e.work[: e.n_pad]
                         ops.trmv(e.minv, e.y, u, 0)
@@ -392,10 +410,7 @@ class Exact_GP(GPR):
 
     def _minv(self, e):
         if not e.minv_valid:
-            ops = get_ops()
-            if e.minv is None:
-                e.minv = ops.empty(e.n_pad, e.n_pad, dtype=self.dtype)
-            ops.trtri(e.chol, e.invd, e.minv)
+            get_ops().trtri(e.chol, e.invd, self._expert_inverse(e))
             e.minv_valid = True
         return e.minv
 
@@ -686,11 +701,8 @@ class Exact_GP(GPR):
         nb, n_pad = len(experts), experts[0].n_pad
         m = xpd.shape[-2]
         diag = want == "diag"
-        if diag and bat["minv"] is None:      # inverses not formed with the factor (lazy model): form them into one stack now
-            bat["minv"] = ops.empty(nb, n_pad, n_pad, dtype=self.dtype)
-            for b, e in enumerate(experts):
-                e.minv, e.minv_valid = bat["minv"][b], False
-        if diag:
+        if diag:                              # inverses not formed with the factor (lazy model): form them into one stack now
+            self._batch_inverse()
             for e in experts:
                 self._minv(e)
         # outputs: one fresh buffer per call, rows long enough for the padded last chunk -- the kernels write every chunk's means and

@@ -67,7 +67,9 @@ class _MemoLoss(Loss):
             return hit[1].copy(), (hit[2].copy() if hit[2] is not None else None)
         reuse = hit is not None and want_grad and self._factor_key == key
         loss, grad = self._evaluate_device(params, want_grad, key if self.memoize else None, reuse)
-        self._memo = (key, loss.copy(), grad.copy() if want_grad else None)
+        # (the key holds id()s: the memo keeps the tensors and the covariance they name alive, so that no later x / y / cov can come to
+        # lie at one of their addresses -- with the same version counter -- and be served this result)
+        self._memo = (key, loss.copy(), grad.copy() if want_grad else None, (m._x, m._y, m.cov))
         return loss, grad
 
     def loss(self, params: ndarray) -> float:
