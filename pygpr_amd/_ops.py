@@ -321,6 +321,29 @@ class HipOps:
         self._chk(m, q)
         self._call("pg_loo_fold", _code(m.dtype), int(n), _p(m), m.stride(0), _p(q), self._st())
 
+    # -- the inducing-point GP's contraction (include/pygpr_hip_sparse.h) --------------------------
+    def kernel_cross_grad_worksize(self, m, n, nhp):
+        return int(self.lib.pg_kernel_cross_grad_worksize(int(m), int(n), int(nhp)))
+
+    def kernel_cross_grad(self, spec, hp, z, x, w, grad, accumulate=False, work=None):
+        """grad[p] (+)= sum_ij w[i][j] dk(z_i, x_j)/dtheta_p for the parameters of the spec's stationary components
+        (pg_kernel_cross_grad): z [m, d], x [n, d], w a 2-D device tensor or view with at least [m, n] and unit stride along a row, grad
+        [nhp] float64; noise entries and entries outside the spec keep their bits.  One pg_covspec only.  work: kernel_cross_grad_worksize
+        doubles, allocated when None."""
+        (sp,) = _passes(spec)
+        self._chk(hp, z, x, grad, work)
+        m, d = z.shape
+        n = x.shape[0]
+        if not (w.is_cuda and w.dim() == 2 and w.stride(1) == 1 and w.shape[0] >= m and w.shape[1] >= n and w.dtype == z.dtype == x.dtype):
+            raise ValueError("kernel_cross_grad needs w [>= m, >= n] on the device in the points' dtype, unit stride along a row")
+        assert hp.dtype == torch.float64 and grad.dtype == torch.float64 and x.shape[1] == d
+        if work is None:
+            work = self.empty(max(1, self.kernel_cross_grad_worksize(m, n, grad.numel())), dtype=torch.float64)
+        assert work.dtype == torch.float64 and work.numel() >= self.kernel_cross_grad_worksize(m, n, grad.numel())
+        self._call("pg_kernel_cross_grad", _code(w.dtype), C.byref(sp), _p(hp), _p(z), z.stride(0), m, _p(x), x.stride(0), n, d, _p(w),
+                   w.stride(0), _p(grad), int(bool(accumulate)), _p(work), self._st())
+        return grad
+
     # -- normal variates (include/pygpr_hip_sample.h) -------------------------------------------
     def randn(self, out, rows, cols, seed, stream_id=0, row0=0):
         """out[r][q] = normal(seed, stream_id, row0 + r, q) for r < rows, q < cols, zero in the rest of out (pg_randn): out is a 2-D

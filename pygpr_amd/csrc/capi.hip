@@ -6,6 +6,7 @@
 #include "linalg.h"
 #include "pygpr_hip_loo.h"
 #include "pygpr_hip_sample.h"
+#include "sparse.h"
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -626,6 +627,23 @@ int pg_loo_fold(pg_handle h, int dtype, int n, void* M, long ldm, const void* q,
     NEED(n >= 1 && ldm >= n, "1 <= n <= ldm");
     return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
         return pg_loo_fold_t<T>(ST(stream), n, (T*)M, ldm, (const T*)q);
+    });
+}
+
+long pg_kernel_cross_grad_worksize(int m, int n, int nhp) { return (m >= 0 && n >= 0 && nhp >= 0) ? pg_cross_grad_worksize_impl(m, n, nhp) : -1; }
+
+int pg_kernel_cross_grad(pg_handle h, int dtype, const pg_covspec* spec, const double* hp, const void* Z, long ldz, int m, const void* X,
+                         long ldx, int n, int d, const void* W, long ldw, double* grad, int accumulate, void* work, void* stream) {
+    JOIN(h, stream);
+    NEED(h && hp && Z && X && W && grad && work, "null pointer");
+    if (check_spec(spec, __func__)) return -1;
+    if (!(m >= 0 && n >= 0 && d >= 1 && d <= PG_MAX_DIM)) { pg_set_error("%s: bad shape (0 <= m, n; 1 <= d <= PG_MAX_DIM)", __func__); return -2; }
+    if ((m + 63) / 64 > 65535) { pg_set_error("%s: m <= 64 * 65535", __func__); return -2; }
+    NEED(ldz >= d && ldx >= d && ldw >= n, "ldz, ldx >= d and ldw >= n");
+    for (int c = 0; c < (spec->ncomp & ~PG_SPEC_PRODUCT); ++c) NEED(spec->off[c] >= 0, "negative offset in the covariance spec");
+    return dispatch(dtype, __func__, [&](auto t) { using T = decltype(t);
+        return pg_cross_grad_t<T>(ST(stream), *spec, hp, (const T*)Z, ldz, m, (const T*)X, ldx, n, d, (const T*)W, ldw, grad, accumulate,
+                                  (double*)work);
     });
 }
 

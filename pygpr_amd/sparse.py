@@ -1,0 +1,345 @@
+"""Inducing-point GP regression: Titsias' collapsed variational bound ("VFE" / SGPR) on the MI355X.  New, not in the reference.
+
+With m inducing inputs z, Kuu = k(z, z) + JITTER I, Kuf = k(z, x), sigma^2 = sum sigma_n^2 over the White_noise children,
+Phi = Kuf Kuf^T, b = Kuf y, Sigma = Kuu + Phi / sigma^2, c = Sigma^-1 b and T = n kdiag - tr(Kuu^-1 Phi):
+
+    L     = sum log diag Ls - sum log diag Lu + n/2 log sigma^2 + y^T y / (2 sigma^2) - b^T c / (2 sigma^4) + n/2 log 2pi + T / (2 sigma^2)
+    mean* = Ksu c / sigma^2,      cov* = Kss - Ksu (Kuu^-1 - Sigma^-1) Kus      (Kss keeps the noise, as Exact_GP.predict keeps it)
+
+L is the NEGATIVE bound: `VFE(model)` follows MLE's protocol, so `CG(VFE(model))` trains the hyper-parameters.  O(n m^2) time and
+O(m^2 + m chunk) memory: the training points are streamed in chunks of `_SPARSE_CHUNK` columns and nothing of size n x anything
+outlives one chunk.
+
+How one evaluation runs.  Every chunk's Kuf_c is built into an AUGMENTED operand A_c = [Kuf_c; y_c^T; 0] (m_aug = pad(m + 1) rows), so
+that one deep-K product of the GEMM core per chunk, Phi_aug += A_c A_c^T (lower tiles), carries Phi, b (row m) and y^T y (entry
+[m, m]) together.  The m x m algebra runs on padded buffers with the identity in the padding: two factorisations, their inverses
+(trtri + lauum, mirrored), c = Sigma^-1 b by substitution against Ls (never through the explicit inverse: b^T c cancels against
+y^T y), and the product Kuu^-1 Phi_aug (trace: T; times Kuu^-1: the last term of G_uu).  The gradient is
+
+    dL = sum G_uu o dKuu + sum_c sum G_uf,c o dKuf_c + explicit terms in sigma_n and the prior variances,
+    G_uu   = 1/2 Sigma^-1 - 1/2 Kuu^-1 + c c^T / (2 sigma^4) + Kuu^-1 Phi Kuu^-1 / (2 sigma^2)
+    G_uf,c = (Sigma^-1 - Kuu^-1) Kuf_c / sigma^2 - c (y_c - Kuf_c^T c / sigma^2)^T / sigma^4 = [M | -c / sigma^4] A_c,
+             M = (Sigma^-1 - Kuu^-1) / sigma^2 + c c^T / sigma^6
+
+-- the rank-one correction rides in the same NN product as the matrix term, because A_c holds y_c -- and both contractions against
+dK/dtheta are pg_kernel_cross_grad (include/pygpr_hip_sparse.h), which rebuilds the derivative from the point tiles.  Gradients with
+respect to z, batched models, float32 and covariances longer than one pg_covspec are not served.
+"""
+import math
+from typing import Sequence
+
+import numpy as np
+import torch
+from numpy import ndarray
+from torch import Tensor
+
+from . import _lib
+from ._lib import CovSpec
+from ._ops import JITTER, get_ops, pad_to
+from .covar import Covar, spec_of, terms
+from .gpr import _CHUNK, GPR, _checked, _lin_alg_error
+from .loss import _MemoLoss
+
+_SPARSE_CHUNK = 32768   # training points per streamed chunk (columns of Kuf held at a time)
+
+
+def _pass1_variant(ma):
+    """The tiling of pass 1's lower-tile product at m_aug rows.  With fewer 128 x 128 lower tiles than the MI355X has compute units
+    (m_aug <= 2816) the launch is one partly filled round however deep K is; the 64 x 64 tiling has four times the tiles and gives the
+    same bits (an element's k order does not depend on the tile shape).  Measured at K = 32768: 3.44 against 4.66 ms at m_aug = 2304,
+    1.66 against 4.63 ms at 1280."""
+    t = ma // 128
+    return _lib.GEMM_NT_64 if t * (t + 1) // 2 <= 256 else _lib.GEMM_NT
+
+
+def _stationary(sp):
+    """The pass without its noise children: Kuu carries JITTER alone, and the contraction has no noise entries."""
+    out = CovSpec()
+    out.ncomp = sp.ncomp
+    for i in range(_lib.PG_MAX_COMP):
+        out.kind[i], out.off[i] = sp.kind[i], sp.off[i]
+    out.nnoise = 0
+    return out
+
+
+class Sparse_GP(GPR):
+    """Variational inducing-point GP: x [n, d], y [n], z [m, d] inducing inputs (fixed data, like x), all float64; params as Exact_GP's."""
+
+    def __init__(self, x: Tensor, y: Tensor, cov: Covar, z: Tensor) -> None:
+        super().__init__(x, y, cov)
+        self._z = z
+        self._check_data()
+        d = x.shape[-1]
+        _, noise, _ = terms(cov, d)
+        if not noise:
+            raise ValueError("Sparse_GP: the covariance needs a White_noise child (the bound divides by the noise variance)")
+        passes, _ = spec_of(cov, d)
+        if len(passes) != 1:
+            raise NotImplementedError("Sparse_GP: covariances that need more than one pg_covspec pass are not supported")
+        self.params: Tensor = cov.init_params(x)
+        self._dev = None
+        self._dev_key = None
+        self._state = None
+        self._bufs = {}
+        self._z_version = 0
+        self.need_upd = True
+
+    # ---- data -------------------------------------------------------------------------------
+    @property
+    def z(self) -> Tensor:
+        return self._z
+
+    @z.setter
+    def z(self, value: Tensor) -> None:
+        self._z = value
+        self._z_version += 1
+        self._data_changed()
+
+    @property
+    def dtype(self):
+        return torch.float64
+
+    def _data_changed(self) -> None:
+        self._dev = None
+        self._state = None
+        self.need_upd = True
+
+    def _check_data(self) -> None:
+        x, y, z = self._x, self._y, self._z
+        for name, t in (("x", x), ("y", y), ("z", z)):
+            if t.dtype != torch.float64:
+                raise TypeError("Sparse_GP computes in float64 only (the sigma^-4 terms of the bound leave no digits in single "
+                                "precision); %s is %s" % (name, t.dtype))
+        if x.dim() != 2 or y.dim() != 1:
+            raise NotImplementedError("Sparse_GP: batched models are not supported (x [n, d], y [n])")
+        if z.dim() != 2 or z.shape[1] != x.shape[1] or z.shape[0] < 1:
+            raise ValueError("Sparse_GP: z must be [m, %d] with m >= 1, got %s" % (x.shape[1], tuple(z.shape)))
+        if y.shape[0] != x.shape[0]:
+            raise ValueError("Sparse_GP: x holds %d points, y %d values" % (x.shape[0], y.shape[0]))
+
+    def _device_data(self):
+        """(x, y, z) on the device, uploaded once per (tensor identity, version)."""
+        key = tuple(v for t in (self._x, self._y, self._z) for v in (id(t), t._version))
+        if self._dev is None or self._dev_key != key:
+            self._check_data()
+            ops = get_ops()
+            self._dev = tuple(ops.to_device(t, torch.float64) for t in (self._x, self._y, self._z))
+            self._dev_key = key
+            self._state = None
+            self.need_upd = True
+        return self._dev
+
+    def _hp_host(self, params=None) -> ndarray:
+        p = self.params if params is None else params
+        p = p.detach().cpu().numpy() if isinstance(p, Tensor) else np.asarray(p)
+        _, nhp = spec_of(self.cov, self._x.shape[-1])
+        assert p.shape[-1] == nhp
+        if p.reshape(-1, nhp).shape[0] != 1:
+            raise NotImplementedError("Sparse_GP: batched hyper-parameters are not supported")
+        return np.array(p.reshape(nhp), dtype=np.float64)
+
+    def _prior(self, hp):
+        """(sigma^2, kdiag, the offsets): the noise variance, the constant prior variance of the stationary part (what
+        Exact_GP._kss_diag forms, without its noise) and (terms, noise offsets)."""
+        tms, noise, _ = terms(self.cov, self._x.shape[-1])
+        sig2 = float(sum(hp[o] ** 2 for o in noise))
+        kdiag = float(sum(np.prod([hp[o] ** 2 for o in offs]) for _, _, offs in tms))
+        return sig2, kdiag, tms, noise
+
+    def _buf(self, name, *shape, zero=False):
+        """Device scratch kept per name and shape (a ragged last chunk has buffers of its own): one evaluation after the other runs on
+        the stream, so one set serves them all."""
+        t = self._bufs.get((name, shape))
+        if t is None:
+            t = self._bufs[(name, shape)] = get_ops().empty(*shape, dtype=torch.float64)
+        if zero:
+            t.zero_()
+        return t
+
+    # ---- the bound --------------------------------------------------------------------------
+    def _build_chunk(self, ops, spec, hpd, zd, xd, yd, s, nc, m, ma):
+        """A_c = [k(z, x_c); y_c^T; 0] as [m_aug, pad(nc)] (the cross build zeroes the padding)."""
+        a = self._buf("chunk", ma, pad_to(nc))
+        ops.kernel_build(spec, hpd, zd, xd[s: s + nc], a)
+        a[m, :nc] = yd[s: s + nc]
+        return a
+
+    def _evaluate(self, hp: ndarray, want_grad: bool, keep: bool):
+        """One evaluation of the bound at the host vector hp: (loss, grad | None); keep: leave the prediction state behind.  Everything
+        is enqueued before the ONE synchronisation that reads the status words and the scalars."""
+        ops = get_ops()
+        xd, yd, zd = self._device_data()
+        n, d = xd.shape
+        m = zd.shape[0]
+        ma = pad_to(m + 1)
+        (sp,), nhp = spec_of(self.cov, d)
+        spec = _stationary(sp)
+        sig2, kdiag, tms, noise = self._prior(hp)
+        hpd = ops.to_device(torch.from_numpy(hp), torch.float64)
+        ch = int(_SPARSE_CHUNK)
+        chunks = [(s, min(ch, n - s)) for s in range(0, n, ch)]
+        info = torch.zeros(2, dtype=torch.int32, device=ops.device)
+        res = [None]
+        keepers = {}
+
+        def enqueue():
+            # pass 1: Phi_aug = sum_c A_c A_c^T (lower tiles; mirrored once at the end)
+            phi = self._buf("phi", ma, ma, zero=True)
+            a = None
+            for s, nc in chunks:
+                a = self._build_chunk(ops, spec, hpd, zd, xd, yd, s, nc, m, ma)
+                ops.gemm_raw(_pass1_variant(ma), ma, ma, a.shape[1], 1.0, a, a, 1.0, phi, tri=1)
+            ops.symmetrize(phi, ma)
+            phm, b, yy = phi[:m, :m], phi[:m, m], phi[m, m]
+            # the m x m algebra: Lu, Ls, the two inverses
+            lu = self._buf("lu", ma, ma)
+            ops.kernel_build(spec, hpd, zd, None, lu, jitter=JITTER)       # Kuu + JITTER I, identity in the padding
+            ls = self._buf("ls", ma, ma)
+            ls.copy_(lu)
+            ls[:m, :m].add_(phm, alpha=1.0 / sig2)                          # Sigma
+            invd = self._buf("invd", 2, ops.potrf_worksize(ma, torch.float64))
+            minv = self._buf("minv", ma, ma)
+            kuui, sgi = (self._buf("kuui", ma, ma), self._buf("sgi", ma, ma)) if not keep else (ops.empty(ma, ma), ops.empty(ma, ma))
+            for i, (fac, inv) in enumerate(((lu, kuui), (ls, sgi))):
+                ops.potrf(fac, invd[i], info[i: i + 1])
+                ops.trtri(fac, invd[i], minv)
+                ops.lauum(minv, inv)
+                ops.symmetrize(inv, ma)
+            ldu = lu.diagonal()[:m].log().sum()
+            lds = ls.diagonal()[:m].log().sum()
+            # c = Sigma^-1 b by substitution against Ls: cond(Sigma) is cond(Kuu) times n / sigma^2, and b^T c cancels against y^T y in the
+            # loss -- c from the explicit inverse costs the loss three digits (measured: 5e-10 against 3e-13 at cond(Sigma) = 1e7)
+            bvec = self._buf("bvec", ma, zero=True)
+            bvec[:m] = b
+            cvec = self._buf("cvec", ma)
+            ops.potrs_vec(ls, invd[1], bvec, cvec)
+            c = cvec[:m].clone()
+            kp = self._buf("kphi", ma, ma)
+            ops.gemm_raw(_lib.GEMM_NN, ma, ma, ma, 1.0, kuui, phi, 0.0, kp)      # Kuu^-1 Phi_aug
+            tr_sp = (sgi[:m, :m] * phm).sum() if want_grad else ldu.new_zeros(())      # tr(Sigma^-1 Phi): both symmetric
+            scal = [ldu, lds, yy, (b * c).sum(), tr_sp, kp[:m, :m].diagonal().sum(), (c * (phm * c).sum(1)).sum()]
+            grad = ops.zeros(nhp, dtype=torch.float64)
+            if want_grad:
+                g = self._buf("guu", ma, ma)
+                ops.gemm_raw(_lib.GEMM_NN, ma, ma, ma, 1.0, kp, kuui, 0.0, g)     # Kuu^-1 Phi Kuu^-1 in [:m, :m]
+                cc = torch.outer(c, c)
+                gm = g[:m, :m]
+                gm.mul_(0.5 / sig2).add_(sgi[:m, :m], alpha=0.5).sub_(kuui[:m, :m], alpha=0.5).add_(cc, alpha=0.5 / sig2 ** 2)
+                work = self._buf("gwork", max(1, ops.kernel_cross_grad_worksize(m, max(m, min(ch, n)), nhp)))
+                ops.kernel_cross_grad(spec, hpd, zd, zd, g, grad, accumulate=False, work=work)
+                mw = self._buf("mw", ma, ma, zero=True)                           # [M | -c / sigma^4 | 0], zero rows below m
+                mw[:m, :m].add_(sgi[:m, :m], alpha=1.0 / sig2).sub_(kuui[:m, :m], alpha=1.0 / sig2).add_(cc, alpha=1.0 / sig2 ** 3)
+                mw[:m, m] = c * (-1.0 / sig2 ** 2)
+                for s, nc in chunks:       # pass 2: rebuild A_c (one chunk: it is still there), W_c = [M | -c / sigma^4] A_c, contract
+                    if len(chunks) > 1:
+                        a = self._build_chunk(ops, spec, hpd, zd, xd, yd, s, nc, m, ma)
+                    w = self._buf("w", ma, a.shape[1])
+                    ops.gemm_raw(_lib.GEMM_NN, ma, a.shape[1], ma, 1.0, mw, a, 0.0, w)
+                    ops.kernel_cross_grad(spec, hpd, zd, xd[s: s + nc], w, grad, accumulate=True, work=work)
+            if keep:
+                keepers.update(c=c, kuui=kuui, sgi=sgi, hpd=hpd)
+            res[0] = torch.cat([torch.stack(scal), grad]).cpu().numpy()          # the one sync + transfer
+
+        for st in _checked(enqueue, lambda: info.tolist()):
+            if st:
+                raise _lin_alg_error(st, " -- Kuu or Sigma of the inducing points")
+        ldu, lds, yy, bc, tr_sp, tr_kp, cpc = res[0][:7]
+        t = n * kdiag - tr_kp
+        loss = lds - ldu + 0.5 * n * math.log(sig2) + yy / (2 * sig2) - bc / (2 * sig2 ** 2) + 0.5 * n * math.log(2 * math.pi) + t / (2 * sig2)
+        grad = None
+        if want_grad:
+            grad = res[0][7:].copy()
+            dsig2 = (-tr_sp / (2 * sig2 ** 2) + n / (2 * sig2) - yy / (2 * sig2 ** 2) + bc / sig2 ** 3 - cpc / (2 * sig2 ** 4)
+                     - t / (2 * sig2 ** 2))
+            for o in noise:
+                grad[o] = 2.0 * hp[o] * dsig2
+            for _, _, offs in tms:          # the trace of Kff: n / (2 sigma^2) dkdiag/dsigma_c (a product term: 2 term / sigma_c)
+                for o in offs:
+                    others = np.prod([hp[o2] ** 2 for o2 in offs if o2 != o])
+                    grad[o] += n / (2 * sig2) * 2.0 * hp[o] * others
+        if keep:
+            self._state = dict(keepers, m=m, ma=ma, sig2=sig2, kss=kdiag + sig2, spec=spec, full_spec=sp)
+        return np.array(loss), grad
+
+    def update(self) -> None:
+        self._device_data()                  # first: an in-place edit of x / y / z (version bump) marks the model dirty here
+        if self.need_upd:
+            self._state = None
+            self._evaluate(self._hp_host(), want_grad=False, keep=True)
+            ops = get_ops()
+            st = self._state
+            m, ma = st["m"], st["ma"]
+            bm = ops.zeros(ma, ma, dtype=torch.float64)       # [Kuu^-1 - Sigma^-1 | c / sigma^2 | 0]: variance and mean from one product
+            bm[:m, :m].add_(st["kuui"][:m, :m]).sub_(st["sgi"][:m, :m])
+            bm[:m, m] = st["c"] / st["sig2"]
+            st["bm"] = bm
+            self.need_upd = False
+        return None
+
+    # ---- prediction -------------------------------------------------------------------------
+    def predict(self, xp: Tensor, var: str = "full") -> Sequence[Tensor]:
+        """[mean, var | covariance | NotImplemented] of y* at xp [q, d]: mean = Ksu c / sigma^2, cov = Kss - Ksu (Kuu^-1 - Sigma^-1) Kus
+        with the noise on the diagonal of Kss.  var="diag" chunks the test points; var="full" takes them in one piece."""
+        if torch.is_grad_enabled() and isinstance(xp, Tensor) and xp.requires_grad:
+            raise NotImplementedError("Sparse_GP.predict is not differentiable in the test points; use Exact_GP")
+        if xp.dim() != 2 or xp.shape[1] != self._x.shape[1]:
+            raise NotImplementedError("Sparse_GP.predict: xp must be [q, %d] (no batches)" % self._x.shape[1])
+        ops = get_ops()
+        self.update()
+        st = self._state
+        m, ma, bm, spec, hpd = st["m"], st["ma"], st["bm"], st["spec"], st["hpd"]
+        _, _, zd = self._device_data()
+        xpd = ops.to_device(xp, torch.float64)
+        q = xpd.shape[0]
+        want = var if var in ("full", "diag") else "none"
+        mean = ops.empty(q, dtype=torch.float64)
+        if want == "full":
+            qp = pad_to(q)
+            kt = ops.empty(qp, ma, dtype=torch.float64)
+            v = ops.empty(qp, ma, dtype=torch.float64)
+            cov = ops.empty(qp, qp, dtype=torch.float64)
+            ops.kernel_build(spec, hpd, xpd, zd, kt)                                   # Ksu, test-point-major; zero in column m and beyond
+            ops.gemm_raw(_lib.GEMM_NN, qp, ma, ma, 1.0, kt, bm, 0.0, v)                # [Ksu (Kuu^-1 - Sigma^-1) | mean | 0]
+            mean.copy_(v[:q, m])
+            ops.kernel_build(st["full_spec"], hpd, xpd, None, cov)                     # Kss incl. sigma_n^2, identity in the padding
+            ops.gemm_raw(_lib.GEMM_NT, qp, qp, ma, -1.0, v, kt, 1.0, cov, tri=1)       # (column m of kt is zero: the mean does not enter)
+            ops.symmetrize(cov, qp)                                                    # the upper triangle is the mirror: exactly symmetric
+            return [mean.to(xp.device), cov[:q, :q].contiguous().to(xp.device)]
+        vr = ops.empty(q, dtype=torch.float64) if want == "diag" else None
+        for s in range(0, q, _CHUNK):
+            xq = xpd[s: s + _CHUNK]
+            qc = xq.shape[0]
+            qp = pad_to(qc)
+            kt = self._buf("pkt", qp, ma)
+            v = self._buf("pv", qp, ma)
+            ops.kernel_build(spec, hpd, xq, zd, kt)
+            ops.gemm_raw(_lib.GEMM_NN, qp, ma, ma, 1.0, kt, bm, 0.0, v)
+            mean[s: s + qc] = v[:qc, m]
+            if want == "diag":
+                vr[s: s + qc] = st["kss"] - (v[:qc, :m] * kt[:qc, :m]).sum(1)
+        if want == "diag":
+            return [mean.to(xp.device), vr.to(xp.device)]
+        return [mean.to(xp.device), NotImplemented]
+
+
+class VFE(_MemoLoss):
+    """The negative collapsed variational bound of a Sparse_GP as a training objective with MLE's protocol (`CG(VFE(model))`)."""
+
+    def __init__(self, model: Sparse_GP) -> None:
+        if not isinstance(model, Sparse_GP):
+            raise TypeError("VFE is the loss of a Sparse_GP, got %s" % type(model).__name__)
+        super().__init__(model)
+        self._z_seen = None
+
+    def _evaluate(self, params: ndarray, want_grad: bool):
+        m = self.model
+        token = (id(m._z), m._z._version, m._z_version)      # the memo's key holds x, y and the covariance: z is this model's own
+        if token != self._z_seen:
+            self._memo = None
+            self._z_seen = token
+        return super()._evaluate(params, want_grad)
+
+    def _evaluate_device(self, params: ndarray, want_grad: bool, key=None, reuse_factor=False):
+        m = self.model
+        loss, grad = m._evaluate(m._hp_host(np.asarray(params, dtype=np.float64)), want_grad, keep=False)
+        return loss, grad

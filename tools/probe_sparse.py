@@ -1,0 +1,99 @@
+"""Sparse_GP timings on the GPU: one VFE.loss_and_grad and one predict of 8192 points at n = 262144, m = 2048, d = 8 (fp64), and where
+the evaluation's time goes -- the covariance build of a chunk, the two streaming products of the GEMM core (pass 1: Phi_aug += A A^T on
+the lower tiles, K = the chunk; pass 2: W = [M | -c / sigma^4] A), the rectangular contraction pg_kernel_cross_grad, and the rest (the
+m x m algebra, the Kuu contraction, transfers), taken as the difference.  Each piece is timed alone on one full chunk and multiplied
+by the number of chunks.  Median of `--reps` after two warm-up runs, events on the caller stream.  One JSON line.
+
+    python tools/probe_sparse.py [--n 262144] [--m 2048] [--d 8] [--q 8192] [--reps 5]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import pygpr_amd as pg  # noqa: E402
+from pygpr_amd import _lib  # noqa: E402
+from pygpr_amd import sparse as sp  # noqa: E402
+from pygpr_amd._ops import pad_to  # noqa: E402
+
+
+def timed(fn, reps, warm=2):
+    for _ in range(warm):
+        fn()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return float(np.median(ms))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=262144)
+    ap.add_argument("--m", type=int, default=2048)
+    ap.add_argument("--d", type=int, default=8)
+    ap.add_argument("--q", type=int, default=8192)
+    ap.add_argument("--reps", type=int, default=5)
+    args = ap.parse_args()
+    n, m, d = args.n, args.m, args.d
+    rng = np.random.default_rng(1)
+    x = rng.random((n, d))
+    y = np.sin(x.sum(1)) + 0.1 * rng.standard_normal(n)
+    z = x[rng.choice(n, m, replace=False)]
+    hp = np.concatenate([[1.1], np.full(d, 0.9), [0.3]])
+    gp = pg.Sparse_GP(torch.from_numpy(x), torch.from_numpy(y), pg.Compose([pg.Squared_exponential(), pg.White_noise()]), torch.from_numpy(z))
+    gp.set_params(torch.from_numpy(hp))
+    vfe = pg.VFE(gp)
+    vfe.memoize = False
+    t_eval = timed(lambda: vfe.loss_and_grad(hp), args.reps)
+    t_loss = timed(lambda: vfe.loss(hp), args.reps)
+    xp = torch.from_numpy(rng.random((args.q, d)))
+    gp.update()
+    t_pred = timed(lambda: gp.predict(xp, var="diag"), args.reps)
+
+    # the pieces, on one full chunk
+    ops = pg._ops.get_ops()
+    xd, yd, zd = gp._device_data()
+    ch = min(sp._SPARSE_CHUNK, n)
+    nch = -(-n // sp._SPARSE_CHUNK)
+    ma, cp = pad_to(m + 1), pad_to(ch)
+    (full,), nhp = pg.covar.spec_of(gp.cov, d)
+    spec = sp._stationary(full)
+    hpd = ops.to_device(torch.from_numpy(hp), torch.float64)
+    a = ops.empty(ma, cp, dtype=torch.float64)
+    phi = ops.zeros(ma, ma, dtype=torch.float64)
+    mw = ops.zeros(ma, ma, dtype=torch.float64)
+    w = ops.empty(ma, cp, dtype=torch.float64)
+    grad = ops.zeros(nhp, dtype=torch.float64)
+    work = ops.empty(ops.kernel_cross_grad_worksize(m, ch, nhp), dtype=torch.float64)
+    t_build = timed(lambda: ops.kernel_build(spec, hpd, zd, xd[:ch], a), args.reps)
+    t_nt = timed(lambda: ops.gemm_raw(sp._pass1_variant(ma), ma, ma, cp, 1.0, a, a, 1.0, phi, tri=1), args.reps)
+    t_nt128 = timed(lambda: ops.gemm_raw(_lib.GEMM_NT, ma, ma, cp, 1.0, a, a, 1.0, phi, tri=1), args.reps)
+    t_nn = timed(lambda: ops.gemm_raw(_lib.GEMM_NN, ma, cp, ma, 1.0, mw, a, 0.0, w), args.reps)
+    t_cg = timed(lambda: ops.kernel_cross_grad(spec, hpd, zd, xd[:ch], w, grad, accumulate=True, work=work), args.reps)
+    pieces = nch * (2 * t_build + t_nt + t_nn + t_cg)
+    print(json.dumps({
+        "n": n, "m": m, "d": d, "dtype": "fp64", "chunk": sp._SPARSE_CHUNK, "chunks": nch, "reps": args.reps,
+        "loss_and_grad_ms": round(t_eval, 2), "loss_ms": round(t_loss, 2), "predict_diag_q%d_ms" % args.q: round(t_pred, 2),
+        "per_chunk_build_ms": round(t_build, 3), "per_chunk_pass1_nt_ms": round(t_nt, 3), "per_chunk_pass2_nn_ms": round(t_nn, 3),
+        "per_chunk_cross_grad_ms": round(t_cg, 3),
+        "pass1_tiling": 64 if sp._pass1_variant(ma) == _lib.GEMM_NT_64 else 128, "per_chunk_pass1_nt_128_tiles_ms": round(t_nt128, 3),
+        "pass1_nt_tflops": round(ma * (ma + 1.0) * cp / (t_nt * 1e-3) / 1e12, 2),       # the lower triangle: ma (ma + 1) / 2 outputs, 2 flop each
+        "pass2_nn_tflops": round(2.0 * ma * ma * cp / (t_nn * 1e-3) / 1e12, 2),
+        "cross_grad_gpairs_per_s": round(m * ch / (t_cg * 1e-3) / 1e9, 2),
+        "cross_grad_w_gbs": round(8.0 * m * ch / (t_cg * 1e-3) / 1e9, 1),
+        "streamed_ms": round(pieces, 2), "rest_ms": round(t_eval - pieces, 2),
+    }), flush=True)
+
+
+if __name__ == "__main__":
+    main()
