@@ -344,6 +344,40 @@ class HipOps:
                    w.stride(0), _p(grad), int(bool(accumulate)), _p(work), self._st())
         return grad
 
+    # -- greedy inducing-point selection (include/pygpr_hip_select.h) ----------------------------
+    def greedy_select_worksize(self, n, m_max):
+        return int(self.lib.pg_greedy_select_worksize(int(n), int(m_max)))
+
+    def greedy_select(self, spec, hp, x, m_max, floor, work=None, out=None):
+        """Up to m_max pivots of x [n, d] (float64) by largest residual prior variance under the spec's stationary components
+        (pg_greedy_select; the spec's noise entries are ignored).  Returns device tensors (piv [m_max] int32, count [1] int32, trace
+        [m_max], resid [n]); piv and trace hold their results in [0, count) and are not touched behind it.  Asynchronous: read count
+        after a sync.  One pg_covspec only.  work: greedy_select_worksize doubles (8 n m_max bytes and a little), allocated when None;
+        out: the four outputs as contiguous device tensors of at least those lengths, allocated when None."""
+        (sp,) = _passes(spec)
+        self._chk(hp, work)
+        if not (x.is_cuda and x.dim() == 2 and x.stride(1) == 1 and x.dtype == torch.float64):
+            raise ValueError("greedy_select needs x [n, d] float64 on the device, unit stride along a row")
+        assert hp.dtype == torch.float64
+        n, d = x.shape
+        m_max = int(m_max)
+        size = self.greedy_select_worksize(n, m_max)
+        if size < 0:
+            raise ValueError("greedy_select: 0 <= m_max <= n, got m_max = %d, n = %d" % (m_max, n))
+        if work is None:
+            work = self.empty(size, dtype=torch.float64)
+        assert work.dtype == torch.float64 and work.numel() >= size
+        if out is None:
+            out = (torch.empty(max(m_max, 1), dtype=torch.int32, device=self.device), torch.empty(1, dtype=torch.int32, device=self.device),
+                   self.empty(max(m_max, 1), dtype=torch.float64), self.empty(max(n, 1), dtype=torch.float64))
+        piv, count, trace, resid = out
+        self._chk(piv, count, trace, resid)
+        assert piv.dtype == count.dtype == torch.int32 and trace.dtype == resid.dtype == torch.float64
+        assert piv.numel() >= m_max and count.numel() >= 1 and trace.numel() >= m_max and resid.numel() >= n
+        self._call("pg_greedy_select", PG_F64, C.byref(sp), _p(hp), _p(x), x.stride(0), n, d, m_max, float(floor), _p(piv), _p(count),
+                   _p(trace), _p(resid), _p(work), self._st())
+        return piv[:m_max], count, trace[:m_max], resid[:n]
+
     # -- normal variates (include/pygpr_hip_sample.h) -------------------------------------------
     def randn(self, out, rows, cols, seed, stream_id=0, row0=0):
         """out[r][q] = normal(seed, stream_id, row0 + r, q) for r < rows, q < cols, zero in the rest of out (pg_randn): out is a 2-D

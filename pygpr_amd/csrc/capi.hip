@@ -7,6 +7,7 @@
 #include "pygpr_hip_loo.h"
 #include "pygpr_hip_sample.h"
 #include "sparse.h"
+#include "select.h"
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -645,6 +646,25 @@ int pg_kernel_cross_grad(pg_handle h, int dtype, const pg_covspec* spec, const d
         return pg_cross_grad_t<T>(ST(stream), *spec, hp, (const T*)Z, ldz, m, (const T*)X, ldx, n, d, (const T*)W, ldw, grad, accumulate,
                                   (double*)work);
     });
+}
+
+long pg_greedy_select_worksize(int n, int m_max) { return (n >= 0 && m_max >= 0 && m_max <= n) ? pg_greedy_select_worksize_impl(n, m_max) : -1; }
+
+int pg_greedy_select(pg_handle h, int dtype, const pg_covspec* spec, const double* hp, const void* X, long ldx, int n, int d, int m_max,
+                     double floor, int* piv, int* count, double* trace, double* resid, void* work, void* stream) {
+    JOIN(h, stream);
+    NEED(h && hp && count, "null pointer");
+    NEED(dtype == PG_F64, "float64 only (dtype must be PG_F64)");
+    if (check_spec(spec, __func__)) return -1;
+    NEED((spec->ncomp & ~PG_SPEC_PRODUCT) >= 1, "the spec has no stationary component");
+    for (int c = 0; c < (spec->ncomp & ~PG_SPEC_PRODUCT); ++c) NEED(spec->off[c] >= 0, "negative offset in the covariance spec");
+    if (!(n >= 0 && d >= 1 && d <= PG_MAX_DIM && m_max >= 0 && m_max <= n)) {
+        pg_set_error("%s: bad shape (0 <= m_max <= n; 1 <= d <= PG_MAX_DIM)", __func__);
+        return -2;
+    }
+    NEED(ldx >= d, "ldx >= d");
+    NEED(m_max == 0 || (X && piv && trace && resid && work), "null pointer");
+    return pg_greedy_select_impl(ST(stream), *spec, hp, (const double*)X, ldx, n, d, m_max, floor, piv, count, trace, resid, (double*)work);
 }
 
 int pg_randn(pg_handle h, int dtype, long seed, int stream_id, int row0, int rows, int cols, void* Z, long ldz, int rows_pad, int cols_pad,

@@ -24,9 +24,12 @@ y^T y), and the product Kuu^-1 Phi_aug (trace: T; times Kuu^-1: the last term of
 -- the rank-one correction rides in the same NN product as the matrix term, because A_c holds y_c -- and both contractions against
 dK/dtheta are pg_kernel_cross_grad (include/pygpr_hip_sparse.h), which rebuilds the derivative from the point tiles.  Gradients with
 respect to z, batched models, float32 and covariances longer than one pg_covspec are not served.
+
+z is data.  `select_inducing` / `Sparse_GP.greedy` choose it among the training points: greedy conditional-variance selection, the
+partial pivoted Cholesky factorisation of k(x, x) on the device (include/pygpr_hip_select.h; 8 n m bytes of workspace for the factor).
 """
 import math
-from typing import Sequence
+from typing import NamedTuple, Sequence
 
 import numpy as np
 import torch
@@ -62,8 +65,64 @@ def _stationary(sp):
     return out
 
 
+def _prior_of(cov, d, hp):
+    """(sigma^2, kdiag, the terms, the noise offsets) of a covariance at the host vector hp: see Sparse_GP._prior."""
+    tms, noise, _ = terms(cov, d)
+    sig2 = float(sum(hp[o] ** 2 for o in noise))
+    kdiag = float(sum(np.prod([hp[o] ** 2 for o in offs]) for _, _, offs in tms))
+    return sig2, kdiag, tms, noise
+
+
+class Selection(NamedTuple):
+    """What select_inducing returns, on the device of the points it was given: `index` [count] int64, the chosen training points in
+    selection order; `trace` [count], the trace term of the collapsed bound (n kdiag - tr(Kuu^-1 Kuf Kfu), without jitter) after
+    each choice -- the curve to pick m from; `residual` [n], the prior variance the chosen set leaves unexplained at every point."""
+    index: Tensor
+    trace: Tensor
+    residual: Tensor
+
+
+def select_inducing(x: Tensor, cov: Covar, params, m: int, tol: float = 0.0) -> Selection:
+    """Greedy conditional-variance selection of up to m inducing points among the rows of x [n, d] (float64) at the hyper-parameters
+    `params`: repeatedly the point whose prior variance the points chosen so far explain least -- the partial pivoted Cholesky
+    factorisation of k(x, x) (pg_greedy_select, include/pygpr_hip_select.h).  The stationary part of `cov` alone decides; a
+    White_noise child is neither required nor used.  Selection stops early once the largest residual variance is no longer above
+    max(tol * kdiag, JITTER): a point whose conditional variance is below the jitter Sparse_GP adds to Kuu cannot improve the bound.
+    Needs 8 n m bytes of device workspace (the factor), unlike the model's O(m^2 + m chunk)."""
+    if not isinstance(x, Tensor) or x.dtype != torch.float64:
+        raise TypeError("select_inducing computes in float64 only; x is %s" % getattr(x, "dtype", type(x).__name__))
+    if x.dim() != 2:
+        raise NotImplementedError("select_inducing: batched points are not supported (x [n, d])")
+    n, d = x.shape
+    tms, _, _ = terms(cov, d)
+    if not tms:
+        raise ValueError("select_inducing: the covariance has no stationary term to select by")
+    passes, nhp = spec_of(cov, d)
+    if len(passes) != 1:
+        raise NotImplementedError("select_inducing: covariances that need more than one pg_covspec pass are not supported")
+    p = params.detach().cpu().numpy() if isinstance(params, Tensor) else np.asarray(params)
+    if p.dtype != np.float64:
+        raise TypeError("select_inducing computes in float64 only; params is %s" % p.dtype)
+    if p.shape[-1] != nhp:
+        raise ValueError("select_inducing: the covariance takes %d hyper-parameters, got %d" % (nhp, p.shape[-1]))
+    if p.reshape(-1, nhp).shape[0] != 1:
+        raise NotImplementedError("select_inducing: batched hyper-parameters are not supported")
+    hp = np.array(p.reshape(nhp), dtype=np.float64)
+    if not (isinstance(m, (int, np.integer)) and 1 <= m <= n):
+        raise ValueError("select_inducing: m must be an integer in [1, %d], got %r" % (n, m))
+    _, kdiag, _, _ = _prior_of(cov, d, hp)
+    floor = max(float(tol) * kdiag, JITTER)
+    ops = get_ops()
+    xd = ops.to_device(x, torch.float64)
+    hpd = ops.to_device(torch.from_numpy(hp), torch.float64)
+    piv, count, trace, resid = ops.greedy_select(_stationary(passes[0]), hpd, xd, int(m), floor)
+    c = int(count.cpu()[0])                                        # the one synchronisation
+    return Selection(piv[:c].to(device=x.device, dtype=torch.int64), trace[:c].to(x.device), resid.to(x.device))
+
+
 class Sparse_GP(GPR):
-    """Variational inducing-point GP: x [n, d], y [n], z [m, d] inducing inputs (fixed data, like x), all float64; params as Exact_GP's."""
+    """Variational inducing-point GP: x [n, d], y [n], z [m, d] inducing inputs (fixed data, like x), all float64; params as Exact_GP's.
+    `Sparse_GP.greedy(x, y, cov, m)` chooses z among the training points; `select_inducing` chooses it again at the current params."""
 
     def __init__(self, x: Tensor, y: Tensor, cov: Covar, z: Tensor) -> None:
         super().__init__(x, y, cov)
@@ -83,6 +142,24 @@ class Sparse_GP(GPR):
         self._bufs = {}
         self._z_version = 0
         self.need_upd = True
+
+    # ---- inducing inputs from the training points -------------------------------------------
+    @classmethod
+    def greedy(cls, x: Tensor, y: Tensor, cov: Covar, m: int, params=None, tol: float = 0.0) -> "Sparse_GP":
+        """A model whose m (or fewer: `tol`) inducing inputs are chosen among x by `select_inducing` at `params`, which the model
+        then holds, or at cov.init_params(x)."""
+        res = select_inducing(x, cov, cov.init_params(x) if params is None else params, m, tol)
+        model = cls(x, y, cov, x[res.index])
+        if params is not None:
+            model.set_params(params if isinstance(params, Tensor) else torch.as_tensor(np.asarray(params)))
+        return model
+
+    def select_inducing(self, m: int = None, tol: float = 0.0) -> Selection:
+        """Choose the inducing inputs again among the training points at the current params (m: as many as now) and assign them: the
+        model turns dirty and a VFE on it drops its memo.  Returns the Selection."""
+        res = select_inducing(self._x, self.cov, self._hp_host(), self._z.shape[0] if m is None else m, tol)
+        self.z = self._x[res.index]
+        return res
 
     # ---- data -------------------------------------------------------------------------------
     @property
@@ -141,10 +218,7 @@ class Sparse_GP(GPR):
     def _prior(self, hp):
         """(sigma^2, kdiag, the offsets): the noise variance, the constant prior variance of the stationary part (what
         Exact_GP._kss_diag forms, without its noise) and (terms, noise offsets)."""
-        tms, noise, _ = terms(self.cov, self._x.shape[-1])
-        sig2 = float(sum(hp[o] ** 2 for o in noise))
-        kdiag = float(sum(np.prod([hp[o] ** 2 for o in offs]) for _, _, offs in tms))
-        return sig2, kdiag, tms, noise
+        return _prior_of(self.cov, self._x.shape[-1], hp)
 
     def _buf(self, name, *shape, zero=False):
         """Device scratch kept per name and shape (a ragged last chunk has buffers of its own): one evaluation after the other runs on
