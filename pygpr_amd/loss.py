@@ -40,6 +40,16 @@ class Loss():
     def loss_and_grad(self, params: ndarray) -> Tuple[float, ndarray]:
         raise NotImplementedError
 
+    # What an optimiser reads and writes around a run.  A loss whose parameter vector holds more than the model's hyper-parameters
+    # (VFE(train_z=True): the inducing inputs behind them) overrides both.
+    def start_params(self) -> ndarray:
+        """The vector an optimiser starts from: a host copy of model.params."""
+        return torch.clone(self.model.params).numpy()
+
+    def write_back(self, x: ndarray) -> None:
+        """Store an optimiser's result in the model: model.set_params(x)."""
+        self.model.set_params(torch.tensor(x))
+
 
 class _MemoLoss(Loss):
     """A loss whose device evaluation (`_evaluate_device`) is memoised on parameters, data and covariance: what MLE and LOO share."""

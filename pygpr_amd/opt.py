@@ -11,7 +11,6 @@ from typing import Callable
 
 import numpy as np
 import scipy.optimize as scopt
-import torch
 from numpy import ndarray
 
 from .loss import Loss
@@ -45,7 +44,7 @@ class _ScipyDriver(Opt):
         print(*self._trace(params), file=self.fstr)
 
     def minimize(self) -> None:
-        start = torch.clone(self.loss.model.params).numpy()
+        start = self.loss.start_params()
         self.fstr = open("opt.dat", "w")
         try:
             self.res = scopt.minimize(
@@ -59,7 +58,7 @@ class _ScipyDriver(Opt):
         finally:
             self.fstr.close()
         if self.res.success is True or self._write_back_on_failure:
-            self.loss.model.set_params(torch.from_numpy(self.res.x))
+            self.loss.write_back(self.res.x)
         if self.res.success is not True:
             print("Optimizer Failed")
         return None
@@ -118,7 +117,7 @@ class _QuadBase(Opt):
         self.gtol = gtol
 
     def _start(self, par):
-        return self.loss.model.params.numpy() if par is None else par
+        return self.loss.start_params() if par is None else par
 
     def _run(self) -> int:
         k = 0
@@ -130,7 +129,7 @@ class _QuadBase(Opt):
                 k += 1
                 print(k, gnorm, file=fstr)
         if self.loss.model is not None:
-            self.loss.model.set_params(torch.tensor(self.x))
+            self.loss.write_back(self.x)
         return k
 
 

@@ -22,11 +22,24 @@ y^T y), and the product Kuu^-1 Phi_aug (trace: T; times Kuu^-1: the last term of
              M = (Sigma^-1 - Kuu^-1) / sigma^2 + c c^T / sigma^6
 
 -- the rank-one correction rides in the same NN product as the matrix term, because A_c holds y_c -- and both contractions against
-dK/dtheta are pg_kernel_cross_grad (include/pygpr_hip_sparse.h), which rebuilds the derivative from the point tiles.  Gradients with
-respect to z, batched models, float32 and covariances longer than one pg_covspec are not served.
+dK/dtheta are pg_kernel_cross_grad (include/pygpr_hip_sparse.h), which rebuilds the derivative from the point tiles.  Batched
+models, float32 and covariances longer than one pg_covspec are not served.
 
-z is data.  `select_inducing` / `Sparse_GP.greedy` choose it among the training points: greedy conditional-variance selection, the
-partial pivoted Cholesky factorisation of k(x, x) on the device (include/pygpr_hip_select.h; 8 n m bytes of workspace for the factor).
+z is data to `VFE(model)`.  `select_inducing` / `Sparse_GP.greedy` choose it among the training points: greedy conditional-variance
+selection, the partial pivoted Cholesky factorisation of k(x, x) on the device (include/pygpr_hip_select.h; 8 n m bytes of workspace
+for the factor).  `VFE(model, train_z=True)` trains it from there, jointly with the hyper-parameters, on the packed vector
+concat(hp, z.reshape(-1)).  The same weights give the gradient:
+
+    dL/dz_ik = 2 sum_j G_uu[i][j] dk(z_i, z_j)/dz_ik + sum_c sum_j G_uf,c[i][j] dk(z_i, x_j)/dz_ik
+
+(z_j held constant in the first sum: G_uu is symmetric, z_i enters row i and column i; JITTER, kdiag and the sigma^2 terms do not
+depend on z).  Both sums are pg_kernel_xgrad, the contraction of the kernel's first-argument derivative that Exact_GP.predict_grad uses,
+with the lanes on the inducing inputs: one call on G_uu, one accumulating call per chunk on the rows [:m] of the W_c pass 2 already
+holds; dL/dz rides in the evaluation's one transfer.  `predict_grad` is the same contraction on the test points, with u = c / sigma^2
+for the mean and B = V = Ksu (Kuu^-1 - Sigma^-1), the product `predict` forms anyway, for the variance.  z is unconstrained, and Sigma
+is factored unwhitened: a line search that drives two inducing inputs together ends in the LinAlgError an hp-only run ends in when
+sigma_n falls too far, and the error propagates out of the optimiser.  Matern-1/2 has no derivative at a coincident pair: it
+contributes 0.
 """
 import math
 from typing import NamedTuple, Sequence
@@ -121,7 +134,8 @@ def select_inducing(x: Tensor, cov: Covar, params, m: int, tol: float = 0.0) -> 
 
 
 class Sparse_GP(GPR):
-    """Variational inducing-point GP: x [n, d], y [n], z [m, d] inducing inputs (fixed data, like x), all float64; params as Exact_GP's.
+    """Variational inducing-point GP: x [n, d], y [n], z [m, d] inducing inputs (data like x, unless VFE(train_z=True) trains them),
+    all float64; params as Exact_GP's.
     `Sparse_GP.greedy(x, y, cov, m)` chooses z among the training points; `select_inducing` chooses it again at the current params."""
 
     def __init__(self, x: Tensor, y: Tensor, cov: Covar, z: Tensor) -> None:
@@ -238,12 +252,22 @@ class Sparse_GP(GPR):
         a[m, :nc] = yd[s: s + nc]
         return a
 
-    def _evaluate(self, hp: ndarray, want_grad: bool, keep: bool):
+    def _evaluate(self, hp: ndarray, want_grad: bool, keep: bool, want_zgrad: bool = False, z: ndarray = None):
         """One evaluation of the bound at the host vector hp: (loss, grad | None); keep: leave the prediction state behind.  Everything
-        is enqueued before the ONE synchronisation that reads the status words and the scalars."""
+        is enqueued before the ONE synchronisation that reads the status words and the scalars.  z: inducing inputs [m, d] (host) to
+        evaluate at in place of the model's own, which stay as they are.  want_zgrad (with want_grad): the gradient comes back packed,
+        concat(dL/dhp [nhp], dL/dz [m d]) -- the z part accumulated on the device by pg_kernel_xgrad from the weights the
+        hyper-parameter gradient forms anyway, and carried by the same transfer."""
+        assert want_grad or not want_zgrad, "the z-gradient shares the weights of the hyper-parameter gradient"
+        assert z is None or not keep, "the prediction state belongs to the model's own z"
         ops = get_ops()
         xd, yd, zd = self._device_data()
         n, d = xd.shape
+        if z is not None:
+            z = np.ascontiguousarray(z, dtype=np.float64)
+            if z.ndim != 2 or z.shape[1] != d or z.shape[0] < 1:
+                raise ValueError("Sparse_GP: z must be [m, %d] with m >= 1, got %s" % (d, z.shape))
+            zd = ops.to_device(torch.from_numpy(z), torch.float64)
         m = zd.shape[0]
         ma = pad_to(m + 1)
         (sp,), nhp = spec_of(self.cov, d)
@@ -301,6 +325,11 @@ class Sparse_GP(GPR):
                 gm.mul_(0.5 / sig2).add_(sgi[:m, :m], alpha=0.5).sub_(kuui[:m, :m], alpha=0.5).add_(cc, alpha=0.5 / sig2 ** 2)
                 work = self._buf("gwork", max(1, ops.kernel_cross_grad_worksize(m, max(m, min(ch, n)), nhp)))
                 ops.kernel_cross_grad(spec, hpd, zd, zd, g, grad, accumulate=False, work=work)
+                gz = None
+                if want_zgrad:      # 2 sum_j G_uu[i][j] dk(z_i, z_j)/dz_i: z_i enters row i and column i of the symmetric G_uu
+                    gz = self._buf("gz", m, d)
+                    ops.kernel_xgrad(spec, hpd, zd, zd, b=g[:m], out_b=gz)
+                    gz.mul_(2.0)
                 mw = self._buf("mw", ma, ma, zero=True)                           # [M | -c / sigma^4 | 0], zero rows below m
                 mw[:m, :m].add_(sgi[:m, :m], alpha=1.0 / sig2).sub_(kuui[:m, :m], alpha=1.0 / sig2).add_(cc, alpha=1.0 / sig2 ** 3)
                 mw[:m, m] = c * (-1.0 / sig2 ** 2)
@@ -310,6 +339,10 @@ class Sparse_GP(GPR):
                     w = self._buf("w", ma, a.shape[1])
                     ops.gemm_raw(_lib.GEMM_NN, ma, a.shape[1], ma, 1.0, mw, a, 0.0, w)
                     ops.kernel_cross_grad(spec, hpd, zd, xd[s: s + nc], w, grad, accumulate=True, work=work)
+                    if want_zgrad:         # + sum_j G_uf,c[i][j] dk(z_i, x_j)/dz_i: the rows [:m] of the W_c the chunk already holds
+                        ops.kernel_xgrad(spec, hpd, zd, xd[s: s + nc], b=w[:m], out_b=gz, accumulate=True)
+                if want_zgrad:
+                    grad = torch.cat([grad, gz.reshape(-1)])
             if keep:
                 keepers.update(c=c, kuui=kuui, sgi=sgi, hpd=hpd)
             res[0] = torch.cat([torch.stack(scal), grad]).cpu().numpy()          # the one sync + transfer
@@ -355,7 +388,24 @@ class Sparse_GP(GPR):
         """[mean, var | covariance | NotImplemented] of y* at xp [q, d]: mean = Ksu c / sigma^2, cov = Kss - Ksu (Kuu^-1 - Sigma^-1) Kus
         with the noise on the diagonal of Kss.  var="diag" chunks the test points; var="full" takes them in one piece."""
         if torch.is_grad_enabled() and isinstance(xp, Tensor) and xp.requires_grad:
-            raise NotImplementedError("Sparse_GP.predict is not differentiable in the test points; use Exact_GP")
+            raise NotImplementedError("Sparse_GP.predict is not differentiable through autograd; predict_grad returns the derivatives in the "
+                                      "test points")
+        return self._predict(xp, var)[:2]
+
+    def predict_grad(self, xp: Tensor, var: str = "diag") -> Sequence[Tensor]:
+        """[mean, var, dmean, dvar] (var="diag") or [mean, dmean] (var="none") without autograd, Exact_GP.predict_grad's contract:
+        dmean[p, :] = d mean_p / d xp_p = sum_i (c_i / sigma^2) dk(xp_p, z_i)/dxp_p and dvar[p, :] = d var_p / d xp_p =
+        -2 sum_i V_pi dk(xp_p, z_i)/dxp_p with V = Ksu (Kuu^-1 - Sigma^-1), both [q, d] float64 on xp's device.  Mean and variance are
+        `predict`'s own (same path, same bits); V is the product that path forms, and both derivatives come out of one pg_kernel_xgrad
+        call per chunk of test points.  Matern-1/2: a test point on an inducing point contributes 0 for that pair."""
+        if var not in ("diag", "none"):
+            raise ValueError("predict_grad: var must be 'diag' or 'none', got %r" % (var,))
+        with torch.no_grad():
+            mean, vr, dmean, dvar = self._predict(xp, var, grads=True)
+        return [mean, dmean] if var == "none" else [mean, vr, dmean, dvar]
+
+    def _predict(self, xp: Tensor, var: str, grads: bool = False):
+        """[mean, var | covariance | NotImplemented] and, for grads (not with var="full"), the two derivatives in the test points."""
         if xp.dim() != 2 or xp.shape[1] != self._x.shape[1]:
             raise NotImplementedError("Sparse_GP.predict: xp must be [q, %d] (no batches)" % self._x.shape[1])
         ops = get_ops()
@@ -380,6 +430,14 @@ class Sparse_GP(GPR):
             ops.symmetrize(cov, qp)                                                    # the upper triangle is the mirror: exactly symmetric
             return [mean.to(xp.device), cov[:q, :q].contiguous().to(xp.device)]
         vr = ops.empty(q, dtype=torch.float64) if want == "diag" else None
+        dmean = dvar = u = None
+        if grads:
+            d = xpd.shape[1]
+            dmean = ops.empty(q, d, dtype=torch.float64)
+            dvar = ops.empty(q, d, dtype=torch.float64) if want == "diag" else None
+            u = st.get("u")
+            if u is None:
+                u = st["u"] = st["c"] / st["sig2"]
         for s in range(0, q, _CHUNK):
             xq = xpd[s: s + _CHUNK]
             qc = xq.shape[0]
@@ -391,22 +449,68 @@ class Sparse_GP(GPR):
             mean[s: s + qc] = v[:qc, m]
             if want == "diag":
                 vr[s: s + qc] = st["kss"] - (v[:qc, :m] * kt[:qc, :m]).sum(1)
-        if want == "diag":
-            return [mean.to(xp.device), vr.to(xp.device)]
-        return [mean.to(xp.device), NotImplemented]
+            if grads:       # u = c / sigma^2 for the mean, B = V = columns [:m] of the product above for the variance: one pass for both
+                ops.kernel_xgrad(spec, hpd, xq, zd, u=u, b=v[:qc] if want == "diag" else None, out_u=dmean[s: s + qc],
+                                 out_b=dvar[s: s + qc] if want == "diag" else None)
+        out = [mean.to(xp.device), vr.to(xp.device) if want == "diag" else NotImplemented]
+        if grads:
+            out += [dmean.to(xp.device), dvar.mul_(-2.0).to(xp.device) if want == "diag" else None]
+        return out
 
 
 class VFE(_MemoLoss):
-    """The negative collapsed variational bound of a Sparse_GP as a training objective with MLE's protocol (`CG(VFE(model))`)."""
+    """The negative collapsed variational bound of a Sparse_GP as a training objective with MLE's protocol (`CG(VFE(model))`).
 
-    def __init__(self, model: Sparse_GP) -> None:
+    train_z=True trains the inducing inputs with the hyper-parameters: the parameter vector is concat(hp [nhp], z.reshape(-1) [m d]),
+    `loss` / `grad` / `loss_and_grad` take and return that length and evaluate at the z inside the vector without assigning it to the
+    model, and an optimiser starts from (model.params, model.z) and writes both back (`start_params` / `write_back`).  Every
+    evaluation forms the gradient, so that `loss(p)` followed by `grad(p)` is one device evaluation through the memo.  z is
+    unconstrained: no box, no reparametrisation.  Matern-1/2 has no derivative where an inducing input sits on a training point or on
+    another inducing input; that pair contributes 0."""
+
+    def __init__(self, model: Sparse_GP, train_z: bool = False) -> None:
         if not isinstance(model, Sparse_GP):
             raise TypeError("VFE is the loss of a Sparse_GP, got %s" % type(model).__name__)
         super().__init__(model)
         self._z_seen = None
+        self.train_z = bool(train_z)
+
+    # ---- the packed vector (train_z) --------------------------------------------------------
+    def pack(self, hp, z) -> ndarray:
+        """concat(hp [nhp], z.reshape(-1) [m d]) as a new host float64 vector."""
+        as_np = lambda t: t.detach().cpu().numpy() if isinstance(t, Tensor) else np.asarray(t)      # noqa: E731
+        return np.concatenate([as_np(hp).reshape(-1), as_np(z).reshape(-1)]).astype(np.float64)
+
+    def unpack(self, params: ndarray):
+        """(hp [nhp], z [m, d]) views of a packed vector; a vector of any other length than nhp + m d is a ValueError."""
+        mdl = self.model
+        (m, d), (_, nhp) = mdl._z.shape, spec_of(mdl.cov, mdl._x.shape[-1])
+        p = np.asarray(params, dtype=np.float64)
+        if p.ndim != 1 or p.size != nhp + m * d:
+            raise ValueError("VFE(train_z=True) takes concat(hp [%d], z.reshape(-1) [%d x %d]) = %d entries, got shape %s"
+                             % (nhp, m, d, nhp + m * d, p.shape))
+        return p[:nhp], p[nhp:].reshape(m, d)
+
+    def start_params(self) -> ndarray:
+        if not self.train_z:
+            return super().start_params()
+        return self.pack(self.model.params, self.model.z)
+
+    def write_back(self, x: ndarray) -> None:
+        if not self.train_z:
+            return super().write_back(x)
+        dev = x.device if isinstance(x, Tensor) else "cpu"
+        hp, z = self.unpack(x.detach().cpu().numpy() if isinstance(x, Tensor) else x)
+        self.model.set_params(torch.tensor(hp))
+        self.model.z = torch.tensor(z, dtype=torch.float64, device=dev)      # the setter marks the model dirty; the memo goes with it
 
     def _evaluate(self, params: ndarray, want_grad: bool):
         m = self.model
+        if self.train_z:
+            self.unpack(params)                              # a wrong length is refused before anything touches the device
+            # every evaluation forms the gradient: loss(p) and then grad(p) at the same p -- get_learn_rate's order -- is ONE device
+            # evaluation (with the plain loss the second call repeats both passes), and scipy's CG never asks for the loss alone
+            want_grad = True
         token = (id(m._z), m._z._version, m._z_version)      # the memo's key holds x, y and the covariance: z is this model's own
         if token != self._z_seen:
             self._memo = None
@@ -415,5 +519,8 @@ class VFE(_MemoLoss):
 
     def _evaluate_device(self, params: ndarray, want_grad: bool, key=None, reuse_factor=False):
         m = self.model
+        if self.train_z:
+            hp, z = self.unpack(params)
+            return m._evaluate(m._hp_host(hp), want_grad, keep=False, want_zgrad=want_grad, z=z)
         loss, grad = m._evaluate(m._hp_host(np.asarray(params, dtype=np.float64)), want_grad, keep=False)
         return loss, grad

@@ -2,9 +2,12 @@
 the evaluation's time goes -- the covariance build of a chunk, the two streaming products of the GEMM core (pass 1: Phi_aug += A A^T on
 the lower tiles, K = the chunk; pass 2: W = [M | -c / sigma^4] A), the rectangular contraction pg_kernel_cross_grad, and the rest (the
 m x m algebra, the Kuu contraction, transfers), taken as the difference.  Each piece is timed alone on one full chunk and multiplied
-by the number of chunks.  Median of `--reps` after two warm-up runs, events on the caller stream.  One JSON line.
+by the number of chunks.  Beside them: VFE(train_z=True).loss_and_grad, which adds the gradient in the inducing inputs (one
+pg_kernel_xgrad call on Kuu and one per chunk on the W the chunk already holds), that call timed alone on one full chunk, and
+predict_grad on the same test points.  Median of `--reps` after two warm-up runs, events on the caller stream; `--spread` repeats the
+two loss_and_grad medians that many times and reports their range.  One JSON line.
 
-    python tools/probe_sparse.py [--n 262144] [--m 2048] [--d 8] [--q 8192] [--reps 5]
+    python tools/probe_sparse.py [--n 262144] [--m 2048] [--d 8] [--q 8192] [--reps 5] [--spread 3]
 """
 import argparse
 import json
@@ -43,6 +46,7 @@ def main():
     ap.add_argument("--d", type=int, default=8)
     ap.add_argument("--q", type=int, default=8192)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--spread", type=int, default=3)
     args = ap.parse_args()
     n, m, d = args.n, args.m, args.d
     rng = np.random.default_rng(1)
@@ -54,11 +58,19 @@ def main():
     gp.set_params(torch.from_numpy(hp))
     vfe = pg.VFE(gp)
     vfe.memoize = False
-    t_eval = timed(lambda: vfe.loss_and_grad(hp), args.reps)
+    vfz = pg.VFE(gp, train_z=True)
+    vfz.memoize = False
+    pz = vfz.start_params()
+    evals, evals_z = [], []
+    for _ in range(max(1, args.spread)):        # interleaved: both see the same drift of the session
+        evals.append(timed(lambda: vfe.loss_and_grad(hp), args.reps))
+        evals_z.append(timed(lambda: vfz.loss_and_grad(pz), args.reps))
+    t_eval, t_eval_z = float(np.median(evals)), float(np.median(evals_z))
     t_loss = timed(lambda: vfe.loss(hp), args.reps)
     xp = torch.from_numpy(rng.random((args.q, d)))
     gp.update()
     t_pred = timed(lambda: gp.predict(xp, var="diag"), args.reps)
+    t_pred_grad = timed(lambda: gp.predict_grad(xp, var="diag"), args.reps)
 
     # the pieces, on one full chunk
     ops = pg._ops.get_ops()
@@ -80,10 +92,18 @@ def main():
     t_nt128 = timed(lambda: ops.gemm_raw(_lib.GEMM_NT, ma, ma, cp, 1.0, a, a, 1.0, phi, tri=1), args.reps)
     t_nn = timed(lambda: ops.gemm_raw(_lib.GEMM_NN, ma, cp, ma, 1.0, mw, a, 0.0, w), args.reps)
     t_cg = timed(lambda: ops.kernel_cross_grad(spec, hpd, zd, xd[:ch], w, grad, accumulate=True, work=work), args.reps)
+    gz = ops.zeros(m, d, dtype=torch.float64)
+    t_xg = timed(lambda: ops.kernel_xgrad(spec, hpd, zd, xd[:ch], b=w[:m], out_b=gz, accumulate=True), args.reps)
+    t_xg_uu = timed(lambda: ops.kernel_xgrad(spec, hpd, zd, zd, b=mw[:m], out_b=gz), args.reps)
     pieces = nch * (2 * t_build + t_nt + t_nn + t_cg)
     print(json.dumps({
         "n": n, "m": m, "d": d, "dtype": "fp64", "chunk": sp._SPARSE_CHUNK, "chunks": nch, "reps": args.reps,
-        "loss_and_grad_ms": round(t_eval, 2), "loss_ms": round(t_loss, 2), "predict_diag_q%d_ms" % args.q: round(t_pred, 2),
+        "loss_and_grad_ms": round(t_eval, 2), "loss_and_grad_ms_range": [round(min(evals), 2), round(max(evals), 2)],
+        "loss_and_grad_train_z_ms": round(t_eval_z, 2), "loss_and_grad_train_z_ms_range": [round(min(evals_z), 2), round(max(evals_z), 2)],
+        "predict_grad_diag_q%d_ms" % args.q: round(t_pred_grad, 2),
+        "per_chunk_xgrad_ms": round(t_xg, 3), "xgrad_kuu_ms": round(t_xg_uu, 3), "xgrad_ps_per_pair": round(t_xg * 1e9 / (m * ch), 2),
+        "xgrad_streamed_ms": round(nch * t_xg + t_xg_uu, 2),
+        "loss_ms": round(t_loss, 2), "predict_diag_q%d_ms" % args.q: round(t_pred, 2),
         "per_chunk_build_ms": round(t_build, 3), "per_chunk_pass1_nt_ms": round(t_nt, 3), "per_chunk_pass2_nn_ms": round(t_nn, 3),
         "per_chunk_cross_grad_ms": round(t_cg, 3),
         "pass1_tiling": 64 if sp._pass1_variant(ma) == _lib.GEMM_NT_64 else 128, "per_chunk_pass1_nt_128_tiles_ms": round(t_nt128, 3),
