@@ -36,10 +36,28 @@ concat(hp, z.reshape(-1)).  The same weights give the gradient:
 depend on z).  Both sums are pg_kernel_xgrad, the contraction of the kernel's first-argument derivative that Exact_GP.predict_grad uses,
 with the lanes on the inducing inputs: one call on G_uu, one accumulating call per chunk on the rows [:m] of the W_c pass 2 already
 holds; dL/dz rides in the evaluation's one transfer.  `predict_grad` is the same contraction on the test points, with u = c / sigma^2
-for the mean and B = V = Ksu (Kuu^-1 - Sigma^-1), the product `predict` forms anyway, for the variance.  z is unconstrained, and Sigma
-is factored unwhitened: a line search that drives two inducing inputs together ends in the LinAlgError an hp-only run ends in when
-sigma_n falls too far, and the error propagates out of the optimiser.  Matern-1/2 has no derivative at a coincident pair: it
-contributes 0.
+for the mean and B = V = Ksu (Kuu^-1 - Sigma^-1), the product `predict` forms anyway, for the variance.  z is unconstrained, and by
+default Sigma is factored unwhitened: a line search that drives two inducing inputs together ends in the LinAlgError an hp-only run
+ends in when sigma_n falls too far, and the error propagates out of the optimiser -- the whitened evaluation below is the one to train
+z on.  Matern-1/2 has no derivative at a coincident pair: it contributes 0.
+
+Whitened evaluation.  `Sparse_GP(..., whitened=True)` is a second path through the same model for small noise, many
+or trainable inducing inputs, where Sigma spans 1e12 and more and is no longer numerically positive definite.  With Li = Lu^-1,
+V_c = Li A_c (row m still y_c: the padding of Li is the identity), Psi_aug = sum_c V_c V_c^T (Psi, b~ = Li b in row m, y^T y at [m, m]),
+D = I + Psi / sigma^2, Ld = chol(D), c~ = D^-1 b~ by substitution and E = I - D^-1:
+
+    L     = sum log diag Ld + n/2 log sigma^2 + y^T y / (2 sigma^2) - b~^T c~ / (2 sigma^4) + n/2 log 2pi + (n kdiag - tr Psi) / (2 sigma^2)
+    G_uu  = 1/2 Li^T [(D^-1 - I) + c~ c~^T / sigma^4 + Psi / sigma^2] Li
+    W_c   = Li^T ([M~ | -c~ / sigma^4] V_c) = G_uf,c,      M~ = (D^-1 - I) / sigma^2 + c~ c~^T / sigma^6
+    mean* = w c~ / sigma^2,   cov* = Kss - (w E) w^T,   w = Ksu Li^T per chunk of test points;   predict_grad: u = Li^T c~ / sigma^2, V = (w E) Li
+
+D has no eigenvalue below 1 whatever Kuu's condition.  Every chunk is whitened BEFORE it is accumulated (Lu^-1 Phi Lu^-T, formed after
+Phi has lost the digits, fails like Sigma), and the weights stay whitened per chunk: G_uu and W_c come back to original coordinates only
+after the product with the chunk, because Li^T . Li folded into one m x m matrix and applied to the unwhitened Kuf_c or Ksu loses the
+gradient and the variance at small noise.  No new kernel: the products with Li are K-range products of the GEMM core (Li from pg_trtri
+has scratch above its diagonal blocks), three per chunk of training points more than the unwhitened passes and one per chunk of test
+points.  Still one synchronisation per evaluation and O(m^2 + m chunk) memory, with one more chunk-sized buffer.  The default,
+whitened=False, is the evaluation described above, call for call.
 """
 import math
 from typing import NamedTuple, Sequence
@@ -136,11 +154,14 @@ def select_inducing(x: Tensor, cov: Covar, params, m: int, tol: float = 0.0) -> 
 class Sparse_GP(GPR):
     """Variational inducing-point GP: x [n, d], y [n], z [m, d] inducing inputs (data like x, unless VFE(train_z=True) trains them),
     all float64; params as Exact_GP's.
-    `Sparse_GP.greedy(x, y, cov, m)` chooses z among the training points; `select_inducing` chooses it again at the current params."""
+    `Sparse_GP.greedy(x, y, cov, m)` chooses z among the training points; `select_inducing` chooses it again at the current params.
+    whitened=True evaluates the bound, its gradients and the predictions in the coordinates of Lu^-1 (module docstring, "Whitened
+    evaluation"): for small noise, many or trainable inducing inputs, where Sigma itself can no longer be factored."""
 
-    def __init__(self, x: Tensor, y: Tensor, cov: Covar, z: Tensor) -> None:
+    def __init__(self, x: Tensor, y: Tensor, cov: Covar, z: Tensor, whitened: bool = False) -> None:
         super().__init__(x, y, cov)
         self._z = z
+        self._whitened = bool(whitened)
         self._check_data()
         d = x.shape[-1]
         _, noise, _ = terms(cov, d)
@@ -159,11 +180,11 @@ class Sparse_GP(GPR):
 
     # ---- inducing inputs from the training points -------------------------------------------
     @classmethod
-    def greedy(cls, x: Tensor, y: Tensor, cov: Covar, m: int, params=None, tol: float = 0.0) -> "Sparse_GP":
+    def greedy(cls, x: Tensor, y: Tensor, cov: Covar, m: int, params=None, tol: float = 0.0, whitened: bool = False) -> "Sparse_GP":
         """A model whose m (or fewer: `tol`) inducing inputs are chosen among x by `select_inducing` at `params`, which the model
-        then holds, or at cov.init_params(x)."""
+        then holds, or at cov.init_params(x).  whitened: as the constructor's (the selection itself does not depend on it)."""
         res = select_inducing(x, cov, cov.init_params(x) if params is None else params, m, tol)
-        model = cls(x, y, cov, x[res.index])
+        model = cls(x, y, cov, x[res.index], whitened=whitened)
         if params is not None:
             model.set_params(params if isinstance(params, Tensor) else torch.as_tensor(np.asarray(params)))
         return model
@@ -185,6 +206,11 @@ class Sparse_GP(GPR):
         self._z = value
         self._z_version += 1
         self._data_changed()
+
+    @property
+    def whitened(self) -> bool:
+        """Whether the model evaluates in whitened coordinates; fixed at construction."""
+        return self._whitened
 
     @property
     def dtype(self):
@@ -260,6 +286,8 @@ class Sparse_GP(GPR):
         hyper-parameter gradient forms anyway, and carried by the same transfer."""
         assert want_grad or not want_zgrad, "the z-gradient shares the weights of the hyper-parameter gradient"
         assert z is None or not keep, "the prediction state belongs to the model's own z"
+        if self._whitened:
+            return self._evaluate_whitened(hp, want_grad, keep, want_zgrad, z)
         ops = get_ops()
         xd, yd, zd = self._device_data()
         n, d = xd.shape
@@ -368,6 +396,137 @@ class Sparse_GP(GPR):
             self._state = dict(keepers, m=m, ma=ma, sig2=sig2, kss=kdiag + sig2, spec=spec, full_spec=sp)
         return np.array(loss), grad
 
+    def _evaluate_whitened(self, hp: ndarray, want_grad: bool, keep: bool, want_zgrad: bool = False, z: ndarray = None):
+        """_evaluate for a whitened model (module docstring, "Whitened evaluation"): the same contract, one synchronisation, and
+        O(m^2 + m chunk) memory with one chunk-sized buffer more than the unwhitened passes (A_c, V_c and W_c; the product
+        [M~ | -c~ / sigma^4] V_c lands in A_c's buffer).  Li = Lu^-1 comes from pg_trtri, which leaves scratch in the blocks above
+        the diagonal: every product with it is a K-range product of the GEMM core that never reads them."""
+        ops = get_ops()
+        xd, yd, zd = self._device_data()
+        n, d = xd.shape
+        if z is not None:
+            z = np.ascontiguousarray(z, dtype=np.float64)
+            if z.ndim != 2 or z.shape[1] != d or z.shape[0] < 1:
+                raise ValueError("Sparse_GP: z must be [m, %d] with m >= 1, got %s" % (d, z.shape))
+            zd = ops.to_device(torch.from_numpy(z), torch.float64)
+        m = zd.shape[0]
+        ma = pad_to(m + 1)
+        (sp,), nhp = spec_of(self.cov, d)
+        spec = _stationary(sp)
+        sig2, kdiag, tms, noise = self._prior(hp)
+        hpd = ops.to_device(torch.from_numpy(hp), torch.float64)
+        ch = int(_SPARSE_CHUNK)
+        chunks = [(s, min(ch, n - s)) for s in range(0, n, ch)]
+        info = torch.zeros(2, dtype=torch.int32, device=ops.device)
+        res = [None]
+        keepers = {}
+
+        def whiten(li, a):
+            """V_c = Li A_c: the rows [:m] whitened, row m (y_c) and the zero rows below it unchanged (Li is the identity there)."""
+            v = self._buf("v", ma, a.shape[1])
+            ops.trmm_lower(li, a, v)
+            return v
+
+        def enqueue():
+            # Lu and Li = Lu^-1 first: every chunk is whitened before it is accumulated
+            lu = self._buf("lu", ma, ma)
+            ops.kernel_build(spec, hpd, zd, None, lu, jitter=JITTER)       # Kuu + JITTER I, identity in the padding
+            invd = self._buf("invd", 2, ops.potrf_worksize(ma, torch.float64))
+            ops.potrf(lu, invd[0], info[0:1])
+            li = self._buf("li", ma, ma) if not keep else ops.empty(ma, ma)
+            ops.trtri(lu, invd[0], li)
+            # pass 1: Psi_aug = sum_c V_c V_c^T (lower tiles; mirrored once at the end): Psi, b~ = Li b (row m) and y^T y ([m, m])
+            psi = self._buf("psi", ma, ma, zero=True)
+            v = None
+            for s, nc in chunks:
+                v = whiten(li, self._build_chunk(ops, spec, hpd, zd, xd, yd, s, nc, m, ma))
+                ops.gemm_raw(_pass1_variant(ma), ma, ma, v.shape[1], 1.0, v, v, 1.0, psi, tri=1)
+            ops.symmetrize(psi, ma)
+            psm, b, yy = psi[:m, :m], psi[:m, m], psi[m, m]
+            # D = I + Psi / sigma^2 (identity in the padding as well), Ld, c~ = D^-1 b~ by substitution against Ld
+            ld = self._buf("ld", ma, ma, zero=True)
+            ld.diagonal().fill_(1.0)
+            ld[:m, :m].add_(psm, alpha=1.0 / sig2)
+            ops.potrf(ld, invd[1], info[1:2])
+            ldd = ld.diagonal()[:m].log().sum()
+            bvec = self._buf("bvec", ma, zero=True)
+            bvec[:m] = b
+            cvec = self._buf("cvec", ma)
+            ops.potrs_vec(ld, invd[1], bvec, cvec)
+            c = cvec[:m].clone()
+            di = None
+            if want_grad or keep:                                           # D^-1 (the loss alone does not need it)
+                minv = self._buf("minv", ma, ma)
+                di = self._buf("dinv", ma, ma)
+                ops.trtri(ld, invd[1], minv)
+                ops.lauum(minv, di)
+                ops.symmetrize(di, ma)
+            tr_di = di[:m, :m].diagonal().sum() if want_grad else ldd.new_zeros(())
+            scal = [ldd, yy, (b * c).sum(), tr_di, psm.diagonal().sum(), (c * (psm * c).sum(1)).sum()]
+            grad = ops.zeros(nhp, dtype=torch.float64)
+            if want_grad:
+                cc = torch.outer(c, c)
+                # G_uu = 1/2 Li^T [(D^-1 - I) + c~ c~^T / sigma^4 + Psi / sigma^2] Li, back in original coordinates
+                xm = self._buf("xm", ma, ma, zero=True)
+                xm[:m, :m].add_(di[:m, :m]).add_(cc, alpha=1.0 / sig2 ** 2).add_(psm, alpha=1.0 / sig2)
+                xm[:m, :m].diagonal().sub_(1.0)
+                t = self._buf("minv", ma, ma)                               # (D^-1 is formed: the inverse factor's buffer is free)
+                ops.gemm_raw(_lib.GEMM_NN, ma, ma, ma, 1.0, xm, li, 0.0, t, klo=2)      # X Li: Li's rows from the tile column down
+                g = self._buf("guu", ma, ma)
+                ops.gemm_raw(_lib.GEMM_TN, ma, ma, ma, 0.5, li, t, 0.0, g, klo=1)       # 1/2 Li^T (X Li)
+                work = self._buf("gwork", max(1, ops.kernel_cross_grad_worksize(m, max(m, min(ch, n)), nhp)))
+                ops.kernel_cross_grad(spec, hpd, zd, zd, g, grad, accumulate=False, work=work)
+                gz = None
+                if want_zgrad:      # 2 sum_j G_uu[i][j] dk(z_i, z_j)/dz_i: z_i enters row i and column i of the symmetric G_uu
+                    gz = self._buf("gz", m, d)
+                    ops.kernel_xgrad(spec, hpd, zd, zd, b=g[:m], out_b=gz)
+                    gz.mul_(2.0)
+                mw = self._buf("mw", ma, ma, zero=True)                           # [M~ | -c~ / sigma^4 | 0], zero rows below m
+                mw[:m, :m].add_(di[:m, :m], alpha=1.0 / sig2).add_(cc, alpha=1.0 / sig2 ** 3)
+                mw[:m, :m].diagonal().sub_(1.0 / sig2)
+                mw[:m, m] = c * (-1.0 / sig2 ** 2)
+                for s, nc in chunks:       # pass 2: V_c again (one chunk: it is still there), W_c = Li^T ([M~ | -c~ / sigma^4] V_c), contract
+                    if len(chunks) > 1:
+                        v = whiten(li, self._build_chunk(ops, spec, hpd, zd, xd, yd, s, nc, m, ma))
+                    u = self._buf("chunk", ma, v.shape[1])                        # A_c is spent once V_c stands
+                    ops.gemm_raw(_lib.GEMM_NN, ma, v.shape[1], ma, 1.0, mw, v, 0.0, u)
+                    w = self._buf("w", ma, v.shape[1])
+                    ops.gemm_raw(_lib.GEMM_TN, ma, v.shape[1], ma, 1.0, li, u, 0.0, w, klo=1)      # Li^T (.): Li's rows from the tile row down
+                    ops.kernel_cross_grad(spec, hpd, zd, xd[s: s + nc], w, grad, accumulate=True, work=work)
+                    if want_zgrad:
+                        ops.kernel_xgrad(spec, hpd, zd, xd[s: s + nc], b=w[:m], out_b=gz, accumulate=True)
+                if want_zgrad:
+                    grad = torch.cat([grad, gz.reshape(-1)])
+            if keep:
+                em = ops.zeros(ma, ma, dtype=torch.float64)                       # [E | c~ / sigma^2 | 0], E = I - D^-1
+                em[:m, :m].sub_(di[:m, :m])
+                em[:m, :m].diagonal().add_(1.0)
+                em[:m, m] = c / sig2
+                keepers.update(c=c, li=li, bm=em, hpd=hpd)
+            res[0] = torch.cat([torch.stack(scal), grad]).cpu().numpy()          # the one sync + transfer
+
+        for st in _checked(enqueue, lambda: info.tolist()):
+            if st:
+                raise _lin_alg_error(st, " -- Kuu of the inducing points, or D = I + Psi / sigma^2")
+        ldd, yy, bc, tr_di, tr_psi, cpc = res[0][:6]
+        t = n * kdiag - tr_psi
+        loss = ldd + 0.5 * n * math.log(sig2) + yy / (2 * sig2) - bc / (2 * sig2 ** 2) + 0.5 * n * math.log(2 * math.pi) + t / (2 * sig2)
+        grad = None
+        if want_grad:
+            grad = res[0][6:].copy()
+            # tr(Sigma^-1 Phi) = tr(D^-1 Psi) = sigma^2 (m - tr D^-1), b^T c = b~^T c~, c^T Phi c = c~^T Psi c~
+            dsig2 = (-(m - tr_di) / (2 * sig2) + n / (2 * sig2) - yy / (2 * sig2 ** 2) + bc / sig2 ** 3 - cpc / (2 * sig2 ** 4)
+                     - t / (2 * sig2 ** 2))
+            for o in noise:
+                grad[o] = 2.0 * hp[o] * dsig2
+            for _, _, offs in tms:          # the trace of Kff: n / (2 sigma^2) dkdiag/dsigma_c (a product term: 2 term / sigma_c)
+                for o in offs:
+                    others = np.prod([hp[o2] ** 2 for o2 in offs if o2 != o])
+                    grad[o] += n / (2 * sig2) * 2.0 * hp[o] * others
+        if keep:
+            self._state = dict(keepers, m=m, ma=ma, sig2=sig2, kss=kdiag + sig2, spec=spec, full_spec=sp)
+        return np.array(loss), grad
+
     def update(self) -> None:
         self._device_data()                  # first: an in-place edit of x / y / z (version bump) marks the model dirty here
         if self.need_upd:
@@ -375,18 +534,20 @@ class Sparse_GP(GPR):
             self._evaluate(self._hp_host(), want_grad=False, keep=True)
             ops = get_ops()
             st = self._state
-            m, ma = st["m"], st["ma"]
-            bm = ops.zeros(ma, ma, dtype=torch.float64)       # [Kuu^-1 - Sigma^-1 | c / sigma^2 | 0]: variance and mean from one product
-            bm[:m, :m].add_(st["kuui"][:m, :m]).sub_(st["sgi"][:m, :m])
-            bm[:m, m] = st["c"] / st["sig2"]
-            st["bm"] = bm
+            if not self._whitened:          # (the whitened evaluation leaves its own: Li and [E | c~ / sigma^2 | 0])
+                m, ma = st["m"], st["ma"]
+                bm = ops.zeros(ma, ma, dtype=torch.float64)       # [Kuu^-1 - Sigma^-1 | c / sigma^2 | 0]: variance and mean from one product
+                bm[:m, :m].add_(st["kuui"][:m, :m]).sub_(st["sgi"][:m, :m])
+                bm[:m, m] = st["c"] / st["sig2"]
+                st["bm"] = bm
             self.need_upd = False
         return None
 
     # ---- prediction -------------------------------------------------------------------------
     def predict(self, xp: Tensor, var: str = "full") -> Sequence[Tensor]:
         """[mean, var | covariance | NotImplemented] of y* at xp [q, d]: mean = Ksu c / sigma^2, cov = Kss - Ksu (Kuu^-1 - Sigma^-1) Kus
-        with the noise on the diagonal of Kss.  var="diag" chunks the test points; var="full" takes them in one piece."""
+        with the noise on the diagonal of Kss.  var="diag" chunks the test points; var="full" takes them in one piece.  A whitened
+        model whitens every chunk of test points, w = Ksu Li^T, and forms mean = w c~ / sigma^2, cov = Kss - (w E) w^T."""
         if torch.is_grad_enabled() and isinstance(xp, Tensor) and xp.requires_grad:
             raise NotImplementedError("Sparse_GP.predict is not differentiable through autograd; predict_grad returns the derivatives in the "
                                       "test points")
@@ -397,12 +558,19 @@ class Sparse_GP(GPR):
         dmean[p, :] = d mean_p / d xp_p = sum_i (c_i / sigma^2) dk(xp_p, z_i)/dxp_p and dvar[p, :] = d var_p / d xp_p =
         -2 sum_i V_pi dk(xp_p, z_i)/dxp_p with V = Ksu (Kuu^-1 - Sigma^-1), both [q, d] float64 on xp's device.  Mean and variance are
         `predict`'s own (same path, same bits); V is the product that path forms, and both derivatives come out of one pg_kernel_xgrad
-        call per chunk of test points.  Matern-1/2: a test point on an inducing point contributes 0 for that pair."""
+        call per chunk of test points.  Matern-1/2: a test point on an inducing point contributes 0 for that pair.
+        A whitened model: u = Li^T c~ / sigma^2 and V = (w E) Li, w = Ksu Li^T whitened per chunk."""
         if var not in ("diag", "none"):
             raise ValueError("predict_grad: var must be 'diag' or 'none', got %r" % (var,))
         with torch.no_grad():
             mean, vr, dmean, dvar = self._predict(xp, var, grads=True)
         return [mean, dmean] if var == "none" else [mean, vr, dmean, dvar]
+
+    @staticmethod
+    def _whiten_rows(ops, li, kt, w):
+        """w = kt Li^T: a chunk of test points [q_pad, m_aug] in whitened coordinates (column m and beyond stay zero)."""
+        ops.trmm_lower_kt(li, kt, w)
+        return w
 
     def _predict(self, xp: Tensor, var: str, grads: bool = False):
         """[mean, var | covariance | NotImplemented] and, for grads (not with var="full"), the two derivatives in the test points."""
@@ -412,6 +580,7 @@ class Sparse_GP(GPR):
         self.update()
         st = self._state
         m, ma, bm, spec, hpd = st["m"], st["ma"], st["bm"], st["spec"], st["hpd"]
+        li = st.get("li")                    # a whitened model: every kt below is followed by w = kt Li^T, which takes its place
         _, _, zd = self._device_data()
         xpd = ops.to_device(xp, torch.float64)
         q = xpd.shape[0]
@@ -423,6 +592,8 @@ class Sparse_GP(GPR):
             v = ops.empty(qp, ma, dtype=torch.float64)
             cov = ops.empty(qp, qp, dtype=torch.float64)
             ops.kernel_build(spec, hpd, xpd, zd, kt)                                   # Ksu, test-point-major; zero in column m and beyond
+            if li is not None:
+                kt = self._whiten_rows(ops, li, kt, ops.empty(qp, ma, dtype=torch.float64))
             ops.gemm_raw(_lib.GEMM_NN, qp, ma, ma, 1.0, kt, bm, 0.0, v)                # [Ksu (Kuu^-1 - Sigma^-1) | mean | 0]
             mean.copy_(v[:q, m])
             ops.kernel_build(st["full_spec"], hpd, xpd, None, cov)                     # Kss incl. sigma_n^2, identity in the padding
@@ -436,8 +607,13 @@ class Sparse_GP(GPR):
             dmean = ops.empty(q, d, dtype=torch.float64)
             dvar = ops.empty(q, d, dtype=torch.float64) if want == "diag" else None
             u = st.get("u")
-            if u is None:
+            if u is None and li is None:
                 u = st["u"] = st["c"] / st["sig2"]
+            elif u is None:                 # Li^T c~ / sigma^2: the mean's weights back in original coordinates
+                cs = ops.zeros(ma, dtype=torch.float64)
+                cs[:m] = st["c"] / st["sig2"]
+                u = st["u"] = ops.empty(ma, dtype=torch.float64)
+                ops.trmv(li, cs, u, 1, ops.empty((ma // 256) * ma, dtype=torch.float64))
         for s in range(0, q, _CHUNK):
             xq = xpd[s: s + _CHUNK]
             qc = xq.shape[0]
@@ -445,10 +621,16 @@ class Sparse_GP(GPR):
             kt = self._buf("pkt", qp, ma)
             v = self._buf("pv", qp, ma)
             ops.kernel_build(spec, hpd, xq, zd, kt)
+            if li is not None:
+                kt = self._whiten_rows(ops, li, kt, self._buf("pw", qp, ma))
             ops.gemm_raw(_lib.GEMM_NN, qp, ma, ma, 1.0, kt, bm, 0.0, v)
             mean[s: s + qc] = v[:qc, m]
             if want == "diag":
                 vr[s: s + qc] = st["kss"] - (v[:qc, :m] * kt[:qc, :m]).sum(1)
+            if grads and li is not None and want == "diag":      # V = (w E) Li: Li's rows from the tile column down (v's column m meets zeros)
+                vo = self._buf("pvo", qp, ma)
+                ops.gemm_raw(_lib.GEMM_NN, qp, ma, ma, 1.0, v, li, 0.0, vo, klo=2)
+                v = vo
             if grads:       # u = c / sigma^2 for the mean, B = V = columns [:m] of the product above for the variance: one pass for both
                 ops.kernel_xgrad(spec, hpd, xq, zd, u=u, b=v[:qc] if want == "diag" else None, out_u=dmean[s: s + qc],
                                  out_b=dvar[s: s + qc] if want == "diag" else None)
@@ -511,7 +693,8 @@ class VFE(_MemoLoss):
             # every evaluation forms the gradient: loss(p) and then grad(p) at the same p -- get_learn_rate's order -- is ONE device
             # evaluation (with the plain loss the second call repeats both passes), and scipy's CG never asks for the loss alone
             want_grad = True
-        token = (id(m._z), m._z._version, m._z_version)      # the memo's key holds x, y and the covariance: z is this model's own
+        # the memo's key holds x, y and the covariance: z, and which of the two evaluations the model runs, are this model's own
+        token = (id(m._z), m._z._version, m._z_version, m.whitened)
         if token != self._z_seen:
             self._memo = None
             self._z_seen = token

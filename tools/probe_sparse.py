@@ -7,7 +7,12 @@ pg_kernel_xgrad call on Kuu and one per chunk on the W the chunk already holds),
 predict_grad on the same test points.  Median of `--reps` after two warm-up runs, events on the caller stream; `--spread` repeats the
 two loss_and_grad medians that many times and reports their range.  One JSON line.
 
-    python tools/probe_sparse.py [--n 262144] [--m 2048] [--d 8] [--q 8192] [--reps 5] [--spread 3]
+`--whitened` adds the same calls on a Sparse_GP(whitened=True) over the same tensors, in the same run, under "whitened": loss,
+loss_and_grad (with and without train_z), predict and predict_grad, and the three triangular products the whitened evaluation adds,
+each alone on one full chunk with its rate over the flop of the tiles it visits -- pass 1's V = Li A (NN, K range ends with the tile
+row), pass 2's W = Li^T U (TN, K range starts with the tile row) and prediction's w = Ksu Li^T (NT, K range ends with the tile column).
+
+    python tools/probe_sparse.py [--n 262144] [--m 2048] [--d 8] [--q 8192] [--reps 5] [--spread 3] [--whitened]
 """
 import argparse
 import json
@@ -47,6 +52,7 @@ def main():
     ap.add_argument("--q", type=int, default=8192)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--spread", type=int, default=3)
+    ap.add_argument("--whitened", action="store_true")
     args = ap.parse_args()
     n, m, d = args.n, args.m, args.d
     rng = np.random.default_rng(1)
@@ -96,6 +102,30 @@ def main():
     t_xg = timed(lambda: ops.kernel_xgrad(spec, hpd, zd, xd[:ch], b=w[:m], out_b=gz, accumulate=True), args.reps)
     t_xg_uu = timed(lambda: ops.kernel_xgrad(spec, hpd, zd, zd, b=mw[:m], out_b=gz), args.reps)
     pieces = nch * (2 * t_build + t_nt + t_nn + t_cg)
+    white = {}
+    if args.whitened:
+        gw = pg.Sparse_GP(gp.x, gp.y, gp.cov, gp.z, whitened=True)
+        gw.set_params(torch.from_numpy(hp))
+        vw, vwz = pg.VFE(gw), pg.VFE(gw, train_z=True)
+        vw.memoize = vwz.memoize = False
+        gw.update()
+        li = gw._state["li"]
+        qp = pad_to(min(args.q, sp._CHUNK))
+        kt, wq = ops.zeros(qp, ma, dtype=torch.float64), ops.empty(qp, ma, dtype=torch.float64)
+        t_v = timed(lambda: ops.trmm_lower(li, a, w), args.reps)
+        t_w = timed(lambda: ops.gemm_raw(_lib.GEMM_TN, ma, cp, ma, 1.0, li, a, 0.0, w, klo=1), args.reps)
+        t_q = timed(lambda: ops.trmm_lower_kt(li, kt, wq), args.reps)
+        tri = lambda cols, t: round(ma * (ma + 128.0) * cols / (t * 1e-3) / 1e12, 2)      # noqa: E731  (whole 128-tiles on and below the diagonal)
+        white = {"whitened": {
+            "loss_ms": round(timed(lambda: vw.loss(hp), args.reps), 2),
+            "loss_and_grad_ms": round(timed(lambda: vw.loss_and_grad(hp), args.reps), 2),
+            "loss_and_grad_train_z_ms": round(timed(lambda: vwz.loss_and_grad(pz), args.reps), 2),
+            "predict_diag_q%d_ms" % args.q: round(timed(lambda: gw.predict(xp, var="diag"), args.reps), 2),
+            "predict_grad_diag_q%d_ms" % args.q: round(timed(lambda: gw.predict_grad(xp, var="diag"), args.reps), 2),
+            "per_chunk_whiten_nn_khi1_ms": round(t_v, 3), "whiten_nn_khi1_tflops": tri(cp, t_v),
+            "per_chunk_unwhiten_tn_klo1_ms": round(t_w, 3), "unwhiten_tn_klo1_tflops": tri(cp, t_w),
+            "predict_whiten_nt_khi2_q%d_ms" % qp: round(t_q, 3), "predict_whiten_nt_khi2_tflops": tri(qp, t_q),
+        }}
     print(json.dumps({
         "n": n, "m": m, "d": d, "dtype": "fp64", "chunk": sp._SPARSE_CHUNK, "chunks": nch, "reps": args.reps,
         "loss_and_grad_ms": round(t_eval, 2), "loss_and_grad_ms_range": [round(min(evals), 2), round(max(evals), 2)],
@@ -111,7 +141,7 @@ def main():
         "pass2_nn_tflops": round(2.0 * ma * ma * cp / (t_nn * 1e-3) / 1e12, 2),
         "cross_grad_gpairs_per_s": round(m * ch / (t_cg * 1e-3) / 1e9, 2),
         "cross_grad_w_gbs": round(8.0 * m * ch / (t_cg * 1e-3) / 1e9, 1),
-        "streamed_ms": round(pieces, 2), "rest_ms": round(t_eval - pieces, 2),
+        "streamed_ms": round(pieces, 2), "rest_ms": round(t_eval - pieces, 2), **white,
     }), flush=True)
 
 
