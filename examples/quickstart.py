@@ -65,6 +65,12 @@ print("sparse GP, m = 64: bound %.4f, %.4f after reselecting; prior variance lef
 mu_s, var_s = sgp.predict(xs, var="diag")
 print("sparse GP test RMSE %.4f" % float((mu_s - torch.sin(-xs.sum(-1))).pow(2).mean().sqrt()))
 
+# ---- the exact posterior without the n x n matrix: conjugate gradients on the fused covariance product, at the trained parameters
+igp = PyGPR.Iterative_GP(x, y, cov, rank=64, tol=1e-10)
+igp.set_params(gp.params)
+print("iterative vs exact GP: max |mean difference| %.2e after %d CG iterations" % (
+    float((igp.predict(xs, var="none")[0] - mean).abs().max()), igp.cg_info["iterations"]))
+
 # ---- scikit-learn facade
 sk = PyGPR.SK_WRAP(PyGPR.Exact_GP(x, y, cov))
 sk.model.set_params(gp.params)

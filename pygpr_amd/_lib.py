@@ -1,5 +1,5 @@
 """ctypes binding of libpygpr_hip.so (C ABI: include/pygpr_hip.h, include/pygpr_hip_loo.h, include/pygpr_hip_sample.h,
-include/pygpr_hip_sparse.h, include/pygpr_hip_select.h).
+include/pygpr_hip_sparse.h, include/pygpr_hip_select.h, include/pygpr_hip_matmul.h).
 
 There is no CPU fallback: `load()` raises if the shared object is missing, and every compute call
 needs a HIP device.  Build the library with `python __graft_entry__.py` (hipcc, gfx950).
@@ -15,6 +15,7 @@ HEADER_LOO = os.path.join(os.path.dirname(_HERE), "include", "pygpr_hip_loo.h") 
 HEADER_SAMPLE = os.path.join(os.path.dirname(_HERE), "include", "pygpr_hip_sample.h")   # the device normal generator (a third)
 HEADER_SPARSE = os.path.join(os.path.dirname(_HERE), "include", "pygpr_hip_sparse.h")   # the inducing-point GP's contraction (a fourth)
 HEADER_SELECT = os.path.join(os.path.dirname(_HERE), "include", "pygpr_hip_select.h")   # greedy inducing-point selection (a fifth)
+HEADER_MATMUL = os.path.join(os.path.dirname(_HERE), "include", "pygpr_hip_matmul.h")   # the matrix-free covariance product (a sixth)
 
 PG_F64, PG_F32 = 0, 1
 PG_KIND_RBF, PG_KIND_MATERN52, PG_KIND_SQDIST, PG_KIND_MATERN32, PG_KIND_MATERN12 = 0, 1, 2, 3, 4
@@ -89,6 +90,7 @@ _SIGS_LOO = signatures(parse_prototypes(open(HEADER_LOO).read()))
 _SIGS_SAMPLE = signatures(parse_prototypes(open(HEADER_SAMPLE).read()))
 _SIGS_SPARSE = signatures(parse_prototypes(open(HEADER_SPARSE).read()))
 _SIGS_SELECT = signatures(parse_prototypes(open(HEADER_SELECT).read()))
+_SIGS_MATMUL = signatures(parse_prototypes(open(HEADER_MATMUL).read()))
 
 _lib = None
 
@@ -103,12 +105,13 @@ def load(check_symbols=False):
                 "build it with `python __graft_entry__.py`" % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_LOO.items()) + list(_SIGS_SAMPLE.items()) + list(_SIGS_SPARSE.items())
-                                  + list(_SIGS_SELECT.items())):
+                                  + list(_SIGS_SELECT.items()) + list(_SIGS_MATMUL.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib
     if check_symbols:
-        missing = [s for s in header_symbols() + sorted(_SIGS_LOO) + sorted(_SIGS_SAMPLE) + sorted(_SIGS_SPARSE) + sorted(_SIGS_SELECT) if not hasattr(_lib, s)]
+        missing = [s for s in header_symbols() + sorted(_SIGS_LOO) + sorted(_SIGS_SAMPLE) + sorted(_SIGS_SPARSE) + sorted(_SIGS_SELECT)
+                   + sorted(_SIGS_MATMUL) if not hasattr(_lib, s)]
         unbound = [s for s in header_symbols() if s not in _SIGS]
         if missing or unbound:
             raise RuntimeError("C ABI mismatch: missing in .so %s, unbound in _lib.py %s" % (missing, unbound))
@@ -131,7 +134,7 @@ def build_id():
 
     csrc = os.path.join(_HERE, "csrc")
     h = hashlib.sha256()
-    for f in sorted(os.listdir(csrc)) + [HEADER, HEADER_LOO, HEADER_SAMPLE, HEADER_SPARSE, HEADER_SELECT]:
+    for f in sorted(os.listdir(csrc)) + [HEADER, HEADER_LOO, HEADER_SAMPLE, HEADER_SPARSE, HEADER_SELECT, HEADER_MATMUL]:
         path = f if os.path.isabs(f) else os.path.join(csrc, f)
         if path.endswith((".hip", ".h")):
             h.update(os.path.basename(path).encode())

@@ -378,6 +378,44 @@ class HipOps:
                    _p(trace), _p(resid), _p(work), self._st())
         return piv[:m_max], count, trace[:m_max], resid[:n]
 
+    # -- the matrix-free covariance product (include/pygpr_hip_matmul.h) --------------------------
+    def kernel_matmul_worksize(self, nr, nc, nrhs):
+        return int(self.lib.pg_kernel_matmul_worksize(int(nr), int(nc), int(nrhs)))
+
+    def kernel_matmul(self, spec, hp, xr, xc, v, out=None, jitter=0.0, work=None):
+        """out[i][c] = sum_j k(xr_i, xc_j) v[j][c] without forming k (pg_kernel_matmul); xc None: the symmetric operator on xr,
+        k(xr, xr) v + (sum sigma_n^2 + jitter) v.  xr [nr, d], xc [nc, d] float64 device tensors or views with unit stride along a row;
+        v [nc, nrhs] and out [nr, nrhs] likewise (a one-dimensional v counts as one column, and out comes back one-dimensional);
+        out is allocated when None.  One pg_covspec only.  work: kernel_matmul_worksize doubles, allocated when None and needed."""
+        (sp,) = _passes(spec)
+        self._chk(hp, work)
+        vec = v.dim() == 1
+        v2 = v.unsqueeze(1) if vec else v
+        nr, d = xr.shape
+        nc = xc.shape[0] if xc is not None else nr
+        nrhs = v2.shape[1]
+        if out is None:
+            out = self.empty(nr, dtype=torch.float64) if vec else self.empty(nr, nrhs, dtype=torch.float64)
+        o2 = out.unsqueeze(1) if out.dim() == 1 else out
+        for name, t, shape in (("xr", xr, (nr, d)), ("xc", xc, (nc, d)), ("v", v2, (nc, nrhs)), ("out", o2, (nr, nrhs))):
+            if t is None:
+                continue
+            if not (t.is_cuda and t.dim() == 2 and tuple(t.shape) == shape and t.dtype == torch.float64 and (t.stride(1) == 1 or t.shape[1] <= 1)):
+                raise ValueError("kernel_matmul needs %s %s float64 on the device, unit stride along a row" % (name, list(shape)))
+        assert hp.dtype == torch.float64
+
+        def ld(t, width):      # (a matrix of one row or none has no row stride to speak of)
+            return max(int(t.stride(0)), width, 1) if t.shape[0] > 1 else max(width, 1)
+
+        size = self.kernel_matmul_worksize(nr, nc, nrhs)
+        if work is None and size > 0:
+            work = self.empty(size, dtype=torch.float64)
+        assert size == 0 or (work.dtype == torch.float64 and work.numel() >= size)
+        xcp = _p(xc) if xc is None or nc > 0 else _p(hp)      # (an empty tensor has a null address, which would read as the symmetric form)
+        self._call("pg_kernel_matmul", PG_F64, C.byref(sp), _p(hp), _p(xr), ld(xr, d), nr, xcp, ld(xc, d) if xc is not None else 0, nc, d,
+                   _p(v2), ld(v2, nrhs), nrhs, float(jitter), _p(o2), ld(o2, nrhs), _p(work), self._st())
+        return out
+
     # -- normal variates (include/pygpr_hip_sample.h) -------------------------------------------
     def randn(self, out, rows, cols, seed, stream_id=0, row0=0):
         """out[r][q] = normal(seed, stream_id, row0 + r, q) for r < rows, q < cols, zero in the rest of out (pg_randn): out is a 2-D

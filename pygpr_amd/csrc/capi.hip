@@ -8,6 +8,7 @@
 #include "pygpr_hip_sample.h"
 #include "sparse.h"
 #include "select.h"
+#include "kmatmul.h"
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -665,6 +666,32 @@ int pg_greedy_select(pg_handle h, int dtype, const pg_covspec* spec, const doubl
     NEED(ldx >= d, "ldx >= d");
     NEED(m_max == 0 || (X && piv && trace && resid && work), "null pointer");
     return pg_greedy_select_impl(ST(stream), *spec, hp, (const double*)X, ldx, n, d, m_max, floor, piv, count, trace, resid, (double*)work);
+}
+
+long pg_kernel_matmul_worksize(int nr, int nc, int nrhs) { return (nr >= 0 && nc >= 0 && nrhs >= 0) ? pg_kmatmul_worksize_impl(nr, nc, nrhs) : -1; }
+
+int pg_kernel_matmul(pg_handle h, int dtype, const pg_covspec* spec, const double* hp, const void* Xr, long ldr, int nr, const void* Xc,
+                     long ldc, int nc, int d, const void* V, long ldv, int nrhs, double jitter, void* OUT, long ldo, void* work,
+                     void* stream) {
+    JOIN(h, stream);
+    NEED(h && hp, "null pointer");
+    NEED(dtype == PG_F64, "float64 only (dtype must be PG_F64)");
+    if (check_spec(spec, __func__)) return -1;      // (PG_KIND_SQDIST is refused: it is no covariance)
+    for (int c = 0; c < (spec->ncomp & ~PG_SPEC_PRODUCT); ++c) NEED(spec->off[c] >= 0, "negative offset in the covariance spec");
+    for (int q = 0; q < spec->nnoise; ++q) NEED(spec->noise_off[q] >= 0, "negative offset in the covariance spec");
+    const int sym = (Xc == nullptr);
+    if (sym) { Xc = Xr; ldc = ldr; nc = nr; }
+    if (!(nr >= 0 && nc >= 0 && nrhs >= 0 && d >= 1 && d <= PG_MAX_DIM)) {
+        pg_set_error("%s: bad shape (0 <= nr, nc, nrhs; 1 <= d <= PG_MAX_DIM)", __func__);
+        return -2;
+    }
+    if ((nrhs + 31) / 32 > 65535) { pg_set_error("%s: nrhs <= 32 * 65535", __func__); return -2; }
+    NEED(ldr >= d && ldc >= d && ldv >= nrhs && ldo >= nrhs, "ldr, ldc >= d and ldv, ldo >= nrhs");
+    if (nr == 0 || nrhs == 0) return 0;
+    NEED(Xr && OUT && (nc == 0 || (Xc && V)), "null pointer");
+    NEED(work || pg_kmatmul_worksize_impl(nr, nc, nrhs) == 0, "this shape needs its workspace (pg_kernel_matmul_worksize)");
+    return pg_kmatmul_impl(ST(stream), *spec, hp, (const double*)Xr, ldr, nr, (const double*)Xc, ldc, nc, d, sym, (const double*)V, ldv, nrhs,
+                           jitter, (double*)OUT, ldo, (double*)work);
 }
 
 int pg_randn(pg_handle h, int dtype, long seed, int stream_id, int row0, int rows, int cols, void* Z, long ldz, int rows_pad, int cols_pad,

@@ -1,0 +1,320 @@
+"""Matrix-free exact GP regression: Exact_GP's posterior from preconditioned conjugate gradients on the MI355X.  New, not in the
+reference.
+
+The same function as Exact_GP: A = k(x, x) + (sum sigma_n^2 + JITTER) I, alpha = A^-1 y, mean* = k(x*, x) alpha,
+cov* = K** - K*^T A^-1 K* with the noise on the diagonal of K**.  A is never formed: every product A V is pg_kernel_matmul
+(include/pygpr_hip_matmul.h), which evaluates the covariance from the point tiles inside the product.  Memory is O(n (rank + nrhs));
+no n x n array exists at any time, so n is bounded by time, not by the three n x n matrices Exact_GP keeps.
+
+Preconditioner.  The partial pivoted Cholesky factor of k(x, x) that greedy selection computes (`select_inducing`): with m = min(rank, n)
+pivots z = x[piv], Lu = chol(k(z, z) + JITTER I) and L = k(x, z) Lu^-T (n x m, kept), P = L L^T + shift I and, by Woodbury with
+C = shift I + L^T L (m x m, factored once),
+
+    P^-1 r = (r - L C^-1 L^T r) / shift.
+
+L is built in row chunks from cross builds and whitened per chunk like a Sparse_GP's test points; L^T L, L^T r and L u are products of
+the GEMM core on padded buffers (zero rows and columns in the padding, the identity in C's).  rank = 0 is plain CG; a selection that
+stops early (the residual variance fell below the jitter) leaves a preconditioner of that rank.
+
+Solver.  `_solve` runs block PCG on A X = B: every column has its own step lengths -- device tensors, no host round trip -- and all
+columns share one pg_kernel_matmul per iteration.  A column whose p^T A p or r^T z is zero (a zero or converged column) takes a zero
+step.  Every `check_every` iterations the host reads one number, the largest ||r_c|| / ||b_c|| over the columns (a zero column counts
+with ||b_c|| = 1), and stops at <= tol; the true residual b - A x is then formed once, and that is the figure reported.  Past max_iter:
+`NotConverged`, and the model stays dirty.
+
+Training is not served: the log-determinant needs its own estimator.  Train hyper-parameters with `VFE` on a Sparse_GP,
+or with MLE on an Exact_GP of a subset, and fit the exact posterior here.  Batched models, float32 and covariances longer than one
+pg_covspec are refused.
+"""
+from typing import Sequence
+
+import numpy as np
+import torch
+from numpy import ndarray
+from torch import Tensor
+
+from . import _lib
+from ._ops import JITTER, get_ops, pad_to
+from .covar import Covar, spec_of, terms
+from .gpr import _CHUNK, GPR, _checked, _lin_alg_error
+from .sparse import _prior_of, _stationary, select_inducing
+
+_RHS_BLOCK = 64      # test points whose variance columns one block solve carries
+_RHS_PAD = 128       # the GEMM core's column tile: every block of right-hand sides is a buffer of that many columns (or a multiple)
+CHECK_EVERY = 10     # iterations between two reads of the residual
+
+
+class NotConverged(torch.linalg.LinAlgError):
+    """The conjugate gradients did not reach the tolerance within max_iter iterations.  `iterations`: how many were taken;
+    `residual`: the largest ||r_c|| / ||b_c|| of the recurrence at that point."""
+
+    def __init__(self, iterations: int, residual: float, tol: float) -> None:
+        super().__init__("Iterative_GP: conjugate gradients stopped after %d iterations at relative residual %.3e (tol %.1e); raise "
+                         "max_iter or rank, or loosen tol" % (iterations, residual, tol))
+        self.iterations = int(iterations)
+        self.residual = float(residual)
+
+
+class Iterative_GP(GPR):
+    """Exact GP regression without the n x n matrix: x [n, d], y [n] float64, params as Exact_GP's.  rank: pivots of the
+    pivoted-Cholesky preconditioner (0: plain CG); tol: relative residual every solve is taken to; max_iter: iterations a solve may
+    take before it raises NotConverged.  After update(), `cg_info` holds iterations, residual (the true one) and rank of the last
+    solve."""
+
+    _matrix_free = True      # MLE / LOO refuse such a model: they need the factor
+
+    def __init__(self, x: Tensor, y: Tensor, cov: Covar, rank: int = 100, tol: float = 1e-8, max_iter: int = 1000) -> None:
+        super().__init__(x, y, cov)
+        if not (isinstance(rank, (int, np.integer)) and rank >= 0):
+            raise ValueError("Iterative_GP: rank must be a non-negative integer, got %r" % (rank,))
+        if not (tol > 0 and isinstance(max_iter, (int, np.integer)) and max_iter >= 1):
+            raise ValueError("Iterative_GP: tol must be positive and max_iter a positive integer")
+        self.rank, self.tol, self.max_iter = int(rank), float(tol), int(max_iter)
+        self._check_data()
+        passes, _ = spec_of(cov, x.shape[-1])
+        if len(passes) != 1:
+            raise NotImplementedError("Iterative_GP: covariances that need more than one pg_covspec pass are not supported")
+        self.params: Tensor = cov.init_params(x)
+        self._dev = None
+        self._dev_key = None
+        self._state = None
+        self.cg_info = None
+        self.need_upd = True
+
+    # ---- data -------------------------------------------------------------------------------
+    @property
+    def dtype(self):
+        return torch.float64
+
+    def _data_changed(self) -> None:
+        self._dev = None
+        self._state = None
+        self.need_upd = True
+
+    def _check_data(self) -> None:
+        x, y = self._x, self._y
+        for name, t in (("x", x), ("y", y)):
+            if t.dtype != torch.float64:
+                raise TypeError("Iterative_GP computes in float64 only (the solver's tolerance is below single precision); %s is %s"
+                                % (name, t.dtype))
+        if x.dim() != 2 or y.dim() != 1:
+            raise NotImplementedError("Iterative_GP: batched models are not supported (x [n, d], y [n])")
+        if y.shape[0] != x.shape[0]:
+            raise ValueError("Iterative_GP: x holds %d points, y %d values" % (x.shape[0], y.shape[0]))
+
+    def _device_data(self):
+        """(x, y) on the device, uploaded once per (tensor identity, version)."""
+        key = tuple(v for t in (self._x, self._y) for v in (id(t), t._version))
+        if self._dev is None or self._dev_key != key:
+            self._check_data()
+            ops = get_ops()
+            self._dev = tuple(ops.to_device(t, torch.float64) for t in (self._x, self._y))
+            self._dev_key = key
+            self._state = None
+            self.need_upd = True
+        return self._dev
+
+    def _hp_host(self) -> ndarray:
+        p = self.params
+        p = p.detach().cpu().numpy() if isinstance(p, Tensor) else np.asarray(p)
+        if p.dtype != np.float64:
+            raise TypeError("Iterative_GP computes in float64 only; params is %s" % p.dtype)
+        _, nhp = spec_of(self.cov, self._x.shape[-1])
+        assert p.shape[-1] == nhp
+        if p.reshape(-1, nhp).shape[0] != 1:
+            raise NotImplementedError("Iterative_GP: batched hyper-parameters are not supported")
+        return np.array(p.reshape(nhp), dtype=np.float64)
+
+    # ---- the preconditioner -----------------------------------------------------------------
+    def _preconditioner(self, ops, hp, hpd, spec, shift, xd):
+        """(L [n_pad, m_pad], the factor of C = shift I + L^T L, its workspace, m), or None for rank 0."""
+        n, d = xd.shape
+        tms, _, _ = terms(self.cov, d)
+        want = min(self.rank, n)
+        if want == 0 or not tms:
+            return None
+        piv = select_inducing(xd, self.cov, hp, want).index          # (one synchronisation: the count)
+        m = int(piv.shape[0])
+        if m == 0:
+            return None
+        zd = xd[piv].contiguous()
+        ma, npad = pad_to(m), pad_to(n)
+        info = torch.zeros(2, dtype=torch.int32, device=ops.device)
+        out = {}
+
+        def enqueue():
+            lu = ops.empty(ma, ma)
+            ops.kernel_build(spec, hpd, zd, None, lu, jitter=JITTER)       # k(z, z) + JITTER I, identity in the padding
+            invd = ops.empty(2, ops.potrf_worksize(ma, torch.float64))
+            ops.potrf(lu, invd[0], info[0:1])
+            li = ops.empty(ma, ma)
+            ops.trtri(lu, invd[0], li)
+            lmat = ops.empty(npad, ma)
+            for s in range(0, n, _CHUNK):                                  # L = k(x, z) Lu^-T, chunk by chunk straight into its rows
+                nc = min(_CHUNK, n - s)
+                rows = pad_to(nc)
+                kt = ops.empty(rows, ma)
+                ops.kernel_build(spec, hpd, xd[s: s + nc], zd, kt)         # zero in the padding: the rows behind n, the columns behind m
+                ops.trmm_lower_kt(li, kt, lmat[s: s + rows])
+            c = ops.empty(ma, ma)
+            ops.gemm_raw(_lib.GEMM_TN_64 if ma <= 2048 else _lib.GEMM_TN, ma, ma, npad, 1.0, lmat, lmat, 0.0, c)
+            dg = c.diagonal()
+            dg[:m].add_(shift)
+            dg[m:].fill_(1.0)
+            ops.potrf(c, invd[1], info[1:2])
+            out.update(L=lmat, C=c, invd=invd[1], m=m, ma=ma)
+
+        for st in _checked(enqueue, lambda: info.tolist()):
+            if st:
+                raise _lin_alg_error(st, " -- the pivots' covariance or the preconditioner's capacitance matrix")
+        return out
+
+    @staticmethod
+    def _apply_preconditioner(ops, pre, shift, r, z):
+        """z = P^-1 r on [n_pad, cols] buffers (cols a multiple of _RHS_PAD; zero rows and columns stay zero)."""
+        if pre is None:
+            z.copy_(r)
+            return
+        lmat, ma = pre["L"], pre["ma"]
+        npad, cols = r.shape
+        t = ops.empty(ma, cols)
+        ops.gemm_raw(_lib.GEMM_TN_64, ma, cols, npad, 1.0, lmat, r, 0.0, t)       # L^T r
+        u = ops.potrs(pre["C"], pre["invd"], t)                                    # C^-1 L^T r
+        z.copy_(r)
+        ops.gemm_raw(_lib.GEMM_NN, npad, cols, ma, -1.0, lmat, u, 1.0, z)          # r - L u
+        z.mul_(1.0 / shift)
+
+    # ---- the solver -------------------------------------------------------------------------
+    def _solve(self, ops, st, b, nrhs):
+        """X with A X = B for the first nrhs columns of the zero-padded buffer b [n_pad, cols]: (x buffer, iterations, true residual).
+        Raises NotConverged past max_iter."""
+        xd, hpd, spec, shift, pre = st["x"], st["hpd"], st["full_spec"], st["shift"], st["pre"]
+        n = xd.shape[0]
+        bv = b[:n, :nrhs]
+        work = st.get("work")
+        x = torch.zeros_like(b)
+        r = b.clone()
+        z = torch.zeros_like(b)
+        ap = torch.zeros_like(b)
+        xv, rv, zv, apv = x[:n, :nrhs], r[:n, :nrhs], z[:n, :nrhs], ap[:n, :nrhs]
+        self._apply_preconditioner(ops, pre, shift, r, z)
+        p = z.clone()
+        pv = p[:n, :nrhs]
+        rz = (rv * zv).sum(0)
+        bn = bv.norm(dim=0)
+        bn = torch.where(bn == 0, torch.ones_like(bn), bn)
+        zero = torch.zeros_like(rz)
+        it, res = 0, float("inf")
+        while it < self.max_iter:
+            ops.kernel_matmul(spec, hpd, xd, None, pv, out=apv, jitter=JITTER, work=work)
+            pap = (pv * apv).sum(0)
+            step = torch.where((pap != 0) & (rz != 0), rz / pap, zero)
+            xv.addcmul_(pv, step)
+            rv.addcmul_(apv, -step)
+            self._apply_preconditioner(ops, pre, shift, r, z)
+            rz_new = (rv * zv).sum(0)
+            beta = torch.where(rz != 0, rz_new / rz, zero)
+            pv.mul_(beta).add_(zv)
+            rz = rz_new
+            it += 1
+            if it % CHECK_EVERY == 0 or it == self.max_iter:
+                res = float((rv.norm(dim=0) / bn).max())                  # the one synchronisation per CHECK_EVERY iterations
+                if not res > self.tol:                                     # (a NaN residual ends the solve as well: it cannot improve)
+                    break
+        if not res <= self.tol:
+            raise NotConverged(it, res, self.tol)
+        ops.kernel_matmul(spec, hpd, xd, None, xv, out=apv, jitter=JITTER, work=work)
+        true = float(((bv - apv).norm(dim=0) / bn).max())
+        return x, it, true
+
+    # ---- fit --------------------------------------------------------------------------------
+    def update(self) -> None:
+        xd, yd = self._device_data()             # first: an in-place edit of x / y (version bump) marks the model dirty here
+        if not self.need_upd:
+            return None
+        self._state = None
+        ops = get_ops()
+        n, d = xd.shape
+        hp = self._hp_host()
+        (sp,), _ = spec_of(self.cov, d)
+        sig2, kdiag, _, _ = _prior_of(self.cov, d, hp)
+        shift = sig2 + JITTER
+        hpd = ops.to_device(torch.from_numpy(hp), torch.float64)
+        spec = _stationary(sp)
+        pre = self._preconditioner(ops, hp, hpd, spec, shift, xd)
+        size = ops.kernel_matmul_worksize(n, n, _RHS_PAD)
+        st = dict(x=xd, hpd=hpd, spec=spec, full_spec=sp, shift=shift, pre=pre, kss=kdiag + sig2,
+                  work=ops.empty(size) if size > 0 else None)
+        b = ops.zeros(pad_to(n), _RHS_PAD)
+        b[:n, 0] = yd
+        xs, its, res = self._solve(ops, st, b, 1)
+        st["alpha"] = xs[:n, 0].clone()
+        self.cg_info = dict(iterations=its, residual=res, rank=0 if pre is None else pre["m"])
+        self._state = st
+        self.need_upd = False
+        return None
+
+    @property
+    def alpha(self) -> Tensor:
+        """A^-1 y [n] of the fitted model, on x's device."""
+        self.update()
+        return self._state["alpha"].to(self._x.device)
+
+    # ---- prediction -------------------------------------------------------------------------
+    def predict(self, xp: Tensor, var: str = "full") -> Sequence[Tensor]:
+        """[mean, var | covariance | NotImplemented] of y* at xp [q, d]: the mean is one cross product against alpha (no q x n matrix);
+        the variances take the test points in blocks of _RHS_BLOCK, each a block solve A S = k(x, xp_b) at the model's tol."""
+        if torch.is_grad_enabled() and isinstance(xp, Tensor) and xp.requires_grad:
+            raise NotImplementedError("Iterative_GP.predict is not differentiable through autograd; use an Exact_GP for derivatives in "
+                                      "the test points")
+        if xp.dim() != 2 or xp.shape[1] != self._x.shape[1]:
+            raise NotImplementedError("Iterative_GP.predict: xp must be [q, %d] (no batches)" % self._x.shape[1])
+        if xp.dtype != torch.float64:
+            raise TypeError("Iterative_GP computes in float64 only; xp is %s" % xp.dtype)
+        ops = get_ops()
+        self.update()
+        st = self._state
+        xd, hpd, spec = st["x"], st["hpd"], st["spec"]
+        n = xd.shape[0]
+        npad = pad_to(n)
+        xpd = ops.to_device(xp, torch.float64)
+        q = xpd.shape[0]
+        want = var if var in ("full", "diag") else "none"
+        mean = ops.kernel_matmul(spec, hpd, xpd, xd, st["alpha"])
+        if want == "none":
+            return [mean.to(xp.device), NotImplemented]
+        blk = int(_RHS_BLOCK)
+        cols = pad_to(blk, _RHS_PAD)
+        blocks = [(s, min(blk, q - s)) for s in range(0, q, blk)]
+
+        def cross(s, qb):
+            ks = ops.empty(npad, cols)
+            ops.kernel_build(spec, hpd, xd, xpd[s: s + qb], ks)            # k(x, xp_b), zero in the padding
+            return ks
+
+        if want == "diag":
+            vr = ops.empty(q)
+            for s, qb in blocks:
+                ks = cross(s, qb)
+                sol, _, _ = self._solve(ops, st, ks, qb)
+                vr[s: s + qb] = st["kss"] - (ks[:n, :qb] * sol[:n, :qb]).sum(0)
+            return [mean.to(xp.device), vr.to(xp.device)]
+        qp = pad_to(q)
+        cov = ops.empty(qp, qp)
+        ops.kernel_build(st["full_spec"], hpd, xpd, None, cov)              # K** incl. sigma_n^2, identity in the padding
+        g = ops.empty(cols, cols)
+        for j, (s, qb) in enumerate(blocks):                                # the lower block triangle, column of blocks by column
+            ks = cross(s, qb)
+            sol, _, _ = self._solve(ops, st, ks, qb)
+            for s2, qb2 in blocks[j:]:
+                k2 = ks if s2 == s else cross(s2, qb2)
+                ops.gemm_raw(_lib.GEMM_TN_64, cols, cols, npad, 1.0, k2, sol, 0.0, g)      # k(x, xp_b2)^T S_b
+                cov[s2: s2 + qb2, s: s + qb].sub_(g[:qb2, :qb])
+        ops.symmetrize(cov, qp)                                             # the upper triangle is the mirror: exactly symmetric
+        return [mean.to(xp.device), cov[:q, :q].contiguous().to(xp.device)]
+
+    def predict_var(self, xp: Tensor, **kwargs: Tensor) -> Tensor:
+        return self.predict(xp, var="diag")[1]
+
+    def predict_covar(self, xp: Tensor, **kwargs: Tensor) -> Tensor:
+        return self.predict(xp, var="full")[1]

@@ -51,6 +51,13 @@ class Loss():
         self.model.set_params(torch.tensor(x))
 
 
+def _refuse_matrix_free(model, name):
+    """An Iterative_GP holds no factor: the log-determinant and the inverse these losses are made of do not exist there."""
+    if getattr(model, "_matrix_free", False):
+        raise NotImplementedError("%s needs the Cholesky factor, which %s never forms; train the hyper-parameters with VFE on a Sparse_GP "
+                                  "or with %s on an Exact_GP of a subset, then fit the exact posterior" % (name, type(model).__name__, name))
+
+
 class _MemoLoss(Loss):
     """A loss whose device evaluation (`_evaluate_device`) is memoised on parameters, data and covariance: what MLE and LOO share."""
 
@@ -103,6 +110,7 @@ class MLE(_MemoLoss):
     """Negative log marginal likelihood of the hyper-parameters (PyGPR/loss.py:31-128)."""
 
     def __init__(self, model: GPR) -> None:
+        _refuse_matrix_free(model, "MLE")
         super().__init__(model)
         self._bbuf = {}
         self.last_batched = False   # the last device evaluation took the experts-together path (tests / diagnostics)
@@ -240,6 +248,10 @@ class LOO(_MemoLoss):
     mirror of K^-1, one pass that scales it to S and takes p, q (pg_loo_weights), the n^3-flop product S S^T on the GEMM core (lower
     tiles), the rank-one fold (pg_loo_fold) and MLE's own contraction, pg_nlml_grad(S S^T + q q^T, p).  No third n x n buffer: c is
     taken from `m` = L^-1 first, S overwrites `a` = K^-1 in place, S S^T goes over `m`.  Single models only."""
+
+    def __init__(self, model: GPR) -> None:
+        _refuse_matrix_free(model, "LOO")
+        super().__init__(model)
 
     def _buffers(self, n_pad, dtype, nhp, n):
         key = (n_pad, dtype, nhp, n)
