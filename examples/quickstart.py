@@ -71,6 +71,17 @@ igp.set_params(gp.params)
 print("iterative vs exact GP: max |mean difference| %.2e after %d CG iterations" % (
     float((igp.predict(xs, var="none")[0] - mean).abs().max()), igp.cg_info["iterations"]))
 
+# ---- ... and trained there as well: the marginal likelihood and its gradient from 15 probe vectors (stochastic Lanczos quadrature on
+# the solver's own coefficients), a few CG steps from the untrained start.  The estimate is noisy: slq_info says by how much.
+igp.set_params(torch.tensor([1.0] + [1.0] * d + [0.1], dtype=torch.float64))
+sloss = PyGPR.Stochastic_MLE(igp, probes=15, seed=0)
+sopt = PyGPR.CG(sloss)
+sopt.args.update(maxiter=6, disp=False)
+sopt.minimize()
+print("stochastic NLML after %d evaluations: %.2f +- %.2f (exact at the same parameters: %.2f; MLE's optimum: %.2f)" % (
+    sopt.res.nfev, float(sloss.loss(igp.params.numpy())), sloss.slq_info["stderr"] / 2, float(loss.loss(igp.params.numpy())),
+    float(opt.res.fun)))
+
 # ---- scikit-learn facade
 sk = PyGPR.SK_WRAP(PyGPR.Exact_GP(x, y, cov))
 sk.model.set_params(gp.params)

@@ -9,6 +9,7 @@
 #include "sparse.h"
 #include "select.h"
 #include "kmatmul.h"
+#include "lowrank.h"
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -692,6 +693,30 @@ int pg_kernel_matmul(pg_handle h, int dtype, const pg_covspec* spec, const doubl
     NEED(work || pg_kmatmul_worksize_impl(nr, nc, nrhs) == 0, "this shape needs its workspace (pg_kernel_matmul_worksize)");
     return pg_kmatmul_impl(ST(stream), *spec, hp, (const double*)Xr, ldr, nr, (const double*)Xc, ldc, nc, d, sym, (const double*)V, ldv, nrhs,
                            jitter, (double*)OUT, ldo, (double*)work);
+}
+
+long pg_kernel_lowrank_grad_worksize(int nr, int nc, int r, int nhp) {
+    return (nr >= 0 && nc >= 0 && r >= 0 && nhp >= 0) ? pg_lowrank_grad_worksize_impl(nr, nc, r, nhp) : -1;
+}
+
+int pg_kernel_lowrank_grad(pg_handle h, int dtype, const pg_covspec* spec, const double* hp, const void* Xr, long ldr, int nr, const void* Xc,
+                           long ldc, int nc, int d, const void* U, long ldu, const void* V, long ldv, int r, double* grad, int accumulate,
+                           void* work, void* stream) {
+    JOIN(h, stream);
+    NEED(h && hp && grad, "null pointer");
+    NEED(dtype == PG_F64, "float64 only (dtype must be PG_F64)");
+    if (check_spec(spec, __func__)) return -1;      // (PG_KIND_SQDIST is refused: it is no covariance)
+    for (int c = 0; c < (spec->ncomp & ~PG_SPEC_PRODUCT); ++c) NEED(spec->off[c] >= 0, "negative offset in the covariance spec");
+    const int sym = (Xc == nullptr);
+    if (sym) { Xc = Xr; ldc = ldr; nc = nr; }
+    if (!(nr >= 0 && nc >= 0 && d >= 1 && d <= PG_MAX_DIM)) { pg_set_error("%s: bad shape (0 <= nr, nc; 1 <= d <= PG_MAX_DIM)", __func__); return -2; }
+    NEED(r >= 0 && r <= 64, "0 <= r <= 64 (split a larger rank and accumulate)");
+    NEED(ldr >= d && ldc >= d && ldu >= r && ldv >= r, "ldr, ldc >= d and ldu, ldv >= r");
+    const long size = pg_lowrank_grad_worksize_impl(nr, nc, r, 1);
+    NEED(size == 0 || (Xr && Xc && U && V), "null pointer");
+    NEED(size == 0 || work, "this shape needs its workspace (pg_kernel_lowrank_grad_worksize)");
+    return pg_lowrank_grad_impl(ST(stream), *spec, hp, (const double*)Xr, ldr, nr, (const double*)Xc, ldc, nc, d, sym, (const double*)U, ldu,
+                                (const double*)V, ldv, r, grad, accumulate, (double*)work);
 }
 
 int pg_randn(pg_handle h, int dtype, long seed, int stream_id, int row0, int rows, int cols, void* Z, long ldz, int rows_pad, int cols_pad,

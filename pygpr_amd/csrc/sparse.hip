@@ -205,6 +205,13 @@ __global__ __launch_bounds__(256) void pg_cross_grad_reduce_kernel(pg_covspec sp
     }
 }
 
+int pg_cross_grad_reduce(hipStream_t st, const pg_covspec& spec, const double* hp, const double* part, long nblk, int pw, int d, double* grad,
+                         int accumulate) {
+    hipLaunchKernelGGL(pg_cross_grad_reduce_kernel, dim3(pw), dim3(256), 0, st, spec, hp, part, nblk, pw, d, grad, accumulate);
+    PG_CHECK(hipGetLastError());
+    return 0;
+}
+
 static inline long cg_strips(int n) { return ((long)(n + ST_T - 1) / ST_T + ST_CH - 1) / ST_CH; }
 
 long pg_cross_grad_worksize_impl(int m, int n, int nhp) {
@@ -260,9 +267,7 @@ int pg_cross_grad_t(hipStream_t st, const pg_covspec& spec_in, const double* hp,
         if (rc) return rc;
     }
     // (m == 0 or n == 0: an empty sum -- the reduce alone zeroes the spec's entries, or leaves them when accumulating)
-    hipLaunchKernelGGL(pg_cross_grad_reduce_kernel, dim3(pw), dim3(256), 0, st, spec, hp, work, nblk, pw, d, grad, accumulate);
-    PG_CHECK(hipGetLastError());
-    return 0;
+    return pg_cross_grad_reduce(st, spec, hp, work, nblk, pw, d, grad, accumulate);
 }
 
 template int pg_cross_grad_t<double>(hipStream_t, const pg_covspec&, const double*, const double*, long, int, const double*, long, int, int,

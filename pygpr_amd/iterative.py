@@ -22,9 +22,10 @@ step.  Every `check_every` iterations the host reads one number, the largest ||r
 with ||b_c|| = 1), and stops at <= tol; the true residual b - A x is then formed once, and that is the figure reported.  Past max_iter:
 `NotConverged`, and the model stays dirty.
 
-Training is not served: the log-determinant needs its own estimator.  Train hyper-parameters with `VFE` on a Sparse_GP,
-or with MLE on an Exact_GP of a subset, and fit the exact posterior here.  Batched models, float32 and covariances longer than one
-pg_covspec are refused.
+Training.  MLE and LOO need the factor and refuse this model; `Stochastic_MLE` (pygpr_amd/stochastic.py) trains it through
+`CG(Stochastic_MLE(model))`: the log-determinant by stochastic Lanczos quadrature on the coefficients `_solve(..., record=True)` keeps,
+the gradient from the same probe solves through pg_kernel_lowrank_grad.  `VFE` on a Sparse_GP, or MLE on an Exact_GP of a subset, remain
+the cheaper ways to a starting point.  Batched models, float32 and covariances longer than one pg_covspec are refused.
 """
 from typing import Sequence
 
@@ -185,9 +186,12 @@ class Iterative_GP(GPR):
         z.mul_(1.0 / shift)
 
     # ---- the solver -------------------------------------------------------------------------
-    def _solve(self, ops, st, b, nrhs):
+    def _solve(self, ops, st, b, nrhs, record=False):
         """X with A X = B for the first nrhs columns of the zero-padded buffer b [n_pad, cols]: (x buffer, iterations, true residual).
-        Raises NotConverged past max_iter."""
+        Raises NotConverged past max_iter.  record: a fourth result, what the stochastic log-determinant reads from the recurrence --
+        `z0`, the first preconditioned residual P^-1 B (a device buffer like b), and on the host `step`, `beta` and `rz` [iterations, nrhs]
+        (the step lengths, the betas and r^T z after each step) with `rz0` [nrhs], r^T z before the first.  They are kept as device
+        tensors while the solve runs and come over in one transfer at its end."""
         xd, hpd, spec, shift, pre = st["x"], st["hpd"], st["full_spec"], st["shift"], st["pre"]
         n = xd.shape[0]
         bv = b[:n, :nrhs]
@@ -201,6 +205,8 @@ class Iterative_GP(GPR):
         p = z.clone()
         pv = p[:n, :nrhs]
         rz = (rv * zv).sum(0)
+        if record:
+            z0, rz0, steps, betas, rzs = z.clone(), rz, [], [], []
         bn = bv.norm(dim=0)
         bn = torch.where(bn == 0, torch.ones_like(bn), bn)
         zero = torch.zeros_like(rz)
@@ -217,6 +223,10 @@ class Iterative_GP(GPR):
             pv.mul_(beta).add_(zv)
             rz = rz_new
             it += 1
+            if record:
+                steps.append(step)
+                betas.append(beta)
+                rzs.append(rz_new)
             if it % CHECK_EVERY == 0 or it == self.max_iter:
                 res = float((rv.norm(dim=0) / bn).max())                  # the one synchronisation per CHECK_EVERY iterations
                 if not res > self.tol:                                     # (a NaN residual ends the solve as well: it cannot improve)
@@ -225,6 +235,9 @@ class Iterative_GP(GPR):
             raise NotConverged(it, res, self.tol)
         ops.kernel_matmul(spec, hpd, xd, None, xv, out=apv, jitter=JITTER, work=work)
         true = float(((bv - apv).norm(dim=0) / bn).max())
+        if record:
+            rec = torch.stack(steps + betas + rzs + [rz0]).cpu().numpy()
+            return x, it, true, dict(z0=z0, step=rec[:it], beta=rec[it: 2 * it], rz=rec[2 * it: 3 * it], rz0=rec[3 * it])
         return x, it, true
 
     # ---- fit --------------------------------------------------------------------------------

@@ -55,7 +55,8 @@ def _refuse_matrix_free(model, name):
     """An Iterative_GP holds no factor: the log-determinant and the inverse these losses are made of do not exist there."""
     if getattr(model, "_matrix_free", False):
         raise NotImplementedError("%s needs the Cholesky factor, which %s never forms; train the hyper-parameters with VFE on a Sparse_GP "
-                                  "or with %s on an Exact_GP of a subset, then fit the exact posterior" % (name, type(model).__name__, name))
+                                  "or with %s on an Exact_GP of a subset, then fit the exact posterior; Stochastic_MLE trains the model itself from "
+                                  "probe vectors" % (name, type(model).__name__, name))
 
 
 class _MemoLoss(Loss):
