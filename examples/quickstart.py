@@ -82,6 +82,14 @@ print("stochastic NLML after %d evaluations: %.2f +- %.2f (exact at the same par
     sopt.res.nfev, float(sloss.loss(igp.params.numpy())), sloss.slq_info["stderr"] / 2, float(loss.loss(igp.params.numpy())),
     float(opt.res.fun)))
 
+# ---- ... and sampled: posterior functions by pathwise conditioning -- random Fourier features for the prior, ONE block solve for all
+# samples, after which an evaluation anywhere is one cross product and one feature product (no further solve, nothing q x q)
+igp.set_params(gp.params)
+fs = igp.function_samples(n_samples=8, features=1024, seed=0)
+draws = fs(xs)                      # [8, q] draws of the latent function: the same eight functions wherever they are evaluated
+print("8 function samples (%d features, %d CG iterations): largest |sample mean - posterior mean| %.3f, largest sample sd %.3f" % (
+    fs.frequencies.shape[0], fs.cg_info["iterations"], float((draws.mean(0) - mean).abs().max()), float(draws.std(0).max())))
+
 # ---- scikit-learn facade
 sk = PyGPR.SK_WRAP(PyGPR.Exact_GP(x, y, cov))
 sk.model.set_params(gp.params)

@@ -416,6 +416,41 @@ class HipOps:
                    _p(v2), ld(v2, nrhs), nrhs, float(jitter), _p(o2), ld(o2, nrhs), _p(work), self._st())
         return out
 
+    # -- the random-feature product (include/pygpr_hip_feature.h) ----------------------------------
+    def feature_matmul_worksize(self, nr, nf, nrhs):
+        return int(self.lib.pg_feature_matmul_worksize(int(nr), int(nf), int(nrhs)))
+
+    def feature_matmul(self, x, nu, u, w, out=None, work=None):
+        """out[i][c] = sum_f cos(2 pi (x_i . nu_f + u_f)) w[f][c] without forming the features (pg_feature_matmul).  x [nr, d],
+        nu [nf, d] (cycles per unit), w [nf, nrhs] and out [nr, nrhs] float64 device tensors or views with unit stride along a row,
+        u [nf] (cycles) contiguous; a one-dimensional w counts as one column, and out comes back one-dimensional; out is allocated
+        when None.  work: feature_matmul_worksize doubles, allocated when None and needed."""
+        self._chk(work)
+        vec = w.dim() == 1
+        w2 = w.unsqueeze(1) if vec else w
+        nr, d = x.shape
+        nf = nu.shape[0]
+        nrhs = w2.shape[1]
+        if out is None:
+            out = self.empty(nr, dtype=torch.float64) if vec else self.empty(nr, nrhs, dtype=torch.float64)
+        o2 = out.unsqueeze(1) if out.dim() == 1 else out
+        for name, t, shape in (("x", x, (nr, d)), ("nu", nu, (nf, d)), ("w", w2, (nf, nrhs)), ("out", o2, (nr, nrhs))):
+            if not (t.is_cuda and t.dim() == 2 and tuple(t.shape) == shape and t.dtype == torch.float64 and (t.stride(1) == 1 or t.shape[1] <= 1)):
+                raise ValueError("feature_matmul needs %s %s float64 on the device, unit stride along a row" % (name, list(shape)))
+        if not (u.is_cuda and u.dim() == 1 and u.shape[0] == nf and u.dtype == torch.float64 and (nf <= 1 or u.stride(0) == 1)):
+            raise ValueError("feature_matmul needs u [%d] float64 on the device, contiguous" % nf)
+
+        def ld(t, width):      # (a matrix of one row or none has no row stride to speak of)
+            return max(int(t.stride(0)), width, 1) if t.shape[0] > 1 else max(width, 1)
+
+        size = self.feature_matmul_worksize(nr, nf, nrhs)
+        if work is None and size > 0:
+            work = self.empty(size, dtype=torch.float64)
+        assert size == 0 or (work.dtype == torch.float64 and work.numel() >= size)
+        self._call("pg_feature_matmul", PG_F64, _p(x), ld(x, d), nr, _p(nu), ld(nu, d), nf, d, _p(u), _p(w2), ld(w2, nrhs), nrhs, _p(o2),
+                   ld(o2, nrhs), _p(work), self._st())
+        return out
+
     # -- the low-rank gradient contraction (include/pygpr_hip_lowrank.h) --------------------------
     def kernel_lowrank_grad_worksize(self, nr, nc, r, nhp):
         return int(self.lib.pg_kernel_lowrank_grad_worksize(int(nr), int(nc), int(r), int(nhp)))

@@ -9,6 +9,7 @@
 #include "sparse.h"
 #include "select.h"
 #include "kmatmul.h"
+#include "fmatmul.h"
 #include "lowrank.h"
 #include <cstdarg>
 #include <cstdint>
@@ -693,6 +694,26 @@ int pg_kernel_matmul(pg_handle h, int dtype, const pg_covspec* spec, const doubl
     NEED(work || pg_kmatmul_worksize_impl(nr, nc, nrhs) == 0, "this shape needs its workspace (pg_kernel_matmul_worksize)");
     return pg_kmatmul_impl(ST(stream), *spec, hp, (const double*)Xr, ldr, nr, (const double*)Xc, ldc, nc, d, sym, (const double*)V, ldv, nrhs,
                            jitter, (double*)OUT, ldo, (double*)work);
+}
+
+long pg_feature_matmul_worksize(int nr, int nf, int nrhs) { return (nr >= 0 && nf >= 0 && nrhs >= 0) ? pg_fmatmul_worksize_impl(nr, nf, nrhs) : -1; }
+
+int pg_feature_matmul(pg_handle h, int dtype, const void* X, long ldx, int nr, const void* NU, long ldn, int nf, int d, const void* U,
+                      const void* W, long ldw, int nrhs, void* OUT, long ldo, void* work, void* stream) {
+    JOIN(h, stream);
+    NEED(h, "null pointer");
+    NEED(dtype == PG_F64, "float64 only (dtype must be PG_F64)");
+    if (!(nr >= 0 && nf >= 0 && nrhs >= 0 && d >= 1 && d <= PG_MAX_DIM)) {
+        pg_set_error("%s: bad shape (0 <= nr, nf, nrhs; 1 <= d <= PG_MAX_DIM)", __func__);
+        return -2;
+    }
+    if ((nrhs + 31) / 32 > 65535) { pg_set_error("%s: nrhs <= 32 * 65535", __func__); return -2; }
+    NEED(ldx >= d && ldn >= d && ldw >= nrhs && ldo >= nrhs, "ldx, ldn >= d and ldw, ldo >= nrhs");
+    if (nr == 0 || nrhs == 0) return 0;
+    NEED(X && OUT && (nf == 0 || (NU && U && W)), "null pointer");
+    NEED(work || pg_fmatmul_worksize_impl(nr, nf, nrhs) == 0, "this shape needs its workspace (pg_feature_matmul_worksize)");
+    return pg_fmatmul_impl(ST(stream), (const double*)X, ldx, nr, (const double*)NU, ldn, nf, d, (const double*)U, (const double*)W, ldw, nrhs,
+                           (double*)OUT, ldo, (double*)work);
 }
 
 long pg_kernel_lowrank_grad_worksize(int nr, int nc, int r, int nhp) {

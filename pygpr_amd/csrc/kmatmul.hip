@@ -18,32 +18,7 @@
 #include "kmatmul.h"
 #include <type_traits>
 
-#define MM_T 64          // tile edge: rows of OUT per workgroup, column points per step of the walk
-#define MM_PANEL 16      // right-hand sides of one matrix instruction
-#define MM_BLOCK 32      // right-hand sides of one pass over the pairs (two panels)
-#define MM_TARGET 512    // workgroups wanted before the column range is left whole: two per compute unit of a 256-CU part, a constant so
-                         // that the order of the sum depends on the shape alone
-#define MM_SEGMIN 4      // column tiles a segment holds at least
-
-struct MmPlan {
-    int tiles_r, tiles_c, nblk, nseg, tps;      // tps: column tiles per segment
-};
-static inline MmPlan mm_plan(int nr, int nc, int nrhs) {
-    MmPlan p;
-    p.tiles_r = (nr + MM_T - 1) / MM_T;
-    p.tiles_c = (nc + MM_T - 1) / MM_T;
-    p.nblk = (nrhs + MM_BLOCK - 1) / MM_BLOCK;
-    p.nseg = p.tiles_c > 0 ? 1 : 0;
-    p.tps = p.tiles_c;
-    const long wg = (long)p.tiles_r * p.nblk;
-    if (wg > 0 && wg < MM_TARGET && p.tiles_c >= 2 * MM_SEGMIN) {
-        const long want = (MM_TARGET + wg - 1) / wg;
-        const long s = std::min<long>(want, p.tiles_c / MM_SEGMIN);
-        p.tps = (int)((p.tiles_c + s - 1) / s);
-        p.nseg = (p.tiles_c + p.tps - 1) / p.tps;
-    }
-    return p;
-}
+// (the tile constants MM_* and the plan mm_plan are in kmatmul.h: fmatmul.hip walks the same way)
 
 // partial tiles: part[seg][blk][tiles_r * 64][MM_BLOCK]
 template <int DMAX, bool PER, bool PROD, int NB>
@@ -239,6 +214,16 @@ __global__ __launch_bounds__(256) void pg_kmatmul_fold_kernel(pg_covspec spec, c
         s += shift * V[i * ldv + c];
     }
     OUT[i * ldo + c] = s;
+}
+
+int pg_kmatmul_fold_plain(hipStream_t st, const MmPlan& p, const double* part, int nr, int nrhs, double* OUT, long ldo) {
+    const long ne = (long)nr * nrhs;
+    if (ne == 0) return 0;
+    pg_covspec none = {};      // (no shift: neither the spec nor hp is read)
+    hipLaunchKernelGGL(pg_kmatmul_fold_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, none, (const double*)nullptr, part, p.nseg,
+                       p.nblk, (long)p.tiles_r * MM_T, nr, nrhs, (const double*)nullptr, 0L, 0.0, 0, OUT, ldo);
+    PG_CHECK(hipGetLastError());
+    return 0;
 }
 
 long pg_kmatmul_worksize_impl(int nr, int nc, int nrhs) {

@@ -26,6 +26,9 @@ Training.  MLE and LOO need the factor and refuse this model; `Stochastic_MLE` (
 `CG(Stochastic_MLE(model))`: the log-determinant by stochastic Lanczos quadrature on the coefficients `_solve(..., record=True)` keeps,
 the gradient from the same probe solves through pg_kernel_lowrank_grad.  `VFE` on a Sparse_GP, or MLE on an Exact_GP of a subset, remain
 the cheaper ways to a starting point.  Batched models, float32 and covariances longer than one pg_covspec are refused.
+
+Sampling.  `function_samples` draws posterior functions by pathwise conditioning (pygpr_amd/pathwise.py): one block solve
+for all samples, then every evaluation is one cross product and one feature product.  A joint `sampler` stays refused.
 """
 from typing import Sequence
 
@@ -38,6 +41,7 @@ from . import _lib
 from ._ops import JITTER, get_ops, pad_to
 from .covar import Covar, spec_of, terms
 from .gpr import _CHUNK, GPR, _checked, _lin_alg_error
+from .pathwise import FunctionSamples, _check_count, _checked_terms, draw_function_samples
 from .sparse import _prior_of, _stationary, select_inducing
 
 _RHS_BLOCK = 64      # test points whose variance columns one block solve carries
@@ -186,12 +190,14 @@ class Iterative_GP(GPR):
         z.mul_(1.0 / shift)
 
     # ---- the solver -------------------------------------------------------------------------
-    def _solve(self, ops, st, b, nrhs, record=False):
+    def _solve(self, ops, st, b, nrhs, record=False, freeze=False):
         """X with A X = B for the first nrhs columns of the zero-padded buffer b [n_pad, cols]: (x buffer, iterations, true residual).
         Raises NotConverged past max_iter.  record: a fourth result, what the stochastic log-determinant reads from the recurrence --
         `z0`, the first preconditioned residual P^-1 B (a device buffer like b), and on the host `step`, `beta` and `rz` [iterations, nrhs]
         (the step lengths, the betas and r^T z after each step) with `rz0` [nrhs], r^T z before the first.  They are kept as device
-        tensors while the solve runs and come over in one transfer at its end."""
+        tensors while the solve runs and come over in one transfer at its end.  freeze: a column that meets the tolerance at a check
+        takes zero steps from then on, so what it converges to does not depend on the columns it shares the solve with (function
+        samples: sample s is the same whatever n_samples)."""
         xd, hpd, spec, shift, pre = st["x"], st["hpd"], st["full_spec"], st["shift"], st["pre"]
         n = xd.shape[0]
         bv = b[:n, :nrhs]
@@ -210,11 +216,14 @@ class Iterative_GP(GPR):
         bn = bv.norm(dim=0)
         bn = torch.where(bn == 0, torch.ones_like(bn), bn)
         zero = torch.zeros_like(rz)
+        active = torch.ones_like(rz, dtype=torch.bool) if freeze else None
         it, res = 0, float("inf")
         while it < self.max_iter:
             ops.kernel_matmul(spec, hpd, xd, None, pv, out=apv, jitter=JITTER, work=work)
             pap = (pv * apv).sum(0)
             step = torch.where((pap != 0) & (rz != 0), rz / pap, zero)
+            if freeze:
+                step = torch.where(active, step, zero)
             xv.addcmul_(pv, step)
             rv.addcmul_(apv, -step)
             self._apply_preconditioner(ops, pre, shift, r, z)
@@ -228,7 +237,10 @@ class Iterative_GP(GPR):
                 betas.append(beta)
                 rzs.append(rz_new)
             if it % CHECK_EVERY == 0 or it == self.max_iter:
-                res = float((rv.norm(dim=0) / bn).max())                  # the one synchronisation per CHECK_EVERY iterations
+                resc = rv.norm(dim=0) / bn
+                if freeze:                                                 # (a frozen column's r stands still: it keeps the figure it froze at)
+                    active = active & (resc > self.tol)
+                res = float(resc.max())                                    # the one synchronisation per CHECK_EVERY iterations
                 if not res > self.tol:                                     # (a NaN residual ends the solve as well: it cannot improve)
                     break
         if not res <= self.tol:
@@ -325,6 +337,52 @@ class Iterative_GP(GPR):
                 cov[s2: s2 + qb2, s: s + qb].sub_(g[:qb2, :qb])
         ops.symmetrize(cov, qp)                                             # the upper triangle is the mirror: exactly symmetric
         return [mean.to(xp.device), cov[:q, :q].contiguous().to(xp.device)]
+
+    # ---- function samples -------------------------------------------------------------------
+    def function_samples(self, n_samples: int = 1, features: int = 1024, seed: int = 0, prior: bool = False) -> FunctionSamples:
+        """n_samples functions drawn from the posterior by pathwise conditioning (pygpr_amd/pathwise.py), as a FunctionSamples to
+        evaluate at any points: `features` frequencies per stationary component (twice as many features), all randomness from pg_randn
+        at `seed`.  The samples are of the latent function (no observation noise).  One fit and, for every _RHS_BLOCK samples, one block
+        solve at the model's tol -- each of the block's full width, whatever n_samples, and with columns frozen once converged, so that
+        sample s does not depend on n_samples; NotConverged and a failed preconditioner propagate as from update().  prior=True: draws
+        of the prior at the current params -- no fit, no solve."""
+        if not isinstance(seed, (int, np.integer)):
+            raise ValueError("Iterative_GP.function_samples: the seed must be an integer, got %r" % (seed,))
+        _check_count("Iterative_GP.function_samples: n_samples", n_samples)
+        _check_count("Iterative_GP.function_samples: features", features)
+        _checked_terms(self.cov, self._x.shape[1])      # a kind without a spectral law is refused before anything is fitted
+        if prior:      # (of x only the width is read)
+            return draw_function_samples(self.cov, self._hp_host(), self._x, None, 0.0, n_samples, features, seed, None)
+        ops = get_ops()
+        self.update()
+        st = self._state
+        xd, yd = self._device_data()
+        n = xd.shape[0]
+        npad = pad_to(n)
+
+        def solve(b):
+            blk = int(_RHS_BLOCK)
+            cols = pad_to(blk, _RHS_PAD)
+            v = torch.empty_like(b)
+            its, worst, count = 0, 0.0, 0
+            for s in range(0, b.shape[1], blk):
+                sb = min(blk, b.shape[1] - s)
+                buf = ops.zeros(npad, cols)
+                buf[:n, :sb] = b[:, s: s + sb]
+                sol, it, res = self._solve(ops, st, buf, blk, freeze=True)      # the full width: zero columns take zero steps
+                v[:, s: s + sb] = sol[:n, :sb]
+                its, worst, count = max(its, it), max(worst, res), count + 1
+            return v, dict(solves=count, iterations=its, residual=worst, rank=self.cg_info["rank"])
+
+        return draw_function_samples(self.cov, self._hp_host(), xd, yd, st["shift"], n_samples, features, seed, solve)
+
+    def sample(self, xp: Tensor, n_samples: int = 1, seed: int = 0, features: int = 1024, prior: bool = False) -> Tensor:
+        """function_samples(n_samples, features, seed, prior)(xp): [n_samples, q] draws of the latent function at xp [q, d]."""
+        return self.function_samples(n_samples, features, seed, prior)(xp)
+
+    def sampler(self, xp: Tensor, **kwargs):
+        raise NotImplementedError("Iterative_GP has no joint sampler (a q x q factor is what this model cannot afford); draw functions "
+                                  "with function_samples(...) and evaluate them at xp")
 
     def predict_var(self, xp: Tensor, **kwargs: Tensor) -> Tensor:
         return self.predict(xp, var="diag")[1]
