@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
+#include <type_traits>
 #include "pygpr_hip.h"
 
 #define PG_TILE 128      // GEMM block tile and Cholesky leaf size
@@ -64,6 +65,31 @@ void pg_set_error(const char* fmt, ...);
             return -100;                                                            \
         }                                                                           \
     } while (0)
+
+// f(std::integral_constant<int, DMAX>{}) for the smallest DMAX of 4, 8, 16, 32, 64 that holds d: the compile-time dimension of the
+// direct-difference kernels (their tiles and unrolled loops are DMAX wide, zero for k >= d).  MAXD = 16: callers that never see more.
+template <int MAXD = 64, class F> static inline int pg_with_dmax(int d, F f) {
+    if (d <= 4) return f(std::integral_constant<int, 4>{});
+    if (d <= 8) return f(std::integral_constant<int, 8>{});
+    if constexpr (MAXD > 16) {
+        if (d <= 16) return f(std::integral_constant<int, 16>{});
+        if (d <= 32) return f(std::integral_constant<int, 32>{});
+        return f(std::integral_constant<int, 64>{});
+    } else {
+        return f(std::integral_constant<int, 16>{});
+    }
+}
+
+// The dynamic-LDS limit of one kernel instantiation, set once per process before its first launch: beyond the 64 KB a kernel gets
+// without opting in, a launch fails.  `bytes` is the most that instantiation is ever launched with.
+template <auto Kernel> static inline int pg_lds_opt_in(size_t bytes) {
+    static bool done = false;
+    if (!done) {
+        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        done = true;
+    }
+    return 0;
+}
 
 // MFMA wrapper: one 16x16x4 step, D = A(16x4) B(4x16) + C.
 // lane l supplies A[l&15][l>>4] and B[l>>4][l&15] for both dtypes

@@ -19,6 +19,10 @@
 #include "fmatmul.h"
 #include <type_traits>
 
+// LDS of pg_fmatmul_kernel in bytes: two feature tiles with their phase row, two panels of W -- the carve-up below
+template <int DMAX, int NB> static constexpr size_t fmatmul_lds_bytes() {
+    return (size_t)(2 * MM_T * (DMAX + 1) + 2 * NB * MM_T * MM_PANEL) * sizeof(double);
+}
 // partial tiles: part[seg][blk][tiles_r * 64][MM_BLOCK]
 template <int DMAX, int NB>
 __global__ __launch_bounds__(256) void pg_fmatmul_kernel(const double* __restrict__ X, long ldx, int nr, const double* __restrict__ NU, long ldn,
@@ -148,13 +152,9 @@ long pg_fmatmul_worksize_impl(int nr, int nf, int nrhs) { return pg_kmatmul_work
 template <int DMAX, int NB>
 static int launch_fmatmul(hipStream_t st, const MmPlan& p, const double* X, long ldx, int nr, const double* NU, long ldn, int nf, int d,
                           const double* U, const double* W, long ldw, int nrhs, double* OUT, long ldo, double* part) {
-    const size_t lds = (size_t)(2 * MM_T * (DMAX + 1) + 2 * NB * MM_T * MM_PANEL) * sizeof(double);
-    static bool attr_done = false;
-    if (!attr_done) {   // DMAX = 32 with two panels and DMAX = 64 need more than the 64 KB a kernel gets without opting in
-        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_fmatmul_kernel<DMAX, NB>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds));
-        attr_done = true;
-    }
+    constexpr size_t lds = fmatmul_lds_bytes<DMAX, NB>();
+    // DMAX = 32 with two panels and DMAX = 64 need more than the 64 KB a kernel gets without opting in
+    if (int rc = pg_lds_opt_in<pg_fmatmul_kernel<DMAX, NB>>(lds)) return rc;
     hipLaunchKernelGGL((pg_fmatmul_kernel<DMAX, NB>), dim3(p.tiles_r, p.nseg, p.nblk), dim3(256), lds, st, X, ldx, nr, NU, ldn, nf, d, U, W, ldw,
                        nrhs, OUT, ldo, part, p.tps, p.tiles_c);
     PG_CHECK(hipGetLastError());
@@ -167,18 +167,12 @@ int pg_fmatmul_impl(hipStream_t st, const double* X, long ldx, int nr, const dou
     const MmPlan p = mm_plan(nr, nf, nrhs);
     double* part = p.nseg > 1 ? work : nullptr;
     if (p.nseg > 0) {
-        auto go = [&](auto nb_c) {
-            constexpr int NB = decltype(nb_c)::value;
-#define FM_GO(DMAX) return launch_fmatmul<DMAX, NB>(st, p, X, ldx, nr, NU, ldn, nf, d, U, W, ldw, nrhs, OUT, ldo, part)
-            if (d <= 4) FM_GO(4);
-            if (d <= 8) FM_GO(8);
-            if (d <= 16) FM_GO(16);
-            if (d <= 32) FM_GO(32);
-            FM_GO(64);
-#undef FM_GO
-        };
-        // one panel when sixteen columns hold every right-hand side, two otherwise
-        const int rc = nrhs <= MM_PANEL ? go(std::integral_constant<int, 1>{}) : go(std::integral_constant<int, 2>{});
+        const int rc = mm_with_nb(nrhs, [&](auto nb_c) {
+            return pg_with_dmax(d, [&](auto dmax_c) {
+                return launch_fmatmul<decltype(dmax_c)::value, decltype(nb_c)::value>(st, p, X, ldx, nr, NU, ldn, nf, d, U, W, ldw, nrhs, OUT, ldo,
+                                                                                      part);
+            });
+        });
         if (rc) return rc;
     }
     if (p.nseg != 1) return pg_kmatmul_fold_plain(st, p, part, nr, nrhs, OUT, ldo);      // the segments in their order, or the empty sum

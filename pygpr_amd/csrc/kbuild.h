@@ -12,6 +12,13 @@ static inline bool pg_spec_strip(const pg_covspec& in, pg_covspec& out) {
     out.ncomp = in.ncomp & ~PG_SPEC_PRODUCT;
     return (in.ncomp & PG_SPEC_PRODUCT) != 0;
 }
+// f(PER, PROD) as std::bool_constant for a stripped spec: a periodic component takes an instantiation of its own (the other kinds'
+// kernels compile exactly as they did without it), a product the one that carries every kind.
+template <class F> static inline int pg_with_kinds(const pg_covspec& spec, bool prod, F f) {
+    bool per = false;
+    for (int c = 0; c < spec.ncomp; ++c) per = per || spec.kind[c] == PG_KIND_PERIODIC;
+    return prod ? f(std::true_type{}, std::true_type{}) : (per ? f(std::true_type{}, std::false_type{}) : f(std::false_type{}, std::false_type{}));
+}
 template <typename T>
 int pg_kbuild(hipStream_t st, const pg_covspec& spec, const double* hp, const T* Xr, long ldr, int nr,
               const T* Xc, long ldc, int nc, int d, int symmetric, int lower_only, int accumulate, double jitter, T* K,

@@ -30,6 +30,7 @@
 // element's weight by the other components' values, and every entry of c follows from the code of the sum.
 #include "kbuild.h"
 #include "kfun.h"
+#include "kpair.h"
 #include "kmfma.h"
 #include <cstdlib>
 #include <type_traits>
@@ -287,12 +288,7 @@ __global__ __launch_bounds__(256) void pg_kbuild_kernel(pg_covspec spec, const d
     };
     load_cols(tcs);
     stage_points(xr, Xr, ldr, nr, tr * KT, d, tid, scale, fast ? 2.0 : 1.0);
-    for (int idx = tid; idx < spec.ncomp * d; idx += 256) {
-        const int c = idx / d, k = idx % d;
-        const double l = hp[spec.off[c] + 1 + k];
-        l2[idx] = (T)(l * l);
-        if constexpr (PER) ipl[idx] = spec.kind[c] == PG_KIND_PERIODIC ? (T)(1.0 / hp[spec.off[c] + d + 1 + k]) : (T)0;
-    }
+    pair_stage_hp<T, PER>(spec, hp, d, d, d, l2, ipl, tid, 256);
     if (tid < spec.ncomp) {
         const double sg = hp[spec.off[tid]];
         sg2[tid] = (T)(sg * sg);
@@ -376,12 +372,8 @@ template <typename T> static constexpr size_t kb_lds_bytes(int d, bool mirror, b
 // One instantiation of pg_kbuild_kernel: its dynamic-LDS limit once, then the launch.
 template <typename T, bool MIRROR, int NPF, bool FAST, bool PER, bool PROD, typename... Args>
 static int kb_launch(dim3 grid, size_t lds, hipStream_t st, Args... args) {
-    static bool attr_done = false;
-    if (!attr_done) {   // large d passes the 64 KB a kernel gets without opting in (134 KB for the mirrored fp64 build at d = 64)
-        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_kbuild_kernel<T, MIRROR, NPF, FAST, PER, PROD>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kb_lds_bytes<T>(PG_MAX_DIM, true, PER)));
-        attr_done = true;
-    }
+    // large d passes the 64 KB a kernel gets without opting in (134 KB for the mirrored fp64 build at d = 64)
+    if (int rc = pg_lds_opt_in<pg_kbuild_kernel<T, MIRROR, NPF, FAST, PER, PROD>>(kb_lds_bytes<T>(PG_MAX_DIM, true, PER))) return rc;
     hipLaunchKernelGGL((pg_kbuild_kernel<T, MIRROR, NPF, FAST, PER, PROD>), grid, dim3(256), lds, st, args...);
     PG_CHECK(hipGetLastError());
     return 0;
@@ -651,7 +643,14 @@ template int pg_centres<float>(hipStream_t, const float*, long, int, const float
 // (elem_value) -- explicitly, never as K / k_cp: a factor that underflows gives 0.  Every entry of cp (sigma, length scales, shape,
 // periods) then follows from the code of the sum; the trace of W for the noise entries takes the unmodified weight, and the reduce
 // kernel's scales are unchanged.
+// The per-pair body, elem_value and the fold below are also the text of pg_cross_grad_kernel (sparse.hip) and pg_lowrank_grad_kernel
+// (lowrank.hip), to be changed together: as shared functions they are compiled to other registers.
 #define GCH 4
+// LDS of pg_grad_kernel in bytes: red, the row tile and two column tiles, l2 (and ipl) -- the carve-up below
+template <typename T, int DMAX, bool PER> static constexpr size_t grad_lds_bytes() {
+    return 4 * kind_nparam(PER ? PG_KIND_PERIODIC : PG_KIND_RQ, DMAX) * sizeof(double) +
+           (size_t)(3 * KT * DMAX + (PER ? 2 : 1) * PG_MAX_COMP * DMAX) * sizeof(T);
+}
 template <typename T, int DMAX, bool PER = false, bool PROD = false>
 __global__ __launch_bounds__(256) void pg_grad_kernel(pg_covspec spec, const double* __restrict__ hp,
                                                       const T* __restrict__ X, long ldx, int n, int d,
@@ -680,15 +679,11 @@ __global__ __launch_bounds__(256) void pg_grad_kernel(pg_covspec spec, const dou
         const int gr = tr * KT + p;
         xr[k * KT + p] = (k < d && gr < n) ? X[(long)gr * ldx + k] : (T)0;
     }
-    for (int idx = tid; idx < spec.ncomp * DMAX; idx += 256) {
-        const int c = idx / DMAX, k = idx % DMAX;
-        const double l = (k < d) ? hp[spec.off[c] + 1 + k] : 0.0;
-        l2[idx] = (T)(l * l);
-        if constexpr (PER) ipl[idx] = (k < d && spec.kind[c] == PG_KIND_PERIODIC) ? (T)(1.0 / hp[spec.off[c] + d + 1 + k]) : (T)0;
-    }
+    pair_stage_hp<T, PER>(spec, hp, d, DMAX, DMAX, l2, ipl, tid, 256);
     for (int idx = tid; idx < nhp; idx += 256) part[(long)blk * nhp + idx] = 0.0;
     static_assert(!PROD || PER, "a product takes the instantiation that carries every kind");
-    // PROD: component c's value at (row, this lane's column) of the point tile xb
+    // PROD: component c's value at (row, this lane's column) of the point tile xb.  kpair.h's pair_value written out: taking it moved the
+    // d > 16 product instantiations of this kernel to more scratch memory
     auto elem_value = [&](int c, int row, const T* xb) -> T {
         const T* lc = l2 + c * DMAX;
         const int kind = spec.kind[c];
@@ -857,22 +852,13 @@ __global__ __launch_bounds__(256) void pg_grad_reduce_kernel(pg_covspec spec, co
         double scale = 0.0;
         bool mine = false;   // entries of children that are not in this spec belong to another pass of a long Compose
         for (int c = 0; c < spec.ncomp; ++c) {
-            const int o = spec.off[c];
-            if (p == o) { scale = 0.5 * 2.0 / hp[o]; mine = true; }       // dK/dsigma = 2K/sigma
-            else if (p > o && p <= o + d) {
-                const double hc = kind_hcoef(spec.kind[c]);      // SE: -2 l_k D_k^2 K, Matern: coef base l_k D_k^2
-                scale = hc * hp[p];
-                // the matrix-pipe contraction summed (l_k D_k)^2: -l_k S = -S' / l_k (l_k = 0: S' = 0 and the derivative is 0)
-                if (presc) scale = hp[p] != 0.0 ? hc / hp[p] : 0.0;
-                mine = true;
-            } else if (spec.kind[c] == PG_KIND_RQ && p == o + d + 1) {
-                scale = 0.5 * 2.0 * hp[p];      // dK/dalpha = 2 alpha K fs (the partial sums hold sum W K fs)
-                mine = true;
-            } else if (spec.kind[c] == PG_KIND_PERIODIC && p > o + d && p <= o + 2 * d) {
-                const double l = hp[p - d];     // dK/dp_k = K l_k^2 sin(2 pi t_k) pi t_k / p_k (the partial sums hold sum W K sin(2 pi t_k) t_k)
-                scale = 0.5 * l * l * PG_PI / hp[p];
-                mine = true;
-            }
+            bool hit = false;
+            const double sc = 0.5 * kind_entry_scale(spec, hp, c, p, d, hit);      // the NLML's 1/2
+            if (!hit) continue;
+            scale = sc;
+            mine = true;
+            // the matrix-pipe contraction summed (l_k D_k)^2: -l_k S = -S' / l_k (l_k = 0: S' = 0 and the derivative is 0)
+            if (presc && p > spec.off[c] && p <= spec.off[c] + d) scale = hp[p] != 0.0 ? kind_hcoef(spec.kind[c]) / hp[p] : 0.0;
         }
         for (int i = 0; i < spec.nnoise; ++i)
             if (p == spec.noise_off[i]) { scale = 0.5 * 2.0 * hp[p]; mine = true; }   // dK/dsigma_n = 2 sigma_n I
@@ -883,14 +869,8 @@ __global__ __launch_bounds__(256) void pg_grad_reduce_kernel(pg_covspec spec, co
 template <typename T, int DMAX, bool PER, bool PROD>
 static int launch_grad(hipStream_t st, const pg_covspec& spec, const double* hp, const T* X, long ldx, int n,
                        int d, const T* Kinv, long ldk, const T* alpha, double* part, int nhp, int tiles, const GradBatch& gb, int nexp) {
-    const size_t lds = (size_t)(3 * KT * DMAX + (PER ? 2 : 1) * PG_MAX_COMP * DMAX) * sizeof(T) +
-                       4 * kind_nparam(PER ? PG_KIND_PERIODIC : PG_KIND_RQ, DMAX) * sizeof(double);
-    static bool attr_done = false;
-    if (!attr_done) {   // d > 32 needs more than the 64 KB a kernel gets without opting in
-        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_grad_kernel<T, DMAX, PER, PROD>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_done = true;
-    }
+    constexpr size_t lds = grad_lds_bytes<T, DMAX, PER>();
+    if (int rc = pg_lds_opt_in<pg_grad_kernel<T, DMAX, PER, PROD>>(lds)) return rc;   // d > 32 needs more than the 64 KB a kernel gets without opting in
     hipLaunchKernelGGL((pg_grad_kernel<T, DMAX, PER, PROD>), dim3((tiles + GCH - 1) / GCH, tiles, nexp), dim3(256), lds, st, spec, hp, X, ldx,
                        n, d, Kinv, ldk, alpha, part, nhp, gb);
     PG_CHECK(hipGetLastError());
@@ -921,18 +901,14 @@ int pg_nlml_grad_t(hipStream_t st, const pg_covspec& spec_in, const double* hp, 
         PG_CHECK(hipGetLastError());
         return 0;
     }
-    bool per = false;      // a periodic component: pg_grad_kernel's own instantiation (never the matrix pipe: the whitelist above)
-    for (int c = 0; c < spec.ncomp; ++c) per = per || spec.kind[c] == PG_KIND_PERIODIC;
-    auto go = [&](auto per_c, auto prod_c) {
-        constexpr bool P = decltype(per_c)::value, Q = decltype(prod_c)::value;
-        if (d <= 4) return launch_grad<T, 4, P, Q>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
-        if (d <= 8) return launch_grad<T, 8, P, Q>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
-        if (d <= 16) return launch_grad<T, 16, P, Q>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
-        if (d <= 32) return launch_grad<T, 32, P, Q>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
-        return launch_grad<T, 64, P, Q>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, work, nhp, tiles, gb, nexp);
-    };
     if (d > PG_MAX_DIM) { pg_set_error("pg_nlml_grad: d=%d > %d", d, PG_MAX_DIM); return -2; }
-    rc = prod ? go(std::true_type{}, std::true_type{}) : (per ? go(std::true_type{}, std::false_type{}) : go(std::false_type{}, std::false_type{}));
+    // (a periodic component never takes the matrix pipe: the whitelist above)
+    rc = pg_with_kinds(spec, prod, [&](auto per_c, auto prod_c) {
+        return pg_with_dmax(d, [&](auto dmax_c) {
+            return launch_grad<T, decltype(dmax_c)::value, decltype(per_c)::value, decltype(prod_c)::value>(st, spec, hp, X, ldx, n, d, Kinv, ldk,
+                                                                                                            alpha, work, nhp, tiles, gb, nexp);
+        });
+    });
     if (rc) return rc;
     hipLaunchKernelGGL(pg_grad_reduce_kernel, dim3(nhp, 1, nexp), dim3(256), 0, st, spec, hp, work, tiles * ((tiles + GCH - 1) / GCH), nhp,
                        d, grad, 0, gb);

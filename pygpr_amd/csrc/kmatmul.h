@@ -36,6 +36,11 @@ static inline MmPlan mm_plan(int nr, int nc, int nrhs) {
     return p;
 }
 
+// one panel when sixteen columns hold every right-hand side, two otherwise: f(std::integral_constant<int, NB>{})
+template <class F> static inline int mm_with_nb(int nrhs, F f) {
+    return nrhs <= MM_PANEL ? f(std::integral_constant<int, 1>{}) : f(std::integral_constant<int, 2>{});
+}
+
 // OUT[i][c] = sum_{seg < p.nseg} part[seg][c / 32][i][c % 32] for i < nr, c < nrhs, the segments in their order (nseg = 0: zeros);
 // part is laid out [nseg][nblk][tiles_r * 64][MM_BLOCK] as the product kernels write it
 int pg_kmatmul_fold_plain(hipStream_t st, const MmPlan& p, const double* part, int nr, int nrhs, double* OUT, long ldo);

@@ -10,16 +10,21 @@
 //   row point   a lane evaluates every one of its pairs against the SAME row point i0 + c16: its coordinates live in registers
 //   column tile 64 points k-major in LDS ([k][64], sparse.hip's layout: the 16 lanes of one g read one word as a broadcast) and the
 //               64 x 16 panels of V beside them, double-buffered; the next tile travels global -> registers while this one is computed
-//   pair        kfun.h's forms from direct differences, as pg_kernel_cross_grad and pg_greedy_select evaluate them
+//   pair        kfun.h's forms from direct differences, four pairs interleaved (kpair.h's pair_sq is one pair at a time: not taken here)
 // Bound by fp64 VALU issue on the pair evaluation: the product adds four matrix instructions per sixteen-column
 // panel to four evaluations of some fifty fp64 operations each.
 #include "kfun.h"
+#include "kpair.h"
 #include "kbuild.h"
 #include "kmatmul.h"
 #include <type_traits>
 
 // (the tile constants MM_* and the plan mm_plan are in kmatmul.h: fmatmul.hip walks the same way)
 
+// LDS of pg_kmatmul_kernel in bytes: two point tiles, two panels of V, l2 (and ipl), cpar -- the carve-up below
+template <int DMAX, bool PER, int NB> static constexpr size_t kmatmul_lds_bytes() {
+    return (size_t)(2 * MM_T * DMAX + 2 * NB * MM_T * MM_PANEL + (PER ? 2 : 1) * PG_MAX_COMP * DMAX + 4 * PG_MAX_COMP) * sizeof(double);
+}
 // partial tiles: part[seg][blk][tiles_r * 64][MM_BLOCK]
 template <int DMAX, bool PER, bool PROD, int NB>
 __global__ __launch_bounds__(256) void pg_kmatmul_kernel(pg_covspec spec, const double* __restrict__ hp, const double* __restrict__ Xr, long ldr,
@@ -41,12 +46,7 @@ __global__ __launch_bounds__(256) void pg_kmatmul_kernel(pg_covspec spec, const 
     double* l2 = vt + 2 * NB * MM_T * MM_PANEL;                 // [ncomp][DMAX] squared inverse length scales, zero for k >= d
     double* ipl = l2 + PG_MAX_COMP * DMAX;                      // PER: [ncomp][DMAX] reciprocal periods, zero for k >= d / other kinds
     double* cpar = ipl + (PER ? PG_MAX_COMP * DMAX : 0);        // [ncomp][4]: sigma^2, the squared shape, its reciprocal
-    for (int idx = tid; idx < spec.ncomp * DMAX; idx += 256) {
-        const int c = idx / DMAX, k = idx % DMAX;
-        const double l = (k < d) ? hp[spec.off[c] + 1 + k] : 0.0;
-        l2[idx] = l * l;
-        if constexpr (PER) ipl[idx] = (k < d && spec.kind[c] == PG_KIND_PERIODIC) ? 1.0 / hp[spec.off[c] + d + 1 + k] : 0.0;
-    }
+    pair_stage_hp<double, PER>(spec, hp, d, DMAX, DMAX, l2, ipl, tid, 256);
     if (tid < spec.ncomp) {
         const double sg = hp[spec.off[tid]], sh = kind_shape2(spec, hp, tid, d);
         cpar[4 * tid] = sg * sg;
@@ -235,13 +235,8 @@ template <int DMAX, bool PER, bool PROD, int NB>
 static int launch_kmatmul(hipStream_t st, const MmPlan& p, const pg_covspec& spec, const double* hp, const double* Xr, long ldr, int nr,
                           const double* Xc, long ldc, int nc, int d, const double* V, long ldv, int nrhs, double jitter, int sym, double* OUT,
                           long ldo, double* part) {
-    const size_t lds = (size_t)(2 * MM_T * DMAX + 2 * NB * MM_T * MM_PANEL + (PER ? 2 : 1) * PG_MAX_COMP * DMAX + 4 * PG_MAX_COMP) * sizeof(double);
-    static bool attr_done = false;
-    if (!attr_done) {   // d > 32 needs more than the 64 KB a kernel gets without opting in
-        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_kmatmul_kernel<DMAX, PER, PROD, NB>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_done = true;
-    }
+    constexpr size_t lds = kmatmul_lds_bytes<DMAX, PER, NB>();
+    if (int rc = pg_lds_opt_in<pg_kmatmul_kernel<DMAX, PER, PROD, NB>>(lds)) return rc;   // d > 32 needs more than the 64 KB a kernel gets without opting in
     hipLaunchKernelGGL((pg_kmatmul_kernel<DMAX, PER, PROD, NB>), dim3(p.tiles_r, p.nseg, p.nblk), dim3(256), lds, st, spec, hp, Xr, ldr, nr, Xc,
                        ldc, nc, d, V, ldv, nrhs, jitter, sym, OUT, ldo, part, p.tps, p.tiles_c);
     PG_CHECK(hipGetLastError());
@@ -256,25 +251,14 @@ int pg_kmatmul_impl(hipStream_t st, const pg_covspec& spec_in, const double* hp,
     const MmPlan p = mm_plan(nr, nc, nrhs);
     double* part = p.nseg > 1 ? work : nullptr;
     if (p.nseg > 0) {
-        bool per = false;      // a periodic component: an instantiation of its own, as in pg_kernel_cross_grad
-        for (int c = 0; c < spec.ncomp; ++c) per = per || spec.kind[c] == PG_KIND_PERIODIC;
-        auto go = [&](auto per_c, auto prod_c, auto nb_c) {
-            constexpr bool P = decltype(per_c)::value, Q = decltype(prod_c)::value;
-            constexpr int NB = decltype(nb_c)::value;
-#define MM_GO(DMAX) return launch_kmatmul<DMAX, P, Q, NB>(st, p, spec, hp, Xr, ldr, nr, Xc, ldc, nc, d, V, ldv, nrhs, jitter, sym, OUT, ldo, part)
-            if (d <= 4) MM_GO(4);
-            if (d <= 8) MM_GO(8);
-            if (d <= 16) MM_GO(16);
-            if (d <= 32) MM_GO(32);
-            MM_GO(64);
-#undef MM_GO
-        };
-        auto kinds = [&](auto nb_c) {
-            return prod ? go(std::true_type{}, std::true_type{}, nb_c)
-                        : (per ? go(std::true_type{}, std::false_type{}, nb_c) : go(std::false_type{}, std::false_type{}, nb_c));
-        };
-        // one panel when sixteen columns hold every right-hand side, two otherwise
-        const int rc = nrhs <= MM_PANEL ? kinds(std::integral_constant<int, 1>{}) : kinds(std::integral_constant<int, 2>{});
+        const int rc = mm_with_nb(nrhs, [&](auto nb_c) {
+            return pg_with_kinds(spec, prod, [&](auto per_c, auto prod_c) {
+                return pg_with_dmax(d, [&](auto dmax_c) {
+                    return launch_kmatmul<decltype(dmax_c)::value, decltype(per_c)::value, decltype(prod_c)::value, decltype(nb_c)::value>(
+                        st, p, spec, hp, Xr, ldr, nr, Xc, ldc, nc, d, V, ldv, nrhs, jitter, sym, OUT, ldo, part);
+                });
+            });
+        });
         if (rc) return rc;
     }
     if (p.nseg != 1) {      // the segments in their order, or the empty sum

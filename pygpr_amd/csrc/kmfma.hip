@@ -268,17 +268,13 @@ int pg_kbuild_mfma(hipStream_t st, const pg_covspec& spec, const double* hp, con
     }
 #define KB_ARGS st, spec, hp, Xr, ldr, nr, Xc, ldc, nc, d, symmetric, jitter, K, ldk, c0, c1, S, strips, nexp, eX, ehp, eK, eXr
 #define KB_KIND(DP, KIND) return mirror ? kb_mfma_launch<T, DP, KIND, true>(KB_ARGS) : kb_mfma_launch<T, DP, KIND, false>(KB_ARGS)
-#define KB_GO(DP)                                                                                                          \
-    do {                                                                                                                   \
-        if (kind == PG_KIND_RBF) KB_KIND(DP, PG_KIND_RBF);                                                                 \
-        if (kind == PG_KIND_MATERN52) KB_KIND(DP, PG_KIND_MATERN52);                                                       \
-        if (kind == PG_KIND_RQ) KB_KIND(DP, PG_KIND_RQ);                                                                   \
-        KB_KIND(DP, PG_KIND_MATERN32);                                                                                     \
-    } while (0)
-    if (d <= 4) KB_GO(4);
-    if (d <= 8) KB_GO(8);
-    KB_GO(16);
-#undef KB_GO
+    return pg_with_dmax<16>(d, [&](auto dp_c) {      // the matrix-pipe bodies stop at d = 16
+        constexpr int DP = decltype(dp_c)::value;
+        if (kind == PG_KIND_RBF) KB_KIND(DP, PG_KIND_RBF);
+        if (kind == PG_KIND_MATERN52) KB_KIND(DP, PG_KIND_MATERN52);
+        if (kind == PG_KIND_RQ) KB_KIND(DP, PG_KIND_RQ);
+        KB_KIND(DP, PG_KIND_MATERN32);
+    });
 #undef KB_KIND
 #undef KB_ARGS
 }
@@ -581,17 +577,13 @@ int pg_grad_mfma(hipStream_t st, const pg_covspec& spec, const double* hp, const
         return -2;
     }
 #define GR_KIND(DP, KIND) return grad_mfma_launch<T, DP, KIND>(st, spec, hp, X, ldx, n, d, Kinv, ldk, alpha, part, nhp, tiles, gb, nexp, gch)
-#define GR_GO(DP)                                                                                                                          \
-    do {                                                                                                                                   \
-        if (kind == PG_KIND_RBF) GR_KIND(DP, PG_KIND_RBF);                                                                                 \
-        if (kind == PG_KIND_MATERN52) GR_KIND(DP, PG_KIND_MATERN52);                                                                       \
-        if (kind == PG_KIND_RQ) GR_KIND(DP, PG_KIND_RQ);                                                                                   \
-        GR_KIND(DP, PG_KIND_MATERN32);                                                                                                     \
-    } while (0)
-    if (d <= 4) GR_GO(4);
-    if (d <= 8) GR_GO(8);
-    GR_GO(16);
-#undef GR_GO
+    return pg_with_dmax<16>(d, [&](auto dp_c) {      // the matrix-pipe bodies stop at d = 16
+        constexpr int DP = decltype(dp_c)::value;
+        if (kind == PG_KIND_RBF) GR_KIND(DP, PG_KIND_RBF);
+        if (kind == PG_KIND_MATERN52) GR_KIND(DP, PG_KIND_MATERN52);
+        if (kind == PG_KIND_RQ) GR_KIND(DP, PG_KIND_RQ);
+        GR_KIND(DP, PG_KIND_MATERN32);
+    });
 #undef GR_KIND
 }
 template int pg_grad_mfma<double>(hipStream_t, const pg_covspec&, const double*, const double*, long, int, int, const double*, long, const double*,

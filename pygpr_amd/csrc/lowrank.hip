@@ -1,10 +1,11 @@
 // The matrix-free hyper-parameter contraction against a low-rank weight (include/pygpr_hip_lowrank.h):
 //   grad[p] (+)= sum_{i, j} (sum_{t < r} U[i][t] V[j][t]) dk(xr_i, xc_j)/dtheta_p
-// pg_kernel_cross_grad (sparse.hip) without its weight matrix.  kmatmul.hip's pattern with the roles turned once more: there a 16 x 16
+// The contraction of pg_kernel_cross_grad (sparse.hip) with the weight formed on the fly.  kmatmul.hip's pattern with the roles turned once more: there a 16 x 16
 // block of covariance values is the A operand of a product; here the 16 x 16 block of W = U V^T is the RESULT of r / 4 steps of
 // v_mfma_f64_16x16x4_f64 on the factor panels, A[i][k] = U[i0 + c16][t0 + g] and B[k][j] = V[j0 + c16][t0 + g], and arrives in the
 // accumulator layout: register q of lane (g = lane >> 4, c16 = lane & 15) holds W[i0 + g + 4 q][j0 + c16].  The pair derivatives are
-// evaluated right there, one weight register against one pair, and folded into per-lane accumulators as pg_cross_grad_kernel does.
+// evaluated right there, one weight register against one pair, and folded into per-lane accumulators: the per-pair body and the fold
+// are pg_cross_grad_kernel's text (see sparse.hip's header on why three kernels carry it), the product rule's factor is kpair.h's.
 //   workgroup   256 threads own one tile of 64 column points and a segment of the row tiles; wave w owns columns 16 w .. 16 w + 15
 //   column      a lane evaluates every one of its pairs against the SAME column point j0 + c16: its coordinates live in registers;
 //               the 64-row panels of V (and of U in the symmetric form) of the column tile sit in LDS for the whole walk
@@ -17,6 +18,7 @@
 // fit the LDS beside a 64-dimensional point tile); every pass has slot rows of its own and the one reduce folds them all.
 // Bound by fp64 VALU issue on the pair evaluation, like pg_kernel_matmul.
 #include "kfun.h"
+#include "kpair.h"
 #include "kbuild.h"
 #include "sparse.h"
 #include "lowrank.h"
@@ -49,6 +51,12 @@ static inline LrPlan lr_plan(int nr, int nc, int r) {
     return p;
 }
 
+// LDS of pg_lowrank_grad_kernel in bytes with rp factor columns staged: red, the row tile (d > 16: and the column tile), l2 (and ipl),
+// four panels -- the carve-up below
+template <int DMAX, bool PER> static constexpr size_t lowrank_lds_bytes(int rp) {
+    return (size_t)(4 * kind_nparam(PER ? PG_KIND_PERIODIC : PG_KIND_RQ, DMAX) + (DMAX <= 16 ? 1 : 2) * LR_T * DMAX +
+                    (PER ? 2 : 1) * PG_MAX_COMP * DMAX + 4 * rp * LR_PS) * sizeof(double);
+}
 // slot rows: part[(seg * tiles_c + tc)][pw], the layout of pg_cross_grad_kernel's
 template <int DMAX, bool PER, bool PROD>
 __global__ __launch_bounds__(256) void pg_lowrank_grad_kernel(pg_covspec spec, const double* __restrict__ hp, const double* __restrict__ Xr, long ldr,
@@ -75,12 +83,7 @@ __global__ __launch_bounds__(256) void pg_lowrank_grad_kernel(pg_covspec spec, c
     double* uc = ur + rp * LR_PS;                                   // symmetric form: U of the column tile
     double* vr = uc + rp * LR_PS;                                   // ... and V of the row tile
     double* xcl = vr + rp * LR_PS;                                  // d > 16: the column points' tile [DMAX][64]
-    for (int idx = tid; idx < spec.ncomp * DMAX; idx += 256) {
-        const int c = idx / DMAX, k = idx % DMAX;
-        const double l = (k < d) ? hp[spec.off[c] + 1 + k] : 0.0;
-        l2[idx] = l * l;
-        if constexpr (PER) ipl[idx] = (k < d && spec.kind[c] == PG_KIND_PERIODIC) ? 1.0 / hp[spec.off[c] + d + 1 + k] : 0.0;
-    }
+    pair_stage_hp<double, PER>(spec, hp, d, DMAX, DMAX, l2, ipl, tid, 256);
     // a 64-row panel of F (global rows first .. first + 63 of `rows`, factor columns t0 .. t0 + rc - 1) -> LDS [t][LR_PS], zero behind the
     // rows and the columns; every address read is an element of the operand (clamped): gaps are not read
     auto stage_panel = [&](double* dst, const double* __restrict__ F, long ldf, int first, int rows) {
@@ -116,30 +119,6 @@ __global__ __launch_bounds__(256) void pg_lowrank_grad_kernel(pg_covspec spec, c
         else return xcj[k * LR_T];
     };
 
-    // PROD: component c's value at (row, this lane's column)
-    auto elem_value = [&](int c, int row) -> double {
-        const double* lc = l2 + c * DMAX;
-        const int kind = spec.kind[c];
-        const double sg = hp[spec.off[c]];
-        const double sig2 = sg * sg;
-        double sq = 0.0;
-        if (kind == PG_KIND_PERIODIC) {
-            const double* ipc = ipl + c * DMAX;
-#pragma unroll
-            for (int k = 0; k < DMAX; ++k) sq += lc[k] * per_sin2<double>((xr[k * LR_T + row] - cj(k)) * ipc[k]);
-            return kind_value<double, PG_KIND_RBF>(sig2, sq);
-        }
-#pragma unroll
-        for (int k = 0; k < DMAX; ++k) {
-            const double df = xr[k * LR_T + row] - cj(k);
-            sq += lc[k] * df * df;
-        }
-        if (kind == PG_KIND_RBF) return kind_value<double, PG_KIND_RBF>(sig2, sq);
-        const double sh = kind_shape2(spec, hp, c, d);
-        double kt, bt, ft;
-        matern_val<double>(kind, sig2, sq, kt, bt, sh, 1.0 / sh, ft);
-        return kt;
-    };
 
     for (int cp = 0; cp < spec.ncomp; ++cp) {
         const int o = spec.off[cp];
@@ -181,8 +160,9 @@ __global__ __launch_bounds__(256) void pg_lowrank_grad_kernel(pg_covspec spec, c
                     const int row = i0 + g + 4 * q;
                     double w = q == 0 ? wq[0] : (q == 1 ? wq[1] : (q == 2 ? wq[2] : wq[3]));
                     if constexpr (PROD) {      // the product rule: the others' values weigh this component's element
+                        auto xa = [&](int k) { return xr[k * LR_T + row]; };
                         for (int c2 = 0; c2 < spec.ncomp; ++c2)
-                            if (c2 != cp) w *= elem_value(c2, row);
+                            if (c2 != cp) w *= pair_value<double, DMAX>(spec, hp, c2, d, l2 + c2 * DMAX, ipl + c2 * DMAX, xa, cj);
                     }
                     if constexpr (PER) {
                         if (kind == PG_KIND_PERIODIC) {      // (padding coordinates: l^2 = 1 / p = 0, so t = 0 and both terms vanish)
@@ -261,21 +241,14 @@ template <int DMAX, bool PER, bool PROD>
 static int launch_lowrank_grad(hipStream_t st, const LrPlan& p, const pg_covspec& spec, const double* hp, const double* Xr, long ldr, int nr,
                                const double* Xc, long ldc, int nc, int d, const double* U, long ldu, const double* V, long ldv, int r, int sym,
                                double* part, int pw) {
-    auto lds_of = [&](int rp) {
-        return (size_t)(4 * kind_nparam(PER ? PG_KIND_PERIODIC : PG_KIND_RQ, DMAX) + (DMAX <= 16 ? 1 : 2) * LR_T * DMAX + (PER ? 2 : 1) * PG_MAX_COMP * DMAX +
-                        4 * rp * LR_PS) * sizeof(double);
-    };
-    static bool attr_done = false;
-    if (!attr_done) {   // the panels of a full pass need more than the 64 KB a kernel gets without opting in
-        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_lowrank_grad_kernel<DMAX, PER, PROD>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_of(LR_RC)));
-        attr_done = true;
-    }
+    // the panels of a full pass need more than the 64 KB a kernel gets without opting in
+    if (int rc = pg_lds_opt_in<pg_lowrank_grad_kernel<DMAX, PER, PROD>>(lowrank_lds_bytes<DMAX, PER>(LR_RC))) return rc;
     const long per_chunk = (long)p.nseg * p.tiles_c;
     for (int ch = 0; ch < p.nchunk; ++ch) {      // passes over the factor columns, each into slot rows of its own
         const int t0 = ch * LR_RC, rc = std::min(LR_RC, r - t0);
-        hipLaunchKernelGGL((pg_lowrank_grad_kernel<DMAX, PER, PROD>), dim3(p.tiles_c, p.nseg), dim3(256), lds_of((rc + 3) & ~3), st, spec, hp, Xr,
-                           ldr, nr, Xc, ldc, nc, d, U, ldu, V, ldv, t0, rc, sym, part + ch * per_chunk * pw, pw, p.tps, p.tiles_r);
+        const size_t lds = lowrank_lds_bytes<DMAX, PER>((rc + 3) & ~3);
+        hipLaunchKernelGGL((pg_lowrank_grad_kernel<DMAX, PER, PROD>), dim3(p.tiles_c, p.nseg), dim3(256), lds, st, spec, hp, Xr, ldr, nr, Xc, ldc,
+                           nc, d, U, ldu, V, ldv, t0, rc, sym, part + ch * per_chunk * pw, pw, p.tps, p.tiles_r);
         PG_CHECK(hipGetLastError());
     }
     return 0;
@@ -290,19 +263,12 @@ int pg_lowrank_grad_impl(hipStream_t st, const pg_covspec& spec_in, const double
     if (pw == 0) return 0;                            // no stationary component: no entry is this call's
     const LrPlan p = lr_plan(nr, nc, r);
     if (p.nblk > 0) {
-        bool per = false;      // a periodic component: an instantiation of its own, as in pg_kernel_cross_grad
-        for (int c = 0; c < spec.ncomp; ++c) per = per || spec.kind[c] == PG_KIND_PERIODIC;
-        auto go = [&](auto per_c, auto prod_c) {
-            constexpr bool P = decltype(per_c)::value, Q = decltype(prod_c)::value;
-#define LR_GO(DMAX) return launch_lowrank_grad<DMAX, P, Q>(st, p, spec, hp, Xr, ldr, nr, Xc, ldc, nc, d, U, ldu, V, ldv, r, sym, work, pw)
-            if (d <= 4) LR_GO(4);
-            if (d <= 8) LR_GO(8);
-            if (d <= 16) LR_GO(16);
-            if (d <= 32) LR_GO(32);
-            LR_GO(64);
-#undef LR_GO
-        };
-        const int rc = prod ? go(std::true_type{}, std::true_type{}) : (per ? go(std::true_type{}, std::false_type{}) : go(std::false_type{}, std::false_type{}));
+        const int rc = pg_with_kinds(spec, prod, [&](auto per_c, auto prod_c) {
+            return pg_with_dmax(d, [&](auto dmax_c) {
+                return launch_lowrank_grad<decltype(dmax_c)::value, decltype(per_c)::value, decltype(prod_c)::value>(
+                    st, p, spec, hp, Xr, ldr, nr, Xc, ldc, nc, d, U, ldu, V, ldv, r, sym, work, pw);
+            });
+        });
         if (rc) return rc;
     }
     // (r == 0 or an empty point set: an empty sum -- the reduce alone zeroes the spec's entries, or leaves them when accumulating)

@@ -6,12 +6,14 @@
 //            wave reads two points per lane, 1 KB of consecutive words per column
 //   step     one workgroup per 128 points, four waves: wave w takes the columns t = w, w + 4, ... of the inner product (eight loads in
 //            flight per lane), the four partial sums meet in LDS in wave order, then one thread per point evaluates k from direct
-//            differences (kfun.h, the forms of sparse.hip), stores l_i and the residual, and the workgroup writes its (max, index, sum)
+//            differences (kfun.h; sel_value: kpair.h's pair_value with loops to the run-time d), stores l_i and the residual, and the
+//            workgroup writes its (max, index, sum)
 //   fold     one workgroup folds the partials (tie: lowest index; a NaN is never a maximum; sums in a fixed order), records piv[j],
 //            trace[j] and count, tests the next pivot against the floor and gathers its row of the factor for the next step
 // The steps are ordinary launches on one stream: no flags, no spinning, no atomics.  All m_max steps are enqueued at once; after the
 // stop the remaining launches see the stop word and return.
 #include "kfun.h"
+#include "kpair.h"
 #include "kbuild.h"
 #include "select.h"
 #include <climits>
@@ -81,7 +83,8 @@ __global__ __launch_bounds__(SEL_WG) void pg_select_init_kernel(pg_covspec spec,
     sel_partials(v, vi, s, w.pmax, w.pidx, w.psum);
 }
 
-// component c at (x_i, the pivot): sparse.hip's elem_value on a point in global memory and the pivot in LDS
+// component c at (x_i, the pivot): kpair.h's pair_value on a point in global memory and the pivot in LDS, with loops to the run-time d
+// (one kernel for every dimension: the step is bound by the factor's traffic, not by these d operations per point)
 __device__ __forceinline__ double sel_value(const pg_covspec& spec, const double* __restrict__ hp, int c, int d, const double* __restrict__ xi,
                                             const double* xp, const double* lc, const double* ipc) {
     const int kind = spec.kind[c];
@@ -115,12 +118,7 @@ __global__ __launch_bounds__(SEL_WG) void pg_select_step_kernel(pg_covspec spec,
     const int p = (int)w.state[SEL_PIVOT];
     const double rp = w.state[SEL_RP];
     for (int k = tid; k < d; k += SEL_WG) xp[k] = X[(long)p * ldx + k];
-    for (int idx = tid; idx < spec.ncomp * d; idx += SEL_WG) {
-        const int c = idx / d, k = idx % d;
-        const double l = hp[spec.off[c] + 1 + k];
-        l2[c * PG_MAX_DIM + k] = l * l;
-        ipl[c * PG_MAX_DIM + k] = spec.kind[c] == PG_KIND_PERIODIC ? 1.0 / hp[spec.off[c] + d + 1 + k] : 0.0;
-    }
+    pair_stage_hp<double, true>(spec, hp, d, d, PG_MAX_DIM, l2, ipl, tid, SEL_WG);
     // sum_{t < j, t = wave mod 4} L[t][i] L[t][p] for the lane's two points (n odd: the last lane's second point is padding, read and dropped)
     const long i0 = (long)blockIdx.x * SEL_PTS + 2 * lane;
     double ax = 0.0, ay = 0.0;

@@ -2,12 +2,15 @@
 //   grad[p] (+)= sum_{i < m, j < n} W_ij dk(z_i, x_j)/dtheta_p
 // for every parameter of the spec's stationary components.  pg_grad_kernel (kbuild.hip) on two point sets: the weight is a matrix the
 // caller hands over instead of K^-1 - alpha alpha^T on the lower triangle, so there is no diagonal, no doubling and no noise trace, and
-// the grid is the full rectangle of 64 x 64 tiles.  The per-pair forms are kfun.h's, from direct differences; the slots of a child in
-// the fold and the scales of the reduce follow pg_grad_kernel / pg_grad_reduce_kernel (without the 1/2 of the NLML).
+// the grid is the full rectangle of 64 x 64 tiles.  The per-pair forms are kfun.h's, from direct differences; staging and the reduce's
+// scales are kpair.h's (without the 1/2 of the NLML).  The per-pair body and the fold into a child's slots are written out here as in
+// pg_grad_kernel (kbuild.hip) and pg_lowrank_grad_kernel (lowrank.hip): the same text three times, to be changed together -- as one
+// shared function it is compiled to other registers.
 // HBM-bound on W: one 8-byte weight per pair is read once, one wave reads one 64-wide row of a tile per step (512 contiguous bytes in
 // fp64, 256 in fp32), both point tiles sit in LDS k-major ([k][64]: the 64 lanes of a wave read 64 consecutive words, every wave reads
 // the row point as a broadcast).  No matrix-pipe body.
 #include "kfun.h"
+#include "kpair.h"
 #include "kbuild.h"
 #include "sparse.h"
 #include <type_traits>
@@ -15,6 +18,10 @@
 #define ST_T 64      // tile edge
 #define ST_CH 4      // column tiles one workgroup walks with its accumulators in registers (pg_grad_kernel's strip)
 
+// LDS of pg_cross_grad_kernel in bytes: red, the row tile and two column tiles, l2 (and ipl) -- the carve-up below
+template <typename T, int DMAX, bool PER> static constexpr size_t cross_grad_lds_bytes() {
+    return 4 * kind_nparam(PER ? PG_KIND_PERIODIC : PG_KIND_RQ, DMAX) * sizeof(double) + (size_t)(3 * ST_T * DMAX + (PER ? 2 : 1) * PG_MAX_COMP * DMAX) * sizeof(T);
+}
 template <typename T, int DMAX, bool PER, bool PROD>
 __global__ __launch_bounds__(256) void pg_cross_grad_kernel(pg_covspec spec, const double* __restrict__ hp, const T* __restrict__ Z, long ldz,
                                                             int m, const T* __restrict__ X, long ldx, int n, int d,
@@ -36,13 +43,9 @@ __global__ __launch_bounds__(256) void pg_cross_grad_kernel(pg_covspec spec, con
         const int gr = tr * ST_T + p;
         xr[k * ST_T + p] = (k < d && gr < m) ? Z[(long)gr * ldz + k] : (T)0;
     }
-    for (int idx = tid; idx < spec.ncomp * DMAX; idx += 256) {
-        const int c = idx / DMAX, k = idx % DMAX;
-        const double l = (k < d) ? hp[spec.off[c] + 1 + k] : 0.0;
-        l2[idx] = (T)(l * l);
-        if constexpr (PER) ipl[idx] = (k < d && spec.kind[c] == PG_KIND_PERIODIC) ? (T)(1.0 / hp[spec.off[c] + d + 1 + k]) : (T)0;
-    }
-    // PROD: component c's value at (row, this lane's column) of the point tile xb
+    pair_stage_hp<T, PER>(spec, hp, d, DMAX, DMAX, l2, ipl, tid, 256);
+    // PROD: component c's value at (row, this lane's column) of the point tile xb.  kpair.h's pair_value written out: taking it moved the
+    // d > 16 product instantiations of this kernel to more scratch memory
     auto elem_value = [&](int c, int row, const T* xb) -> T {
         const T* lc = l2 + c * DMAX;
         const int kind = spec.kind[c];
@@ -183,15 +186,9 @@ __global__ __launch_bounds__(256) void pg_cross_grad_reduce_kernel(pg_covspec sp
     double scale = 0.0;
     bool mine = false;
     for (int c = 0; c < spec.ncomp; ++c) {
-        const int o = spec.off[c];
-        if (p == o) { scale = 2.0 / hp[o]; mine = true; }       // dK/dsigma = 2K/sigma
-        else if (p > o && p <= o + d) { scale = 2.0 * kind_hcoef(spec.kind[c]) * hp[p]; mine = true; }      // coef base l_k D_k^2
-        else if (spec.kind[c] == PG_KIND_RQ && p == o + d + 1) { scale = 2.0 * hp[p]; mine = true; }        // dK/dalpha = 2 alpha K fs
-        else if (spec.kind[c] == PG_KIND_PERIODIC && p > o + d && p <= o + 2 * d) {
-            const double l = hp[p - d];     // dK/dp_k = K l_k^2 sin(2 pi t_k) pi t_k / p_k
-            scale = l * l * PG_PI / hp[p];
-            mine = true;
-        }
+        bool hit = false;
+        const double sc = kind_entry_scale(spec, hp, c, p, d, hit);
+        if (hit) { scale = sc; mine = true; }
     }
     if (!mine) return;
     double s = 0.0;
@@ -229,14 +226,8 @@ int pg_cross_grad_extent(const pg_covspec& spec_in, int d) {
 template <typename T, int DMAX, bool PER, bool PROD>
 static int launch_cross_grad(hipStream_t st, const pg_covspec& spec, const double* hp, const T* Z, long ldz, int m, const T* X, long ldx, int n,
                              int d, const T* W, long ldw, double* part, int pw, int tiles_m, int tiles_n) {
-    const size_t lds = (size_t)(3 * ST_T * DMAX + (PER ? 2 : 1) * PG_MAX_COMP * DMAX) * sizeof(T) +
-                       4 * kind_nparam(PER ? PG_KIND_PERIODIC : PG_KIND_RQ, DMAX) * sizeof(double);
-    static bool attr_done = false;
-    if (!attr_done) {   // d > 32 needs more than the 64 KB a kernel gets without opting in
-        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_cross_grad_kernel<T, DMAX, PER, PROD>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_done = true;
-    }
+    constexpr size_t lds = cross_grad_lds_bytes<T, DMAX, PER>();
+    if (int rc = pg_lds_opt_in<pg_cross_grad_kernel<T, DMAX, PER, PROD>>(lds)) return rc;   // d > 32 needs more than the 64 KB a kernel gets without opting in
     hipLaunchKernelGGL((pg_cross_grad_kernel<T, DMAX, PER, PROD>), dim3((tiles_n + ST_CH - 1) / ST_CH, tiles_m), dim3(256), lds, st, spec, hp, Z,
                        ldz, m, X, ldx, n, d, W, ldw, part, pw, tiles_n);
     PG_CHECK(hipGetLastError());
@@ -253,17 +244,12 @@ int pg_cross_grad_t(hipStream_t st, const pg_covspec& spec_in, const double* hp,
     const int tiles_m = (m + ST_T - 1) / ST_T, tiles_n = (n + ST_T - 1) / ST_T;
     const long nblk = (long)tiles_m * cg_strips(n);
     if (nblk > 0) {
-        bool per = false;      // a periodic component: an instantiation of its own, as in pg_grad_kernel
-        for (int c = 0; c < spec.ncomp; ++c) per = per || spec.kind[c] == PG_KIND_PERIODIC;
-        auto go = [&](auto per_c, auto prod_c) {
-            constexpr bool P = decltype(per_c)::value, Q = decltype(prod_c)::value;
-            if (d <= 4) return launch_cross_grad<T, 4, P, Q>(st, spec, hp, Z, ldz, m, X, ldx, n, d, W, ldw, work, pw, tiles_m, tiles_n);
-            if (d <= 8) return launch_cross_grad<T, 8, P, Q>(st, spec, hp, Z, ldz, m, X, ldx, n, d, W, ldw, work, pw, tiles_m, tiles_n);
-            if (d <= 16) return launch_cross_grad<T, 16, P, Q>(st, spec, hp, Z, ldz, m, X, ldx, n, d, W, ldw, work, pw, tiles_m, tiles_n);
-            if (d <= 32) return launch_cross_grad<T, 32, P, Q>(st, spec, hp, Z, ldz, m, X, ldx, n, d, W, ldw, work, pw, tiles_m, tiles_n);
-            return launch_cross_grad<T, 64, P, Q>(st, spec, hp, Z, ldz, m, X, ldx, n, d, W, ldw, work, pw, tiles_m, tiles_n);
-        };
-        const int rc = prod ? go(std::true_type{}, std::true_type{}) : (per ? go(std::true_type{}, std::false_type{}) : go(std::false_type{}, std::false_type{}));
+        const int rc = pg_with_kinds(spec, prod, [&](auto per_c, auto prod_c) {
+            return pg_with_dmax(d, [&](auto dmax_c) {
+                return launch_cross_grad<T, decltype(dmax_c)::value, decltype(per_c)::value, decltype(prod_c)::value>(
+                    st, spec, hp, Z, ldz, m, X, ldx, n, d, W, ldw, work, pw, tiles_m, tiles_n);
+            });
+        });
         if (rc) return rc;
     }
     // (m == 0 or n == 0: an empty sum -- the reduce alone zeroes the spec's entries, or leaves them when accumulating)

@@ -25,6 +25,7 @@
 //     the product is formed explicitly, never as K / k_c: a factor that underflows gives 0.
 #include "kbuild.h"
 #include "kfun.h"
+#include "kpair.h"
 #include <type_traits>
 
 #define XT 64        // test points of a workgroup = training points of a staged tile
@@ -36,6 +37,12 @@ struct XgradBatch {  // strides between batched experts (elements); 0 shares an 
 
 // HOLD (d <= 16): the test point and the sixteen differences of a pair live in registers; otherwise the test points are read from
 // LDS and the accumulators cover KC = 16 coordinates per pass (passes over the coordinates repeat the distances: d > 16 is rare).
+// LDS of pg_xgrad_kernel in bytes: red, the training tile, (!HOLD) the test points, l2s, us, bs, ips -- the carve-up below
+template <typename T, int DMAX> static constexpr size_t xgrad_lds_bytes() {
+    constexpr int KC = DMAX <= 16 ? DMAX : 16;
+    return (size_t)4 * KC * XT * sizeof(double) +
+           (size_t)(XT * DMAX + (DMAX <= 16 ? 0 : XT * (DMAX + 1)) + 2 * PG_MAX_COMP * DMAX + XT + XT * BLD) * sizeof(T);
+}
 template <typename T, int DMAX, bool HU, bool HB, bool PROD = false>
 __global__ __launch_bounds__(256) void pg_xgrad_kernel(pg_covspec spec, const double* __restrict__ hp, const T* __restrict__ Xq, long ldq,
                                                        int m, const T* __restrict__ Z, long ldz, int n, int d, const T* __restrict__ u,
@@ -74,43 +81,15 @@ __global__ __launch_bounds__(256) void pg_xgrad_kernel(pg_covspec spec, const do
             xrs[r * (DMAX + 1) + k] = (g < m && k < d) ? Xq[(long)g * ldq + k] : (T)0;
         }
     }
-    for (int idx = tid; idx < spec.ncomp * DMAX; idx += 256) {
-        const int c = idx / DMAX, k = idx % DMAX;
-        const double l = (k < d) ? hp[spec.off[c] + 1 + k] : 0.0;
-        l2s[idx] = (T)(l * l);
-        ips[idx] = (k < d && spec.kind[c] == PG_KIND_PERIODIC) ? (T)(1.0 / hp[spec.off[c] + d + 1 + k]) : (T)0;
-    }
+    pair_stage_hp<T, true>(spec, hp, d, DMAX, DMAX, l2s, ips, tid, 256);      // (1 / p_k is always staged: no instantiation of its own)
 
     // PROD: the product of the values of every component but cp at (this lane's test point, the staged training point zc)
     auto others = [&](int cp, const T* zc) -> double {
         double oth = 1.0;
-        for (int c2 = 0; c2 < spec.ncomp; ++c2) {
-            if (c2 == cp) continue;
-            const T* l = l2s + c2 * DMAX;
-            const int kind2 = spec.kind[c2];
-            const double sg2 = hp[spec.off[c2]];
-            const T s2 = (T)(sg2 * sg2);
-            T sq = (T)0, kv;
-            if (kind2 == PG_KIND_PERIODIC) {
-                const T* ip = ips + c2 * DMAX;
-#pragma unroll
-                for (int k = 0; k < DMAX; ++k) sq += l[k] * per_sin2<T>(((HOLD ? xr[HOLD ? k : 0] : xrs[lane * (DMAX + 1) + k]) - zc[k]) * ip[k]);
-                kv = s2 * pg_exp(-sq);
-            } else {
-#pragma unroll
-                for (int k = 0; k < DMAX; ++k) {
-                    const T dd = (HOLD ? xr[HOLD ? k : 0] : xrs[lane * (DMAX + 1) + k]) - zc[k];
-                    sq += l[k] * dd * dd;
-                }
-                if (kind2 == PG_KIND_RBF) kv = s2 * pg_exp(-sq);
-                else {
-                    const double sh2 = kind_shape2(spec, hp, c2, d);
-                    T bt, ft;
-                    matern_val<T>(kind2, s2, sq, kv, bt, (T)sh2, (T)(1.0 / sh2), ft);
-                }
-            }
-            oth *= (double)kv;
-        }
+        auto xa = [&](int k) { return HOLD ? xr[HOLD ? k : 0] : xrs[lane * (DMAX + 1) + k]; };
+        auto xz = [&](int k) { return zc[k]; };
+        for (int c2 = 0; c2 < spec.ncomp; ++c2)
+            if (c2 != cp) oth *= (double)pair_value<T, DMAX>(spec, hp, c2, d, l2s + c2 * DMAX, ips + c2 * DMAX, xa, xz);
         return oth;
     };
 
@@ -265,15 +244,8 @@ template <typename T, int DMAX, bool HU, bool HB, bool PROD>
 static int launch_xgrad(hipStream_t st, const pg_covspec& spec, const double* hp, const T* Xq, long ldq, int m, const T* Z, long ldz,
                         int n, int d, const T* u, const T* B, long ldb, int trans_b, double* part, int nsplit, int ct, long mrows,
                         const XgradBatch& xb, int nexp) {
-    constexpr int KC = DMAX <= 16 ? DMAX : 16;
-    const size_t lds = (size_t)4 * KC * XT * sizeof(double) +
-                       (size_t)(XT * DMAX + (DMAX <= 16 ? 0 : XT * (DMAX + 1)) + 2 * PG_MAX_COMP * DMAX + XT + XT * BLD) * sizeof(T);
-    static bool attr_done = false;
-    if (!attr_done) {   // d > 16 in fp64 passes the 64 KB a kernel gets without opting in
-        PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_xgrad_kernel<T, DMAX, HU, HB, PROD>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_done = true;
-    }
+    constexpr size_t lds = xgrad_lds_bytes<T, DMAX>();
+    if (int rc = pg_lds_opt_in<pg_xgrad_kernel<T, DMAX, HU, HB, PROD>>(lds)) return rc;   // d > 16 in fp64 passes the 64 KB a kernel gets without opting in
     hipLaunchKernelGGL((pg_xgrad_kernel<T, DMAX, HU, HB, PROD>), dim3(nsplit, (m + XT - 1) / XT, nexp), dim3(256), lds, st, spec, hp, Xq, ldq, m, Z,
                        ldz, n, d, u, B, ldb, trans_b, part, ct, mrows, xb);
     PG_CHECK(hipGetLastError());
@@ -314,12 +286,10 @@ int pg_xgrad_t(hipStream_t st, int ncu, const pg_covspec& spec_in, const double*
     const long mrows = (long)((m + XT - 1) / XT) * XT;
     const XgradBatch xb = {xq_stride, z_stride, hp_stride, u_stride, b_stride};
     auto go = [&](auto prod_c) {
-        constexpr bool P = decltype(prod_c)::value;
-        if (d <= 4) return launch_xgrad_w<T, 4, P>(st, spec, hp, Xq, ldq, m, Z, ldz, n, d, u, B, ldb, trans_b, work, nsplit, ct, mrows, xb, nexp);
-        if (d <= 8) return launch_xgrad_w<T, 8, P>(st, spec, hp, Xq, ldq, m, Z, ldz, n, d, u, B, ldb, trans_b, work, nsplit, ct, mrows, xb, nexp);
-        if (d <= 16) return launch_xgrad_w<T, 16, P>(st, spec, hp, Xq, ldq, m, Z, ldz, n, d, u, B, ldb, trans_b, work, nsplit, ct, mrows, xb, nexp);
-        if (d <= 32) return launch_xgrad_w<T, 32, P>(st, spec, hp, Xq, ldq, m, Z, ldz, n, d, u, B, ldb, trans_b, work, nsplit, ct, mrows, xb, nexp);
-        return launch_xgrad_w<T, 64, P>(st, spec, hp, Xq, ldq, m, Z, ldz, n, d, u, B, ldb, trans_b, work, nsplit, ct, mrows, xb, nexp);
+        return pg_with_dmax(d, [&](auto dmax_c) {
+            return launch_xgrad_w<T, decltype(dmax_c)::value, decltype(prod_c)::value>(st, spec, hp, Xq, ldq, m, Z, ldz, n, d, u, B, ldb, trans_b, work,
+                                                                                     nsplit, ct, mrows, xb, nexp);
+        });
     };
     const int rc = prod ? go(std::true_type{}) : go(std::false_type{});
     if (rc) return rc;

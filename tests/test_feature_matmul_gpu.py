@@ -23,6 +23,7 @@ pytestmark = pytest.mark.gpu
 SHAPES = [(70, 150, 1), (70, 150, 16), (70, 150, 17), (70, 150, 33), (5, 5000, 2), (257, 17, 4), (1, 1, 1)]
 DIMS = [1, 3, 17, 33]            # the register ladder: DMAX 4, 4, 32, 64
 MORE = [(70, 150, 17, 7), (5, 5000, 2, 7), (70, 150, 17, 12), (5, 5000, 2, 12)]      # ... and its steps DMAX 8 and 16
+MORE += [(70, 150, 17, 5), (70, 150, 17, 9)]      # d = 5, 9 as the covariance kernels' tests have them (d = 33 at this shape: DIMS)
 
 
 @functools.lru_cache(maxsize=None)

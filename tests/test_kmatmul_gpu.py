@@ -16,7 +16,7 @@ import torch
 import matmul_ref as mr
 from kind_tools import dev, ops  # noqa: F401  (ops: the module's fixture)
 from test_framed_gpu import F64, ok, p, run
-from test_sparse_gpu import KMODELS, _hp, spec_for
+from test_sparse_gpu import DEEP_D, DEEP_MODELS, KMODELS, _hp, spec_for
 
 pytestmark = pytest.mark.gpu
 
@@ -59,9 +59,13 @@ def call(ops, terms, hp, xr, xc, v, jitter):
     return out.cpu().numpy()
 
 
-@pytest.mark.parametrize("name", sorted(KMODELS))
-@pytest.mark.parametrize("d", [1, 3, 17])
-@pytest.mark.parametrize("nr,nc,nrhs", CROSS)
+# every model and shape at d = 1, 3, 17 (the kernel's DMAX 4 and 32), then d = 5, 9, 33 (DMAX 8, 16 and 64, the last with its opt-in LDS
+# size) at one ragged two-by-three-tile shape with two panels of right-hand sides, for a plain, a periodic and a product model
+CROSS_GRID = [s + (d, name) for name in sorted(KMODELS) for d in (1, 3, 17) for s in CROSS]
+CROSS_GRID += [(70, 150, 20, d, name) for d in DEEP_D for name in DEEP_MODELS]
+
+
+@pytest.mark.parametrize("nr,nc,nrhs,d,name", CROSS_GRID, ids=["-".join(str(v) for v in c) for c in CROSS_GRID])
 def test_cross_form_against_the_restatement(ops, nr, nc, nrhs, d, name):
     terms, hp, xr, xc, v, jit, ref, scale, ref64, own = mcase(name, nr, nc, nrhs, d)
     got = call(ops, terms, hp, xr, xc, v, jit)

@@ -17,7 +17,7 @@ import torch
 import lowrank_ref as lr
 from kind_tools import dev, ops  # noqa: F401  (ops: the module's fixture)
 from test_framed_gpu import F64, gaps_odd, ok, p, run
-from test_sparse_gpu import KMODELS, SENT, _hp, spec_for
+from test_sparse_gpu import DEEP_D, DEEP_MODELS, KMODELS, SENT, _hp, spec_for
 
 pytestmark = pytest.mark.gpu
 
@@ -70,10 +70,19 @@ def judge(label, got, start, accumulate, ref_ld, scale, mine, own, r, sym):
     assert np.all(err[mine] <= allowed[mine]), (label, float(rel.max()), own)
 
 
-@pytest.mark.parametrize("accumulate", [False, True], ids=["set", "acc"])
-@pytest.mark.parametrize("name", sorted(KMODELS))
-@pytest.mark.parametrize("d", [1, 3, 17])
-@pytest.mark.parametrize("nr,nc,r", CROSS)
+def grid(shapes, deep):
+    """Every model, shape and mode at d = 1, 3, 17 (DMAX 4 and 32), then d = 5, 9, 33 (DMAX 8 and 16: the column point held in registers,
+    pairs unrolled by two and by one; DMAX 64: the opt-in LDS size) at the one shape `deep` for a plain, a periodic and a product model."""
+    g = [s + (d, name, acc) for acc in (False, True) for name in sorted(KMODELS) for d in (1, 3, 17) for s in shapes]
+    g += [deep + (d, name, False) for d in DEEP_D for name in DEEP_MODELS]
+    return g, ["-".join(str(v) for v in c[:-1]) + ("-acc" if c[-1] else "-set") for c in g]
+
+
+CROSS_GRID, CROSS_IDS = grid(CROSS, (70, 150, 5))
+SYM_GRID, SYM_IDS = grid(SYM, (150, 5))
+
+
+@pytest.mark.parametrize("nr,nc,r,d,name,accumulate", CROSS_GRID, ids=CROSS_IDS)
 def test_cross_form_against_the_restatement(ops, nr, nc, r, d, name, accumulate):
     terms, hp, xr, xc, u, v, ref, ref_ld, scale, mine, own = lcase(name, nr, nc, r, d)
     start = np.full(hp.size, SENT) + np.arange(hp.size)
@@ -82,10 +91,7 @@ def test_cross_form_against_the_restatement(ops, nr, nc, r, d, name, accumulate)
           False)
 
 
-@pytest.mark.parametrize("accumulate", [False, True], ids=["set", "acc"])
-@pytest.mark.parametrize("name", sorted(KMODELS))
-@pytest.mark.parametrize("d", [1, 3, 17])
-@pytest.mark.parametrize("n,r", SYM)
+@pytest.mark.parametrize("n,r,d,name,accumulate", SYM_GRID, ids=SYM_IDS)
 def test_symmetric_form_against_the_restatement(ops, n, r, d, name, accumulate):
     terms, hp, xr, _, u, v, ref, ref_ld, scale, mine, own = lcase(name, n, n, r, d, sym=True)
     start = np.full(hp.size, SENT) + np.arange(hp.size)

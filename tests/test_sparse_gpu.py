@@ -109,10 +109,15 @@ def judge(label, got, start, accumulate, ref, scale, mine, own):
     assert np.all(err <= allowed), (label, float(err.max()), own)
 
 
-@pytest.mark.parametrize("accumulate", [False, True], ids=["set", "acc"])
-@pytest.mark.parametrize("name", sorted(KMODELS))
-@pytest.mark.parametrize("d", [1, 3, 17])
-@pytest.mark.parametrize("m,n", SHAPES)
+# every model, shape and mode at d = 1, 3, 17 (the kernel's DMAX 4 and 32), then the other instantiations -- d = 5, 9, 33: DMAX 8, 16
+# and 64, the last with its opt-in LDS size -- at the one ragged two-by-three-tile shape for a plain, a periodic and a product model
+DEEP_D = [5, 9, 33]
+DEEP_MODELS = ["se+wn", "per", "se*per"]
+GRID = [(m, n, d, name, acc) for acc in (False, True) for name in sorted(KMODELS) for d in (1, 3, 17) for m, n in SHAPES]
+GRID += [(70, 150, d, name, False) for d in DEEP_D for name in DEEP_MODELS]
+
+
+@pytest.mark.parametrize("m,n,d,name,accumulate", GRID, ids=["%d-%d-%d-%s-%s" % (c[:4] + ("acc" if c[4] else "set",)) for c in GRID])
 def test_cross_grad_against_the_restatement(ops, m, n, d, name, accumulate):
     terms, hp, z, x, w, ref, scale, mine, own = kcase(name, m, n, d)
     start = np.full(hp.size, SENT) + np.arange(hp.size)
