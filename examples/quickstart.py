@@ -89,6 +89,9 @@ fs = igp.function_samples(n_samples=8, features=1024, seed=0)
 draws = fs(xs)                      # [8, q] draws of the latent function: the same eight functions wherever they are evaluated
 print("8 function samples (%d features, %d CG iterations): largest |sample mean - posterior mean| %.3f, largest sample sd %.3f" % (
     fs.frequencies.shape[0], fs.cg_info["iterations"], float((draws.mean(0) - mean).abs().max()), float(draws.std(0).max())))
+slopes = fs.grad(xs)                # [8, q, d]: the same eight functions' derivatives in the test points (no solve either)
+print("largest |d sample / d x*| %.3f; largest |d mean / d x*| %.3f" % (
+    float(slopes.abs().max()), float(igp.predict_grad(xs, var="none")[1].abs().max())))
 
 # ---- scikit-learn facade
 sk = PyGPR.SK_WRAP(PyGPR.Exact_GP(x, y, cov))

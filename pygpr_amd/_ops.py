@@ -416,6 +416,49 @@ class HipOps:
                    _p(v2), ld(v2, nrhs), nrhs, float(jitter), _p(o2), ld(o2, nrhs), _p(work), self._st())
         return out
 
+    # -- the derivative's matrix-free product (include/pygpr_hip_dmatmul.h) ------------------------
+    def kernel_matmul_dx_worksize(self, nr, nc, d, nrhs):
+        return int(self.lib.pg_kernel_matmul_dx_worksize(int(nr), int(nc), int(d), int(nrhs)))
+
+    def kernel_matmul_dx(self, spec, hp, xr, xc, v, out=None, work=None):
+        """out[i][k][c] = sum_j dk(xr_i, xc_j)/dxr_ik v[j][c] without forming dk (pg_kernel_matmul_dx; cross form only: xc may be xr).
+        xr [nr, d], xc [nc, d] float64 device tensors or views with unit stride along a row, v [nc, nrhs] likewise; out [nr, d, nrhs]
+        with unit stride along its last dimension (a one-dimensional v counts as one column, and out is [nr, d] then); out is
+        allocated when None.  One pg_covspec only.  work: kernel_matmul_dx_worksize doubles, allocated when None and needed."""
+        (sp,) = _passes(spec)
+        self._chk(hp, work)
+        if xc is None:
+            raise ValueError("kernel_matmul_dx has a cross form only: pass xc (it may be xr)")
+        vec = v.dim() == 1
+        v2 = v.unsqueeze(1) if vec else v
+        nr, d = xr.shape
+        nc = xc.shape[0]
+        nrhs = v2.shape[1]
+        if out is None:
+            out = self.empty(nr, d, dtype=torch.float64) if vec else self.empty(nr, d, nrhs, dtype=torch.float64)
+        o3 = out.unsqueeze(2) if out.dim() == 2 and vec else out
+        for name, t, shape in (("xr", xr, (nr, d)), ("xc", xc, (nc, d)), ("v", v2, (nc, nrhs))):
+            if not (t.is_cuda and t.dim() == 2 and tuple(t.shape) == shape and t.dtype == torch.float64 and (t.stride(1) == 1 or t.shape[1] <= 1)):
+                raise ValueError("kernel_matmul_dx needs %s %s float64 on the device, unit stride along a row" % (name, list(shape)))
+        if not (o3.is_cuda and o3.dim() == 3 and tuple(o3.shape) == (nr, d, nrhs) and o3.dtype == torch.float64
+                and (o3.stride(2) == 1 or nrhs <= 1)):
+            raise ValueError("kernel_matmul_dx needs out %s float64 on the device, unit stride along its last dimension" % [nr, d, nrhs])
+        assert hp.dtype == torch.float64
+
+        def ld(t, width):      # (a matrix of one row or none has no row stride to speak of)
+            return max(int(t.stride(0)), width, 1) if t.shape[0] > 1 else max(width, 1)
+
+        ldk = max(int(o3.stride(1)), nrhs, 1) if d > 1 else max(nrhs, 1)
+        ldo = max(int(o3.stride(0)), d * ldk) if nr > 1 else d * ldk
+        size = self.kernel_matmul_dx_worksize(nr, nc, d, nrhs)
+        if work is None and size > 0:
+            work = self.empty(size, dtype=torch.float64)
+        assert size == 0 or (work.dtype == torch.float64 and work.numel() >= size)
+        xcp = _p(xc) if nc > 0 else _p(hp)      # (an empty tensor has a null address, which the library refuses: it has no symmetric form)
+        self._call("pg_kernel_matmul_dx", PG_F64, C.byref(sp), _p(hp), _p(xr), ld(xr, d), nr, xcp, ld(xc, d), nc, d, _p(v2), ld(v2, nrhs), nrhs,
+                   _p(o3), ldo, ldk, _p(work), self._st())
+        return out
+
     # -- the random-feature product (include/pygpr_hip_feature.h) ----------------------------------
     def feature_matmul_worksize(self, nr, nf, nrhs):
         return int(self.lib.pg_feature_matmul_worksize(int(nr), int(nf), int(nrhs)))

@@ -9,6 +9,7 @@
 #include "sparse.h"
 #include "select.h"
 #include "kmatmul.h"
+#include "dmatmul.h"
 #include "fmatmul.h"
 #include "lowrank.h"
 #include <cstdarg>
@@ -694,6 +695,32 @@ int pg_kernel_matmul(pg_handle h, int dtype, const pg_covspec* spec, const doubl
     NEED(work || pg_kmatmul_worksize_impl(nr, nc, nrhs) == 0, "this shape needs its workspace (pg_kernel_matmul_worksize)");
     return pg_kmatmul_impl(ST(stream), *spec, hp, (const double*)Xr, ldr, nr, (const double*)Xc, ldc, nc, d, sym, (const double*)V, ldv, nrhs,
                            jitter, (double*)OUT, ldo, (double*)work);
+}
+
+long pg_kernel_matmul_dx_worksize(int nr, int nc, int d, int nrhs) {
+    return (nr >= 0 && nc >= 0 && d >= 0 && nrhs >= 0) ? pg_dmatmul_worksize_impl(nr, nc, d, nrhs) : -1;
+}
+
+int pg_kernel_matmul_dx(pg_handle h, int dtype, const pg_covspec* spec, const double* hp, const void* Xr, long ldr, int nr, const void* Xc,
+                        long ldc, int nc, int d, const void* V, long ldv, int nrhs, void* OUT, long ldo, long ldk, void* work,
+                        void* stream) {
+    JOIN(h, stream);
+    NEED(h && hp, "null pointer");
+    NEED(dtype == PG_F64, "float64 only (dtype must be PG_F64)");
+    if (check_spec(spec, __func__)) return -1;      // (PG_KIND_SQDIST is refused: it is no covariance)
+    for (int c = 0; c < (spec->ncomp & ~PG_SPEC_PRODUCT); ++c) NEED(spec->off[c] >= 0, "negative offset in the covariance spec");
+    NEED(Xc, "cross form only (Xc must not be NULL; it may be Xr)");
+    if (!(nr >= 0 && nc >= 0 && nrhs >= 0 && d >= 1 && d <= PG_MAX_DIM)) {
+        pg_set_error("%s: bad shape (0 <= nr, nc, nrhs; 1 <= d <= PG_MAX_DIM)", __func__);
+        return -2;
+    }
+    if ((long)((nrhs + 31) / 32) * dmm_nchunk(d) > 65535) { pg_set_error("%s: nrhs <= 32 * (65535 / chunks of d)", __func__); return -2; }
+    NEED(ldr >= d && ldc >= d && ldv >= nrhs && ldk >= nrhs && ldo >= (long)d * ldk, "ldr, ldc >= d, ldv, ldk >= nrhs and ldo >= d * ldk");
+    if (nr == 0 || nrhs == 0) return 0;
+    NEED(Xr && OUT && (nc == 0 || V), "null pointer");
+    NEED(work || pg_dmatmul_worksize_impl(nr, nc, d, nrhs) == 0, "this shape needs its workspace (pg_kernel_matmul_dx_worksize)");
+    return pg_dmatmul_impl(ST(stream), *spec, hp, (const double*)Xr, ldr, nr, (const double*)Xc, ldc, nc, d, (const double*)V, ldv, nrhs,
+                           (double*)OUT, ldo, ldk, (double*)work);
 }
 
 long pg_feature_matmul_worksize(int nr, int nf, int nrhs) { return (nr >= 0 && nf >= 0 && nrhs >= 0) ? pg_fmatmul_worksize_impl(nr, nf, nrhs) : -1; }

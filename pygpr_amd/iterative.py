@@ -27,6 +27,10 @@ Training.  MLE and LOO need the factor and refuse this model; `Stochastic_MLE` (
 the gradient from the same probe solves through pg_kernel_lowrank_grad.  `VFE` on a Sparse_GP, or MLE on an Exact_GP of a subset, remain
 the cheaper ways to a starting point.  Batched models, float32 and covariances longer than one pg_covspec are refused.
 
+Derivatives.  `predict_grad` gives d mean / dx* and d var / dx* without autograd: both from pg_kernel_xgrad, the mean's
+against alpha, the variance's against the block solve its value takes anyway.  `predict` itself stays closed to autograd.  The
+derivative of a function sample, S right-hand sides at once, is pg_kernel_matmul_dx's (include/pygpr_hip_dmatmul.h).
+
 Sampling.  `function_samples` draws posterior functions by pathwise conditioning (pygpr_amd/pathwise.py): one block solve
 for all samples, then every evaluation is one cross product and one feature product.  A joint `sampler` stays refused.
 """
@@ -286,16 +290,63 @@ class Iterative_GP(GPR):
         return self._state["alpha"].to(self._x.device)
 
     # ---- prediction -------------------------------------------------------------------------
+    def _check_xp(self, xp, who):
+        if xp.dim() != 2 or xp.shape[1] != self._x.shape[1]:
+            raise NotImplementedError("Iterative_GP.%s: xp must be [q, %d] (no batches)" % (who, self._x.shape[1]))
+        if xp.dtype != torch.float64:
+            raise TypeError("Iterative_GP computes in float64 only; xp is %s" % xp.dtype)
+
+    def _diag_variance(self, ops, st, xpd, dvar=None):
+        """var [q] at the device points xpd: the test points in blocks of _RHS_BLOCK, each a block solve A S = k(x, xp_b) at the model's
+        tol.  dvar [q, d]: also filled, dvar[p] = -2 sum_i S_ip dk(xp_p, x_i)/dxp_p from the same solution (pg_kernel_xgrad's B form
+        on the n x 64 block, stored transposed) -- K** has a constant diagonal, so there is no other term."""
+        xd, hpd, spec = st["x"], st["hpd"], st["spec"]
+        n, q = xd.shape[0], xpd.shape[0]
+        npad = pad_to(n)
+        blk = int(_RHS_BLOCK)
+        cols = pad_to(blk, _RHS_PAD)
+        vr = ops.empty(q)
+        for s in range(0, q, blk):
+            qb = min(blk, q - s)
+            ks = ops.empty(npad, cols)
+            ops.kernel_build(spec, hpd, xd, xpd[s: s + qb], ks)            # k(x, xp_b), zero in the padding
+            sol, _, _ = self._solve(ops, st, ks, qb)
+            vr[s: s + qb] = st["kss"] - (ks[:n, :qb] * sol[:n, :qb]).sum(0)
+            if dvar is not None:
+                ops.kernel_xgrad(spec, hpd, xpd[s: s + qb], xd, b=sol[:n], out_b=dvar[s: s + qb], trans_b=True)
+        if dvar is not None:
+            dvar.mul_(-2.0)
+        return vr
+
+    def predict_grad(self, xp: Tensor, var: str = "diag") -> Sequence[Tensor]:
+        """[mean, var, dmean, dvar] (var="diag") or [mean, dmean] (var="none") without autograd, Exact_GP.predict_grad's contract:
+        dmean[p, :] = d mean_p / d xp_p and dvar[p, :] = d var_p / d xp_p, [q, d] float64 on xp's device.  Mean and variance are
+        `predict`'s own (same path, same bits).  dmean is pg_kernel_xgrad's vector form against alpha (no q x n matrix; for ONE
+        right-hand side that VALU pass is three times faster than pg_kernel_matmul_dx); the variance and its derivative
+        share one block solve per _RHS_BLOCK test points, and var="none" solves nothing."""
+        if var not in ("diag", "none"):
+            raise ValueError("predict_grad: var must be 'diag' or 'none', got %r" % (var,))
+        self._check_xp(xp, "predict_grad")
+        ops = get_ops()
+        self.update()
+        st = self._state
+        xd, hpd, spec = st["x"], st["hpd"], st["spec"]
+        xpd = ops.to_device(xp.detach(), torch.float64)
+        mean = ops.kernel_matmul(spec, hpd, xpd, xd, st["alpha"])
+        dmean, _ = ops.kernel_xgrad(spec, hpd, xpd, xd, u=st["alpha"])
+        if var == "none":
+            return [mean.to(xp.device), dmean.to(xp.device)]
+        dvar = ops.empty(xpd.shape[0], xd.shape[1])
+        vr = self._diag_variance(ops, st, xpd, dvar)
+        return [mean.to(xp.device), vr.to(xp.device), dmean.to(xp.device), dvar.to(xp.device)]
+
     def predict(self, xp: Tensor, var: str = "full") -> Sequence[Tensor]:
         """[mean, var | covariance | NotImplemented] of y* at xp [q, d]: the mean is one cross product against alpha (no q x n matrix);
         the variances take the test points in blocks of _RHS_BLOCK, each a block solve A S = k(x, xp_b) at the model's tol."""
         if torch.is_grad_enabled() and isinstance(xp, Tensor) and xp.requires_grad:
             raise NotImplementedError("Iterative_GP.predict is not differentiable through autograd; use an Exact_GP for derivatives in "
                                       "the test points")
-        if xp.dim() != 2 or xp.shape[1] != self._x.shape[1]:
-            raise NotImplementedError("Iterative_GP.predict: xp must be [q, %d] (no batches)" % self._x.shape[1])
-        if xp.dtype != torch.float64:
-            raise TypeError("Iterative_GP computes in float64 only; xp is %s" % xp.dtype)
+        self._check_xp(xp, "predict")
         ops = get_ops()
         self.update()
         st = self._state
@@ -318,12 +369,7 @@ class Iterative_GP(GPR):
             return ks
 
         if want == "diag":
-            vr = ops.empty(q)
-            for s, qb in blocks:
-                ks = cross(s, qb)
-                sol, _, _ = self._solve(ops, st, ks, qb)
-                vr[s: s + qb] = st["kss"] - (ks[:n, :qb] * sol[:n, :qb]).sum(0)
-            return [mean.to(xp.device), vr.to(xp.device)]
+            return [mean.to(xp.device), self._diag_variance(ops, st, xpd).to(xp.device)]
         qp = pad_to(q)
         cov = ops.empty(qp, qp)
         ops.kernel_build(st["full_spec"], hpd, xpd, None, cov)              # K** incl. sigma_n^2, identity in the padding

@@ -37,6 +37,7 @@ STREAM_DIR = 0x5200      # pg_randn stream of the directions g of component c: S
 STREAM_CHI = 0x5210      # ... of the normals whose square sum is a Matern component's chi^2: STREAM_CHI + c
 STREAM_W = 0x5220        # ... of the feature weights W [nf, S]
 STREAM_EPS = 0x5221      # ... of the noise draws E [n, S]
+_GRAD_COLUMNS = 512      # columns of the derivative's feature weights (coordinates x samples) one feature product carries
 
 _KIND_NAMES = {_lib.PG_KIND_RQ: "Rational_quadratic", _lib.PG_KIND_PERIODIC: "Periodic"}
 _DOF = {_lib.PG_KIND_MATERN12: 1, _lib.PG_KIND_MATERN32: 3, _lib.PG_KIND_MATERN52: 5}      # m = 2 nu
@@ -112,7 +113,8 @@ class FunctionSamples:
     weights, so later set_params or data edits of the model do not change it.  Sample s depends on (seed, features, s) and not on
     n_samples.  Memory: O(n (d + S) + nf (d + S)); nothing is n x nf or q x n.
 
-    `frequencies` [nf, d], `phases` [nf] and `weights` [nf, S] (the normals times the features' amplitudes) are host copies;
+    `frequencies` [nf, d], `phases` [nf], `weights` [nf, S] (the normals times the features' amplitudes) and `data_weights` [n, S] (the
+    solved A^-1 (y - Phi(X) w_s - eps_s); None for a prior) are host copies: f_s(.) = Phi(.) weights[:, s] + k(., X) data_weights[:, s];
     `cg_info`: solves, iterations (the most any block solve took) and residual (the worst true one) -- None for a prior."""
 
     def __init__(self, spec, hpd: Optional[Tensor], x: Optional[Tensor], nu: Tensor, u: Tensor, w: Tensor, v: Optional[Tensor],
@@ -134,14 +136,40 @@ class FunctionSamples:
     def weights(self) -> ndarray:
         return self._w.cpu().numpy()
 
-    def __call__(self, xp: Tensor) -> Tensor:
+    @property
+    def data_weights(self) -> Optional[ndarray]:
+        return None if self._v is None else self._v.cpu().numpy()
+
+    def _checked_device(self, xp: Tensor):
         d = self._nu.shape[1]
         if not isinstance(xp, Tensor) or xp.dim() != 2 or xp.shape[1] != d:
             raise NotImplementedError("FunctionSamples: xp must be [q, %d] (no batches)" % d)
         if xp.dtype != torch.float64:
             raise TypeError("FunctionSamples computes in float64 only; xp is %s" % xp.dtype)
         ops = get_ops()
-        xpd = ops.to_device(xp.detach(), torch.float64)
+        return ops, ops.to_device(xp.detach(), torch.float64)
+
+    def grad(self, xp: Tensor) -> Tensor:
+        """[n_samples, q, d] on xp's device: entry [s, p, k] is d f_s(xp_p) / d xp_pk, the derivative of what `fs(xp)` returns.  The
+        feature part is the feature product at phases u + 0.25 (exact in cycles: d/dt cos(2 pi t) = 2 pi cos(2 pi (t + 1/4))) against
+        the weights 2 pi nu_fk w_fs, d S columns taken in blocks of coordinates; the data part is one pg_kernel_matmul_dx against the
+        solved weights (include/pygpr_hip_dmatmul.h).  No solve, nothing q x n."""
+        ops, xpd = self._checked_device(xp)
+        q, d, S = xpd.shape[0], self._nu.shape[1], self.n_samples
+        out = ops.empty(q, d, S)
+        uq = self._u + 0.25
+        kb = max(1, _GRAD_COLUMNS // S)
+        for k0 in range(0, d, kb):
+            k1 = min(d, k0 + kb)
+            wk = (2.0 * np.pi) * self._nu[:, k0:k1, None] * self._w[:, None, :]           # [nf, kb, S]
+            part = ops.feature_matmul(xpd, self._nu, uq, wk.reshape(wk.shape[0], (k1 - k0) * S))
+            out[:, k0:k1, :] = part.reshape(q, k1 - k0, S)
+        if self._v is not None:
+            out += ops.kernel_matmul_dx(self._spec, self._hpd, xpd, self._x, self._v)
+        return out.permute(2, 0, 1).contiguous().to(xp.device)
+
+    def __call__(self, xp: Tensor) -> Tensor:
+        ops, xpd = self._checked_device(xp)
         out = ops.feature_matmul(xpd, self._nu, self._u, self._w)                      # [q, S]
         if self._v is not None:
             out += ops.kernel_matmul(self._spec, self._hpd, xpd, self._x, self._v)
