@@ -459,6 +459,41 @@ class HipOps:
                    _p(o3), ldo, ldk, _p(work), self._st())
         return out
 
+    # -- the cross-covariance's squared row norms (include/pygpr_hip_rowsq.h) ----------------------
+    def kernel_rowsq_worksize(self, nr, nc):
+        return int(self.lib.pg_kernel_rowsq_worksize(int(nr), int(nc)))
+
+    def kernel_rowsq(self, spec, hp, xr, xc, out=None, work=None):
+        """out[i] = sum_j k(xr_i, xc_j)^2 without forming k (pg_kernel_rowsq; cross form only: xc may be xr, no noise term).  xr [nr, d],
+        xc [nc, d] float64 device tensors or views with unit stride along a row; out [nr] float64 on the device at any stride, allocated
+        when None.  One pg_covspec only.  work: kernel_rowsq_worksize doubles, allocated when None and needed."""
+        (sp,) = _passes(spec)
+        self._chk(hp, work)
+        if xc is None:
+            raise ValueError("kernel_rowsq has a cross form only: pass xc (it may be xr)")
+        nr, d = xr.shape
+        nc = xc.shape[0]
+        if out is None:
+            out = self.empty(nr, dtype=torch.float64)
+        for name, t, shape in (("xr", xr, (nr, d)), ("xc", xc, (nc, d))):
+            if not (t.is_cuda and t.dim() == 2 and tuple(t.shape) == shape and t.dtype == torch.float64 and (t.stride(1) == 1 or t.shape[1] <= 1)):
+                raise ValueError("kernel_rowsq needs %s %s float64 on the device, unit stride along a row" % (name, list(shape)))
+        if not (out.is_cuda and out.dim() == 1 and out.shape[0] == nr and out.dtype == torch.float64 and (nr <= 1 or out.stride(0) >= 1)):
+            raise ValueError("kernel_rowsq needs out %s float64 on the device" % [nr])
+        assert hp.dtype == torch.float64
+
+        def ld(t, width):      # (a matrix of one row or none has no row stride to speak of)
+            return max(int(t.stride(0)), width, 1) if t.shape[0] > 1 else max(width, 1)
+
+        size = self.kernel_rowsq_worksize(nr, nc)
+        if work is None and size > 0:
+            work = self.empty(size, dtype=torch.float64)
+        assert size == 0 or (work.dtype == torch.float64 and work.numel() >= size)
+        xcp = _p(xc) if nc > 0 else _p(hp)      # (an empty tensor has a null address, which the library refuses: it has no symmetric form)
+        self._call("pg_kernel_rowsq", PG_F64, C.byref(sp), _p(hp), _p(xr), ld(xr, d), nr, xcp, ld(xc, d), nc, d, _p(out),
+                   int(out.stride(0)) if nr > 1 else 1, _p(work), self._st())
+        return out
+
     # -- the random-feature product (include/pygpr_hip_feature.h) ----------------------------------
     def feature_matmul_worksize(self, nr, nf, nrhs):
         return int(self.lib.pg_feature_matmul_worksize(int(nr), int(nf), int(nrhs)))

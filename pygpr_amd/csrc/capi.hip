@@ -10,6 +10,7 @@
 #include "select.h"
 #include "kmatmul.h"
 #include "dmatmul.h"
+#include "krowsq.h"
 #include "fmatmul.h"
 #include "lowrank.h"
 #include <cstdarg>
@@ -695,6 +696,27 @@ int pg_kernel_matmul(pg_handle h, int dtype, const pg_covspec* spec, const doubl
     NEED(work || pg_kmatmul_worksize_impl(nr, nc, nrhs) == 0, "this shape needs its workspace (pg_kernel_matmul_worksize)");
     return pg_kmatmul_impl(ST(stream), *spec, hp, (const double*)Xr, ldr, nr, (const double*)Xc, ldc, nc, d, sym, (const double*)V, ldv, nrhs,
                            jitter, (double*)OUT, ldo, (double*)work);
+}
+
+long pg_kernel_rowsq_worksize(int nr, int nc) { return (nr >= 0 && nc >= 0) ? pg_krowsq_worksize_impl(nr, nc) : -1; }
+
+int pg_kernel_rowsq(pg_handle h, int dtype, const pg_covspec* spec, const double* hp, const void* Xr, long ldr, int nr, const void* Xc,
+                    long ldc, int nc, int d, void* OUT, long ldo, void* work, void* stream) {
+    JOIN(h, stream);
+    NEED(h && hp, "null pointer");
+    NEED(dtype == PG_F64, "float64 only (dtype must be PG_F64)");
+    if (check_spec(spec, __func__)) return -1;      // (PG_KIND_SQDIST is refused: it is no covariance)
+    for (int c = 0; c < (spec->ncomp & ~PG_SPEC_PRODUCT); ++c) NEED(spec->off[c] >= 0, "negative offset in the covariance spec");
+    NEED(Xc, "cross form only (Xc must not be NULL; it may be Xr)");
+    if (!(nr >= 0 && nc >= 0 && d >= 1 && d <= PG_MAX_DIM)) {
+        pg_set_error("%s: bad shape (0 <= nr, nc; 1 <= d <= PG_MAX_DIM)", __func__);
+        return -2;
+    }
+    NEED(ldr >= d && ldc >= d && ldo >= 1, "ldr, ldc >= d and ldo >= 1");
+    if (nr == 0) return 0;
+    NEED(Xr && OUT, "null pointer");
+    NEED(work || pg_krowsq_worksize_impl(nr, nc) == 0, "this shape needs its workspace (pg_kernel_rowsq_worksize)");
+    return pg_krowsq_impl(ST(stream), *spec, hp, (const double*)Xr, ldr, nr, (const double*)Xc, ldc, nc, d, (double*)OUT, ldo, (double*)work);
 }
 
 long pg_kernel_matmul_dx_worksize(int nr, int nc, int d, int nrhs) {

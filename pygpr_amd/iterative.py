@@ -31,6 +31,11 @@ Derivatives.  `predict_grad` gives d mean / dx* and d var / dx* without autograd
 against alpha, the variance's against the block solve its value takes anyway.  `predict` itself stays closed to autograd.  The
 derivative of a function sample, S right-hand sides at once, is pg_kernel_matmul_dx's (include/pygpr_hip_dmatmul.h).
 
+Cached variances.  `variance_cache` builds a `VarianceCache` (pygpr_amd/varcache.py): a Galerkin projection of A^-1 onto a
+block-Krylov space started from the preconditioner's factor, y and optional anchor points, built once from a handful of wide products;
+every variance afterwards is one cross product and no solve, an upper bound of the exact variance, and with `bounds` it comes with a
+certified lower bound whose |k*|^2 term is pg_kernel_rowsq (include/pygpr_hip_rowsq.h).  `predict` keeps its block solves.
+
 Sampling.  `function_samples` draws posterior functions by pathwise conditioning (pygpr_amd/pathwise.py): one block solve
 for all samples, then every evaluation is one cross product and one feature product.  A joint `sampler` stays refused.
 """
@@ -47,6 +52,7 @@ from .covar import Covar, spec_of, terms
 from .gpr import _CHUNK, GPR, _checked, _lin_alg_error
 from .pathwise import FunctionSamples, _check_count, _checked_terms, draw_function_samples
 from .sparse import _prior_of, _stationary, select_inducing
+from .varcache import VarianceCache
 
 _RHS_BLOCK = 64      # test points whose variance columns one block solve carries
 _RHS_PAD = 128       # the GEMM core's column tile: every block of right-hand sides is a buffer of that many columns (or a multiple)
@@ -383,6 +389,17 @@ class Iterative_GP(GPR):
                 cov[s2: s2 + qb2, s: s + qb].sub_(g[:qb2, :qb])
         ops.symmetrize(cov, qp)                                             # the upper triangle is the mirror: exactly symmetric
         return [mean.to(xp.device), cov[:q, :q].contiguous().to(xp.device)]
+
+    # ---- cached variances ------------------------------------------------------------------
+    def variance_cache(self, steps: int = 2, anchors: Tensor = None, bounds: bool = True, max_columns: int = 4096) -> VarianceCache:
+        """A VarianceCache of the fitted model (fits if dirty): the Galerkin projection of A^-1 onto span[B0, A B0, ..., A^steps B0],
+        B0 = [L | y | k(X, anchors)] with L the preconditioner's factor and `anchors` [na, d] float64 points where the variance matters
+        (their cross-covariance columns).  Its variances are upper bounds of the exact ones that tighten with steps and anchors;
+        bounds=True also keeps A Q for the lower bound of `variance(xp, bounds=True)`, certified up to a stated rounding model.  A request whose
+        (steps + 1) x (rank + 1 + na) columns exceed max_columns is a ValueError before any product.  The cache is a SNAPSHOT, like a
+        FunctionSamples: later set_params or refits of the model do not change it.  NotConverged and a failed preconditioner
+        propagate as from update(); a failed factorisation of the projected matrix raises like Exact_GP's."""
+        return VarianceCache(self, steps, anchors, bounds, max_columns)
 
     # ---- function samples -------------------------------------------------------------------
     def function_samples(self, n_samples: int = 1, features: int = 1024, seed: int = 0, prior: bool = False) -> FunctionSamples:
