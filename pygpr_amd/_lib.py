@@ -1,6 +1,6 @@
 """ctypes binding of libpygpr_hip.so (C ABI: include/pygpr_hip.h, include/pygpr_hip_loo.h, include/pygpr_hip_sample.h,
 include/pygpr_hip_sparse.h, include/pygpr_hip_select.h, include/pygpr_hip_matmul.h, include/pygpr_hip_lowrank.h, include/pygpr_hip_feature.h,
-include/pygpr_hip_dmatmul.h, include/pygpr_hip_rowsq.h).
+include/pygpr_hip_dmatmul.h, include/pygpr_hip_rowsq.h, include/pygpr_hip_lxgrad.h).
 
 There is no CPU fallback: `load()` raises if the shared object is missing, and every compute call
 needs a HIP device.  Build the library with `python __graft_entry__.py` (hipcc, gfx950).
@@ -21,6 +21,7 @@ HEADER_LOWRANK = os.path.join(os.path.dirname(_HERE), "include", "pygpr_hip_lowr
 HEADER_FEATURE = os.path.join(os.path.dirname(_HERE), "include", "pygpr_hip_feature.h")   # the random-feature product (an eighth)
 HEADER_DMATMUL = os.path.join(os.path.dirname(_HERE), "include", "pygpr_hip_dmatmul.h")   # the derivative's matrix-free product (a ninth)
 HEADER_ROWSQ = os.path.join(os.path.dirname(_HERE), "include", "pygpr_hip_rowsq.h")   # the cross-covariance's squared row norms (a tenth)
+HEADER_LXGRAD = os.path.join(os.path.dirname(_HERE), "include", "pygpr_hip_lxgrad.h")   # the low-rank training-input gradient (an eleventh)
 
 PG_F64, PG_F32 = 0, 1
 PG_KIND_RBF, PG_KIND_MATERN52, PG_KIND_SQDIST, PG_KIND_MATERN32, PG_KIND_MATERN12 = 0, 1, 2, 3, 4
@@ -100,6 +101,7 @@ _SIGS_LOWRANK = signatures(parse_prototypes(open(HEADER_LOWRANK).read()))
 _SIGS_FEATURE = signatures(parse_prototypes(open(HEADER_FEATURE).read()))
 _SIGS_DMATMUL = signatures(parse_prototypes(open(HEADER_DMATMUL).read()))
 _SIGS_ROWSQ = signatures(parse_prototypes(open(HEADER_ROWSQ).read()))
+_SIGS_LXGRAD = signatures(parse_prototypes(open(HEADER_LXGRAD).read()))
 
 _lib = None
 
@@ -115,13 +117,13 @@ def load(check_symbols=False):
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_LOO.items()) + list(_SIGS_SAMPLE.items()) + list(_SIGS_SPARSE.items())
                                   + list(_SIGS_SELECT.items()) + list(_SIGS_MATMUL.items()) + list(_SIGS_LOWRANK.items()) + list(_SIGS_FEATURE.items())
-                                  + list(_SIGS_DMATMUL.items()) + list(_SIGS_ROWSQ.items())):
+                                  + list(_SIGS_DMATMUL.items()) + list(_SIGS_ROWSQ.items()) + list(_SIGS_LXGRAD.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib
     if check_symbols:
         missing = [s for s in header_symbols() + sorted(_SIGS_LOO) + sorted(_SIGS_SAMPLE) + sorted(_SIGS_SPARSE) + sorted(_SIGS_SELECT)
-                   + sorted(_SIGS_MATMUL) + sorted(_SIGS_LOWRANK) + sorted(_SIGS_FEATURE) + sorted(_SIGS_DMATMUL) + sorted(_SIGS_ROWSQ) if not hasattr(_lib, s)]
+                   + sorted(_SIGS_MATMUL) + sorted(_SIGS_LOWRANK) + sorted(_SIGS_FEATURE) + sorted(_SIGS_DMATMUL) + sorted(_SIGS_ROWSQ) + sorted(_SIGS_LXGRAD) if not hasattr(_lib, s)]
         unbound = [s for s in header_symbols() if s not in _SIGS]
         if missing or unbound:
             raise RuntimeError("C ABI mismatch: missing in .so %s, unbound in _lib.py %s" % (missing, unbound))
@@ -144,7 +146,7 @@ def build_id():
 
     csrc = os.path.join(_HERE, "csrc")
     h = hashlib.sha256()
-    for f in sorted(os.listdir(csrc)) + [HEADER, HEADER_LOO, HEADER_SAMPLE, HEADER_SPARSE, HEADER_SELECT, HEADER_MATMUL, HEADER_LOWRANK, HEADER_FEATURE, HEADER_DMATMUL, HEADER_ROWSQ]:
+    for f in sorted(os.listdir(csrc)) + [HEADER, HEADER_LOO, HEADER_SAMPLE, HEADER_SPARSE, HEADER_SELECT, HEADER_MATMUL, HEADER_LOWRANK, HEADER_FEATURE, HEADER_DMATMUL, HEADER_ROWSQ, HEADER_LXGRAD]:
         path = f if os.path.isabs(f) else os.path.join(csrc, f)
         if path.endswith((".hip", ".h")):
             h.update(os.path.basename(path).encode())

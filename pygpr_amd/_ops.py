@@ -568,6 +568,44 @@ class HipOps:
                    _p(u), ld(u, r), _p(v), ld(v, r), r, _p(grad), int(bool(accumulate)), _p(work), self._st())
         return grad
 
+    # -- the low-rank training-input gradient (include/pygpr_hip_lxgrad.h) ------------------------
+    def kernel_lowrank_xgrad_worksize(self, nr, nc, d, r):
+        return int(self.lib.pg_kernel_lowrank_xgrad_worksize(int(nr), int(nc), int(d), int(r)))
+
+    def kernel_lowrank_xgrad(self, spec, hp, xr, xc, u, v, out=None, accumulate=False, work=None):
+        """out[i][k] (+)= sum_j (sum_t u[i][t] v[j][t]) dk(xr_i, xc_j)/dxr_ik, the weight never formed (pg_kernel_lowrank_xgrad); xc None:
+        the weight is u v^T + v u^T over the one point set xr, the gradient of sum_ij (u v^T)_ij k(xr_i, xr_j) in xr.  xr [nr, d],
+        xc [nc, d], u [nr, r], v [nc, r] (r <= 64) float64 device tensors or views with unit stride along a row; out [nr, d] float64 on
+        the device, unit stride along a row, allocated when None.  One pg_covspec only.  work: kernel_lowrank_xgrad_worksize doubles,
+        allocated when None and needed."""
+        (sp,) = _passes(spec)
+        self._chk(hp, out, work)
+        nr, d = xr.shape
+        nc = xc.shape[0] if xc is not None else nr
+        r = u.shape[1] if u.dim() == 2 else -1
+        if out is None:
+            assert not accumulate
+            out = self.empty(nr, d, dtype=torch.float64)
+        for name, t, shape in (("xr", xr, (nr, d)), ("xc", xc, (nc, d)), ("u", u, (nr, r)), ("v", v, (nc, r)), ("out", out, (nr, d))):
+            if t is None:
+                continue
+            if not (t.is_cuda and t.dim() == 2 and tuple(t.shape) == shape and t.dtype == torch.float64
+                    and (t.stride(1) == 1 or t.shape[1] <= 1 or t.shape[0] == 0)):
+                raise ValueError("kernel_lowrank_xgrad needs %s %s float64 on the device, unit stride along a row" % (name, list(shape)))
+        assert hp.dtype == torch.float64
+
+        def ld(t, width):      # (a matrix of one row or none has no row stride to speak of)
+            return max(int(t.stride(0)), width, 1) if t.shape[0] > 1 else max(width, 1)
+
+        size = self.kernel_lowrank_xgrad_worksize(nr, nc, d, r)
+        if work is None and size > 0:
+            work = self.empty(size, dtype=torch.float64)
+        assert size == 0 or (work.dtype == torch.float64 and work.numel() >= size)
+        xcp = _p(xc) if xc is None or nc > 0 else _p(hp)      # (an empty tensor has a null address, which would read as the symmetric form)
+        self._call("pg_kernel_lowrank_xgrad", PG_F64, C.byref(sp), _p(hp), _p(xr), ld(xr, d), nr, xcp, ld(xc, d) if xc is not None else 0, nc, d,
+                   _p(u), ld(u, r), _p(v), ld(v, r), r, _p(out), ld(out, d), int(bool(accumulate)), _p(work), self._st())
+        return out
+
     # -- normal variates (include/pygpr_hip_sample.h) -------------------------------------------
     def randn(self, out, rows, cols, seed, stream_id=0, row0=0):
         """out[r][q] = normal(seed, stream_id, row0 + r, q) for r < rows, q < cols, zero in the rest of out (pg_randn): out is a 2-D

@@ -13,6 +13,7 @@
 #include "krowsq.h"
 #include "fmatmul.h"
 #include "lowrank.h"
+#include "lxgrad.h"
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -787,6 +788,33 @@ int pg_kernel_lowrank_grad(pg_handle h, int dtype, const pg_covspec* spec, const
     NEED(size == 0 || work, "this shape needs its workspace (pg_kernel_lowrank_grad_worksize)");
     return pg_lowrank_grad_impl(ST(stream), *spec, hp, (const double*)Xr, ldr, nr, (const double*)Xc, ldc, nc, d, sym, (const double*)U, ldu,
                                 (const double*)V, ldv, r, grad, accumulate, (double*)work);
+}
+
+long pg_kernel_lowrank_xgrad_worksize(int nr, int nc, int d, int r) {
+    return (nr >= 0 && nc >= 0 && d >= 0 && r >= 0) ? pg_lxgrad_worksize_impl(nr, nc, d, r) : -1;
+}
+
+int pg_kernel_lowrank_xgrad(pg_handle h, int dtype, const pg_covspec* spec, const double* hp, const void* Xr, long ldr, int nr, const void* Xc,
+                            long ldc, int nc, int d, const void* U, long ldu, const void* V, long ldv, int r, void* OUT, long ldo,
+                            int accumulate, void* work, void* stream) {
+    JOIN(h, stream);
+    NEED(h && hp, "null pointer");
+    NEED(dtype == PG_F64, "float64 only (dtype must be PG_F64)");
+    if (check_spec(spec, __func__)) return -1;      // (PG_KIND_SQDIST is refused: it is no covariance)
+    for (int c = 0; c < (spec->ncomp & ~PG_SPEC_PRODUCT); ++c) NEED(spec->off[c] >= 0, "negative offset in the covariance spec");
+    const int sym = (Xc == nullptr);
+    if (sym) { Xc = Xr; ldc = ldr; nc = nr; }
+    NEED(nr >= 0 && nc >= 0 && d >= 1 && d <= PG_MAX_DIM, "bad shape (0 <= nr, nc; 1 <= d <= PG_MAX_DIM)");
+    NEED(r >= 0 && r <= 64, "0 <= r <= 64 (split a larger rank and accumulate)");
+    NEED(ldr >= d && ldc >= d && ldo >= d && ldu >= r && ldv >= r, "ldr, ldc, ldo >= d and ldu, ldv >= r");
+    if (nr == 0) return 0;
+    NEED(!sym || V || r == 0, "the symmetric form needs V [nr][r] (V must not be NULL)");
+    NEED(Xr && OUT, "null pointer");
+    const bool empty = nc == 0 || r == 0;
+    NEED(empty || (Xc && U && V), "null pointer");
+    NEED(work || pg_lxgrad_worksize_impl(nr, nc, d, r) == 0, "this shape needs its workspace (pg_kernel_lowrank_xgrad_worksize)");
+    return pg_lxgrad_impl(ST(stream), *spec, hp, (const double*)Xr, ldr, nr, (const double*)Xc, ldc, nc, d, sym, (const double*)U, ldu,
+                          (const double*)V, ldv, r, (double*)OUT, ldo, accumulate, (double*)work);
 }
 
 int pg_randn(pg_handle h, int dtype, long seed, int stream_id, int row0, int rows, int cols, void* Z, long ldz, int rows_pad, int cols_pad,

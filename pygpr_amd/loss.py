@@ -237,6 +237,52 @@ class MLE(_MemoLoss):
         return loss, grad
 
 
+    def grad_x(self, params: ndarray) -> ndarray:
+        """dNLML/dx [n, d], the gradient in the training inputs of a single float64 model (new, not in the reference).
+        With A = k(x, x) + shift I and W = dNLML/dA = 1/2 (A^-1 - alpha alpha^T) symmetric, both arguments of k carry x_i:
+
+            dNLML/dx_ik = sum_j A^-1_ij d1k_ijk - alpha_i sum_j alpha_j d1k_ijk,     d1k_ijk = dk(x_i, x_j)/dx_ik
+
+        -- pg_kernel_xgrad with Xq = Z = x, u = alpha and B = A^-1 in one pass over the pairs (one per pg_covspec of a long Compose,
+        accumulated), then out_b - alpha[:, None] * out_u.  Noise and jitter have no derivative in x; a pair at r = 0, the diagonal
+        included, contributes 0.  One evaluation of its own (build, Cholesky, L^-1, alpha, A^-1 mirrored) in buffers of its own, outside
+        the memo: loss, grad and loss_and_grad keep their code paths, their buffers and their bits."""
+        ops = get_ops()
+        model = self.model
+        if model.dtype != torch.float64 or np.asarray(params).dtype == np.float32:
+            raise TypeError("MLE.grad_x computes in float64 only; the model is %s, params %s" % (model.dtype, np.asarray(params).dtype))
+        d = model.x.shape[-1]
+        spec, nhp = spec_of(model.cov, d)
+        p = np.asarray(params, dtype=np.float64)
+        assert p.shape[-1] == nhp
+        experts = model._device_data()
+        if p.reshape(-1, nhp).shape[0] != 1 or len(experts) != 1:
+            raise NotImplementedError("MLE.grad_x: batched models and batched params are not supported")
+        e = experts[0]
+        n, n_pad = e.n, e.n_pad
+        hp = ops.to_device(torch.from_numpy(p.reshape(nhp).copy()), torch.float64)
+        a, m = ops.empty(n_pad, n_pad, dtype=model.dtype), ops.empty(n_pad, n_pad, dtype=model.dtype)      # K -> L -> A^-1;  L^-1
+        invd = ops.potrf_workspace(n_pad, model.dtype)
+        info = torch.zeros(1, dtype=torch.int32, device=ops.device)
+        u, alpha = ops.empty(n_pad, dtype=model.dtype), ops.empty(n_pad, dtype=model.dtype)
+        vwork = ops.empty((n_pad // 256) * n_pad, dtype=model.dtype)
+        res = [None]
+
+        def enqueue():
+            ops.build_factor(spec, hp, e.x, a, invd, info, m)                  # covariance build + Cholesky + L^-1 in one call
+            ops.trmv(m, e.y, u, 0)
+            ops.trmv(m, u, alpha, 1, vwork)                                    # alpha = L^-T (L^-1 y)
+            ops.lauum(m, a)                                                    # A^-1 (lower) over the factor ...
+            ops.symmetrize(a, n_pad)                                           # ... mirrored: the contraction reads whole rows
+            out_u, out_b = ops.kernel_xgrad(spec, hp, e.x, e.x, u=alpha, b=a[:n])
+            res[0] = (out_b - alpha[:n, None] * out_u).cpu().numpy()           # the one sync + transfer
+
+        for st in _checked(enqueue, lambda: info.tolist()):
+            if st:
+                raise _lin_alg_error(st)
+        return res[0]
+
+
 class LOO(_MemoLoss):
     """Leave-one-out negative log predictive density of the hyper-parameters (Rasmussen & Williams 5.4.2; new, not in the reference):
 

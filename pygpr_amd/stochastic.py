@@ -21,6 +21,13 @@ The probes come from pg_randn at a fixed seed, so the loss is a deterministic fu
 Loss and gradient are separate estimators -- the gradient is not the derivative of the loss estimate -- and the pivots of the
 preconditioner change discretely with the parameters: a line search stalls once the steps are of the size of that noise, near the
 optimum.
+
+The gradient in the training inputs (`grad_x`, `loss_and_grads`) comes from the same weight: both arguments of k carry x_i,
+so dNLML/dx_ik = sum_j (W_ij + W_ji) dk(x_i, x_j)/dx_ik -- one pg_kernel_lowrank_xgrad call in its symmetric form
+(include/pygpr_hip_lxgrad.h) on the same views U, V, after the same solve; noise and jitter have no derivative in x.  `grad_x` is an
+estimator built from the same probes as `grad`: its data-fit part (the factor column of alpha) is exact to the solver's tol, its trace
+part has the probes' variance, and it is not the derivative of the loss estimate either.  The pivots of the preconditioner change
+discretely with x as well, so what holds for a line search in the parameters holds for one in the inputs.
 """
 from typing import Tuple
 
@@ -91,16 +98,23 @@ class Stochastic_MLE(_MemoLoss):
         self.slq_info = None
         self.grad_calls = 0       # gradient kernels launched so far (tests / diagnostics)
         self.solves = 0           # block solves so far
-        self._kept = None         # the solve of the last evaluation: a grad() at the same point only adds the kernel
+        self.xgrad_calls = 0      # training-input gradient kernels launched so far
+        self._kept = None         # the solve of the last evaluation: a grad() or grad_x() at the same point only adds the kernel
+        self._memo_x = None       # (key, grad_x) of the last training-input gradient
+        self.grad_x_value: ndarray = NotImplemented
 
     # ---- the memo: MLE's, with the probes and the seed in the key -------------------------------
-    def _evaluate(self, params: ndarray, want_grad: bool):
+    def _key(self, params: ndarray):
         m = self.model
         if np.asarray(params).dtype == np.float32:
             raise TypeError("Stochastic_MLE computes in float64 only (the solver's tolerance is below single precision); params is float32")
         tms, noise, _ = terms(m.cov, m._x.shape[-1])
-        key = (np.asarray(params, dtype=np.float64).tobytes(), np.shape(params), id(m._x), m._x._version, id(m._y), m._y._version,
-               id(m.cov), (tms, tuple(noise)), self.probes, self.seed, m.rank, m.tol, m.max_iter)
+        return (np.asarray(params, dtype=np.float64).tobytes(), np.shape(params), id(m._x), m._x._version, id(m._y), m._y._version,
+                id(m.cov), (tms, tuple(noise)), self.probes, self.seed, m.rank, m.tol, m.max_iter)
+
+    def _evaluate(self, params: ndarray, want_grad: bool):
+        m = self.model
+        key = self._key(params)
         hit = self._memo if (self.memoize and self._memo is not None and self._memo[0] == key) else None
         if hit is not None and (hit[2] is not None or not want_grad):
             return hit[1].copy(), (hit[2].copy() if hit[2] is not None else None)
@@ -108,6 +122,47 @@ class Stochastic_MLE(_MemoLoss):
         loss, grad = self._evaluate_device(params, want_grad, key if self.memoize else None, reuse)
         self._memo = (key, loss.copy(), grad.copy() if want_grad else None, (m._x, m._y, m.cov))
         return loss, grad
+
+    def _evaluate_x(self, params: ndarray) -> ndarray:
+        """grad_x at params: the memo's, or one kernel launch on the kept solve of the last evaluation at these parameters and data, or
+        -- when there is none -- a solve of its own, which a following loss() or grad() at the same point finds."""
+        m = self.model
+        key = self._key(params)
+        if self.memoize and self._memo_x is not None and self._memo_x[0] == key:
+            return self._memo_x[1].copy()
+        kept = self._kept if (self.memoize and self._factor_key == key and self._kept is not None) else None
+        if kept is None:
+            self._kept = self._factor_key = None       # the buffers of the last evaluation go before the next one allocates
+            kept = self._solve_all(params)
+            if self.memoize:
+                self._kept, self._factor_key = kept, key
+                if self._memo is None or self._memo[0] != key:
+                    self._memo = (key, kept["loss"].copy(), None, (m._x, m._y, m.cov))
+        gx = self._gradient_x(kept)
+        if self.memoize:
+            self._memo_x = (key, gx.copy())
+        return gx
+
+    def grad_x(self, params: ndarray) -> ndarray:
+        """dNLML/dx [n, d], the estimator of the module docstring: after loss(p), grad(p) or loss_and_grad(p) one kernel launch and no
+        solve."""
+        gx = self._evaluate_x(params)
+        self.grad_x_value = gx
+        return gx
+
+    def loss_and_grads(self, params: ndarray) -> Tuple[float, ndarray, ndarray]:
+        """(loss, grad in the hyper-parameters, grad in the training inputs) from one solve and one launch of each gradient kernel."""
+        llhd, jac = self.loss_and_grad(params)
+        return (llhd, jac, self.grad_x(params))
+
+    def weight_factors(self) -> Tuple[ndarray, ndarray]:
+        """Host copies (U, V), each [n, 1 + probes], of the last evaluation's factors of the weight W ~ U V^T = dNLML/dA:
+        U = [-alpha / 2, A^-1 Z / (2 t)], V = [alpha, P^-1 Z].  A diagnostic in the manner of FunctionSamples.data_weights: grad and grad_x
+        can be restated from them."""
+        if self._kept is None:
+            raise RuntimeError("weight_factors: no evaluation is kept (evaluate first, with memoize on)")
+        u, v = self._factors(self._kept)
+        return u.cpu().numpy().copy(), v.cpu().numpy().copy()
 
     # ---- one evaluation -------------------------------------------------------------------------
     def _solve_all(self, params: ndarray):
@@ -155,19 +210,33 @@ class Stochastic_MLE(_MemoLoss):
                              stderr=float(per_probe.std(ddof=1) / np.sqrt(t)) if t > 1 else float("nan"))
         return dict(st=st, hp=hp, nhp=nhp, n=n, xs=xs, z0=rec["z0"], alpha=alpha, loss=np.array(loss), scaled=False)
 
-    def _gradient(self, kept) -> ndarray:
-        """One symmetric pg_kernel_lowrank_grad call with U = [-alpha / 2, S / (2 t)] and V = [alpha, P^-1 Z]: views into the solver's
-        buffers (leading dimension _RHS_PAD)."""
-        ops = get_ops()
-        model = self.model
-        st, n, t, nhp = kept["st"], kept["n"], self.probes, kept["nhp"]
+    def _factors(self, kept):
+        """U = [-alpha / 2, S / (2 t)] and V = [alpha, P^-1 Z]: views into the solver's buffers (leading dimension _RHS_PAD), scaled in
+        place the first time."""
+        n, t = kept["n"], self.probes
         xs, z0 = kept["xs"], kept["z0"]
         if not kept["scaled"]:
             xs[:, 0].mul_(-0.5)
             xs[:, 1: 1 + t].mul_(0.5 / t)
             z0[:n, 0] = kept["alpha"]
             kept["scaled"] = True
-        u, v = xs[:n, : 1 + t], z0[:n, : 1 + t]
+        return xs[:n, : 1 + t], z0[:n, : 1 + t]
+
+    def _gradient_x(self, kept) -> ndarray:
+        """One symmetric pg_kernel_lowrank_xgrad call on the same views: [n, d]."""
+        ops = get_ops()
+        st = kept["st"]
+        u, v = self._factors(kept)
+        out = ops.kernel_lowrank_xgrad(st["full_spec"], st["hpd"], st["x"], None, u, v)
+        self.xgrad_calls += 1
+        return out.cpu().numpy()                                                    # the one sync + transfer
+
+    def _gradient(self, kept) -> ndarray:
+        """One symmetric pg_kernel_lowrank_grad call with U = [-alpha / 2, S / (2 t)] and V = [alpha, P^-1 Z]."""
+        ops = get_ops()
+        model = self.model
+        st, nhp = kept["st"], kept["nhp"]
+        u, v = self._factors(kept)
         grad = ops.zeros(nhp)
         ops.kernel_lowrank_grad(st["full_spec"], st["hpd"], st["x"], None, u, v, grad)
         self.grad_calls += 1
