@@ -147,11 +147,14 @@ def make_spec(parts, d):
     return ms(kinds, offs, noise)
 
 
+FRAMED_BED = Bed      # the bed of run()'s framed half: tests/test_streamed_gpu.py puts tests/streamed.py's StreamBed here
+
+
 def run(ops, case, dtype, gapset, **kw):
     """The case on packed operands, then on framed ones: frame checks, same bits, values."""
     beds = {}
     for gs in (None, gapset):
-        bed = Bed(ops, dtype, gs)
+        bed = (Bed if gs is None else FRAMED_BED)(ops, dtype, gs)
         checks = case(bed, **kw)
         bed.check()
         beds[gs] = (bed, checks)
