@@ -100,7 +100,7 @@ class Stochastic_MLE(_MemoLoss):
         self.solves = 0           # block solves so far
         self.xgrad_calls = 0      # training-input gradient kernels launched so far
         self._kept = None         # the solve of the last evaluation: a grad() or grad_x() at the same point only adds the kernel
-        self._memo_x = None       # (key, grad_x) of the last training-input gradient
+        self._memo_x = None       # (key, grad_x, the keyed x / y / cov) of the last training-input gradient
         self.grad_x_value: ndarray = NotImplemented
 
     # ---- the memo: MLE's, with the probes and the seed in the key -------------------------------
@@ -121,7 +121,13 @@ class Stochastic_MLE(_MemoLoss):
         reuse = hit is not None and want_grad and self._factor_key == key and self._kept is not None
         loss, grad = self._evaluate_device(params, want_grad, key if self.memoize else None, reuse)
         self._memo = (key, loss.copy(), grad.copy() if want_grad else None, (m._x, m._y, m.cov))
+        self._drop_memo_x(key)
         return loss, grad
+
+    def _drop_memo_x(self, key) -> None:
+        """The memo of grad_x belongs to the point _memo holds: it goes as soon as _memo moves on, and with it its hold on the data."""
+        if self._memo_x is not None and self._memo_x[0] != key:
+            self._memo_x = None
 
     def _evaluate_x(self, params: ndarray) -> ndarray:
         """grad_x at params: the memo's, or one kernel launch on the kept solve of the last evaluation at these parameters and data, or
@@ -138,9 +144,13 @@ class Stochastic_MLE(_MemoLoss):
                 self._kept, self._factor_key = kept, key
                 if self._memo is None or self._memo[0] != key:
                     self._memo = (key, kept["loss"].copy(), None, (m._x, m._y, m.cov))
+                    self._drop_memo_x(key)
         gx = self._gradient_x(kept)
         if self.memoize:
-            self._memo_x = (key, gx.copy())
+            # (the key holds id()s: like _memo, this memo keeps the tensors and the covariance they name alive, so that no later x / y /
+            # cov can come to lie at one of their addresses -- with the same version counter -- and be served this gradient; it is
+            # dropped when _memo moves to another point, so it never holds data that _memo has let go)
+            self._memo_x = (key, gx.copy(), (m._x, m._y, m.cov))
         return gx
 
     def grad_x(self, params: ndarray) -> ndarray:

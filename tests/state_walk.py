@@ -138,9 +138,9 @@ class Spies:
     """Counting wrappers around the methods of the ops object.  `trmm_lower_kt` is also counted by the form of its first operand: a list
     of views, one matrix, or a stack."""
 
-    def __init__(self, monkeypatch, ops):
+    def __init__(self, monkeypatch, ops, names=None):
         self.n = collections.Counter()
-        for name in SPIED:
+        for name in (SPIED if names is None else names):
             monkeypatch.setattr(ops, name, self._wrap(name, getattr(ops, name)))
 
     def _wrap(self, name, real):
@@ -159,11 +159,13 @@ class Spies:
 
 
 class Env:
-    """What a tier gives the sequences: the ops object with its spies, monkeypatch, and the bounds."""
+    """What a tier gives the sequences: the ops object with its spies, monkeypatch, and the bounds.  spied: the ops to count (Exact_GP's
+    by default); device: where the walks create their tensors (None: on the host, whatever the ops object is)."""
 
-    def __init__(self, ops, monkeypatch, tol64, tol32, deriv=10):
+    def __init__(self, ops, monkeypatch, tol64, tol32, deriv=10, spied=None, device=None):
         self.ops, self.monkeypatch, self.deriv = ops, monkeypatch, deriv     # deriv: the factor on the bound of a derivative
-        self.spies = Spies(monkeypatch, ops)
+        self.device = device
+        self.spies = Spies(monkeypatch, ops, spied)
         self.tol = {F64: tol64, F32: tol32}
         self.errors = {}
 
@@ -248,7 +250,8 @@ class Walk:
         return T(np.asarray(a, dtype=np.float64)).to(self.dtype).double().numpy()
 
     def t(self, a):
-        return T(np.ascontiguousarray(a)).to(self.dtype).clone()        # (never the shadow's memory)
+        t = T(np.ascontiguousarray(a)).to(self.dtype).clone()           # (never the shadow's memory)
+        return t if self.env.device is None else t.to(self.env.device)
 
     def draw(self, n, experts=1):
         shape = (n, D) if experts == 1 else (experts, n, D)
@@ -399,10 +402,11 @@ class Walk:
         n = self.n
         (x1, y1), (x2, y2) = self.draw(n), self.draw(n)
         npdt = np.float32 if self.dtype == F32 else np.float64
-        self.gp.x = torch.from_numpy(np.array(x1, dtype=npdt))          # (a copy: not the shadow's memory)
-        self.gp.x = torch.from_numpy(np.array(x2, dtype=npdt))
-        self.gp.y = torch.from_numpy(np.array(y1, dtype=npdt))
-        self.gp.y = torch.from_numpy(np.array(y2, dtype=npdt))
+        put = (lambda t: t) if self.env.device is None else (lambda t: t.to(self.env.device))
+        self.gp.x = put(torch.from_numpy(np.array(x1, dtype=npdt)))     # (a copy: not the shadow's memory)
+        self.gp.x = put(torch.from_numpy(np.array(x2, dtype=npdt)))
+        self.gp.y = put(torch.from_numpy(np.array(y1, dtype=npdt)))
+        self.gp.y = put(torch.from_numpy(np.array(y2, dtype=npdt)))
         gc.collect()
         self.sx, self.sy = x2, y2
         self.dirty = True
