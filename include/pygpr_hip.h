@@ -417,7 +417,13 @@ int pg_rowstep_raw(pg_handle h, int dtype, int n, void* A, long lda, int o0, int
  * variant 0: C = a A B^T + b C (128x128 tiles; tri != 0 -> lower tiles only), 2: C = a A B + b C,
  * 3: C = a A^T B + b C.  klo/khi as in csrc/gemm.h.  A K range that follows the tile rows (klo or khi == 1) needs a row tile that is a
  * multiple of the variant's K tile, one that follows the tile columns (== 2) such a column tile: every variant but the 32 x 32 tiling
- * (K tile 64), which refuses klo/khi with -2 and a text before anything is enqueued.  tests/gemm_ref.py states the whole call in NumPy. */
+ * (K tile 64), which refuses klo/khi with -2 and a text before anything is enqueued.  tests/gemm_ref.py states the whole call in NumPy.
+ * Variants 14 / 15 / 16 / 17 (fp64 only; fp32 is refused with -2): the 128 x 128 tile of variants 0 / 2 / 3 / 5 on four waves with a
+ * software-pipelined K loop, always as one plain launch.  Same arguments, same results bit for bit.  The library itself routes long
+ * fp64 launches of variants 2 and 3 to 15 and 16 (csrc/gemm.hip: pg_gemm); klo | 8 asks for the variant's own form (measurement only,
+ * like klo | 4, the reverse walk).  tri | 2: two problems in one launch (batch = 2), tri | 4: two experts (nexp = 2), each array's
+ * blocks stacked one below the other, experts outermost; tri | 8: one int status flag per expert in the 16 bytes in front of C, a
+ * non-zero flag makes that expert's workgroups return at once -- all three for tests only. */
 int pg_gemm_raw(pg_handle h, int dtype, int variant, int M, int N, int K, double alpha, const void* A, long lda,
                 const void* B, long ldb, double beta, void* C, long ldc, int tri, int klo, int khi, void* stream);
 

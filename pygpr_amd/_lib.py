@@ -34,6 +34,8 @@ PAD = 256  # every dimension given to the O(n^3) entry points is a multiple of t
 
 GEMM_NT, GEMM_NT_RP, GEMM_NN, GEMM_TN, GEMM_TT, GEMM_NT_64, GEMM_NT_64x128, GEMM_NT_32x64, GEMM_NT_32x128, GEMM_TT_64, GEMM_NT_32x32 = 0, 1, 2, 3, 5, 6, 7, 8, 9, 10, 11
 GEMM_TN_64 = 13
+# fp64 only: the 128 x 128 tile of GEMM_NT / NN / TN / TT on four waves with a software-pipelined K loop (gemm.h: GEMM_*_128_PL); same bits
+PIPELINED = {GEMM_NT: 14, GEMM_NN: 15, GEMM_TN: 16, GEMM_TT: 17}
 
 
 class CovSpec(C.Structure):

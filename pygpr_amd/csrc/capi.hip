@@ -155,10 +155,26 @@ static int gemm_raw_t(pg_handle h, int variant, int M, int N, int K, double alph
     p.lda = lda; p.ldb = ldb; p.ldc = ldc;
     p.M = M; p.N = N; p.K = K;
     p.alpha = (T)alpha; p.beta = (T)beta;
-    p.tri = tri; p.klo = klo & 3; p.khi = khi; p.krev = (klo >> 2) & 1;   // (klo bit 2: reverse walk, measurement only)
+    p.klo = klo & 3; p.khi = khi; p.krev = (klo >> 2) & 1;   // (klo bit 2: reverse walk, measurement only)
+    p.exact = (klo >> 3) & 1;                                             // (klo bit 3: the variant's own form, no routing -- measurement only)
     p.sA = p.sB = p.sC = 0; p.batch = 1;
     p.nexp = 1; p.eA = p.eB = p.eC = 0; p.einfo = 0;
     p.part = nullptr; p.ldp = 0; p.info = nullptr; p.noxcd = 0;
+    // tri bits 1 - 3 (tests only: the levels of a launch that the call has no arguments for).  2: batch = 2, 4: nexp = 2 -- the problems lie
+    // stacked, each array's next block right below the previous one (experts outermost); 8: the launch has status flags, one int per
+    // expert, at the 16 bytes in front of C.
+    p.tri = tri & 1;
+    if (tri & 14) {
+        const bool ta = variant == GEMM_TN_128 || variant == GEMM_TT_128 || variant == GEMM_TT_64 || variant == GEMM_TN_64 ||
+                        variant == GEMM_TN_128_PL || variant == GEMM_TT_128_PL;
+        const bool tb = !(variant == GEMM_NN_128 || variant == GEMM_TN_128 || variant == GEMM_TN_64 || variant == GEMM_NN_128_PL ||
+                          variant == GEMM_TN_128_PL);
+        p.batch = (tri & 2) ? 2 : 1;
+        p.nexp = (tri & 4) ? 2 : 1;
+        p.sA = (long)(ta ? K : M) * lda; p.sB = (long)(tb ? N : K) * ldb; p.sC = (long)M * ldc;
+        p.eA = p.batch * p.sA; p.eB = p.batch * p.sB; p.eC = p.batch * p.sC;
+        if (tri & 8) { p.info = reinterpret_cast<const int*>(reinterpret_cast<const char*>(C) - 16); p.einfo = 1; }
+    }
     // PG_RAW_STREAM=upd (measurement only): run the product on the handle's CU-masked update stream instead
     static const char* rs = getenv("PG_RAW_STREAM");
     hipStream_t on = ST(stream);
@@ -1267,7 +1283,8 @@ int pg_gemm_raw(pg_handle h, int dtype, int variant, int M, int N, int K, double
     NEED(h && A && B && C, "null pointer");
     NEED(variant == GEMM_NT_128 || variant == GEMM_NT_RP || variant == GEMM_NN_128 || variant == GEMM_TN_128 ||
              variant == GEMM_TT_128 || variant == GEMM_NT_64 || variant == GEMM_NT_64x128 || variant == GEMM_NT_32x64 ||
-             variant == GEMM_NT_32x128 || variant == GEMM_TT_64 || variant == GEMM_NT_32x32 || variant == GEMM_TN_64,
+             variant == GEMM_NT_32x128 || variant == GEMM_TT_64 || variant == GEMM_NT_32x32 || variant == GEMM_TN_64 ||
+             variant == GEMM_NT_128_PL || variant == GEMM_NN_128_PL || variant == GEMM_TN_128_PL || variant == GEMM_TT_128_PL,
          "variant not exposed");
     NEED16(A, lda); NEED16(B, ldb); NEED16(C, ldc);
     AtomicGuard ag(h, C);

@@ -30,6 +30,7 @@ template <typename T> struct GemmP {
     const int* info;  // device flag: kernels exit at once when *info != 0 (failed factorisation)
     int noxcd;        // 1: keep launch order instead of the XCD-chunked tile order (experiments)
     int atomic_c;     // set by pg_gemm (fp64, beta == 1): the epilogue adds into C with no-return atomics instead of load + store
+    int exact;        // 1: launch the variant asked for in its own form; 0: pg_gemm may route it to the pipelined form (gemm.hip: pg_gemm)
 };
 
 enum GemmVariant {
@@ -46,8 +47,14 @@ enum GemmVariant {
     GEMM_TT_64 = 10,    // TT with 64 x 64 tiles: the small levels of the triangular inverse (few, long 128 x 128 tiles otherwise)
     GEMM_NT_128_SS = 12, // the same epilogue on C = A B^T: the cross-covariance stored test-point-major (K-contiguous B operand)
     GEMM_TN_64 = 13,    // TN with 64 x 64 tiles: K** - V^T V for a few thousand test points (136 lower 128 x 128 tiles leave most CUs idle)
-    GEMM_NT_32x32 = 11  // NT with 32 x 32 tiles and a 64-deep K tile: the chain's U product in the chain-bound tail of the Cholesky
+    GEMM_NT_32x32 = 11, // NT with 32 x 32 tiles and a 64-deep K tile: the chain's U product in the chain-bound tail of the Cholesky
                         // (latency per launch, not throughput, is what counts there: 4x the workgroups, half the K iterations)
+    // fp64 only: the 128 x 128 tile of variants 0 / 2 / 3 / 5 on four waves with a software-pipelined K loop (gemm.hip, PlTile).
+    // Same bits as those variants.  Always the plain four-wave launch: no mixed launch, whatever the shape.
+    GEMM_NT_128_PL = 14,
+    GEMM_NN_128_PL = 15,
+    GEMM_TN_128_PL = 16,
+    GEMM_TT_128_PL = 17
 };
 
 template <typename T> int pg_gemm(pg_ctx* ctx, hipStream_t st, int variant, const GemmP<T>& p);

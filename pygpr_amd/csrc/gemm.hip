@@ -27,11 +27,12 @@ template <typename T, int R, bool KCONT, int BKT = BK, int NTH = 256> struct Sta
     vec_t v[NV];
     unsigned boff[NV];   // this lane's BYTE offsets inside a K tile, relative to the tile's origin (loop invariant)
 
-    // Addressing (round 4): a wave-uniform 64-bit origin (scalar registers, advanced by a scalar add per K tile) plus a 32-bit
-    // per-lane byte offset -- the global_load saddr + voffset form.  With a 64-bit pointer per lane and vector (rounds 1-3) the fp64
-    // 128 x 128 block needed 133 VGPRs: one base pointer was spilled and RELOADED from scratch at the top of every K tile, behind
-    // an `s_waitcnt vmcnt(0)` in front of the tile's loads.  (The offsets stay below 2^32 for every leading dimension the library
-    // can meet: 128 rows x ld x 8 bytes, ld < 4 M elements.)
+    // Addressing: a wave-uniform 64-bit origin plus a 32-bit per-lane byte offset.  (The offsets stay below 2^32 for every leading
+    // dimension the library can meet: 128 rows x ld x 8 bytes, ld < 4 M elements.)  What the compiler makes of it differs:
+    //   load():         the offsets are widened to 64 bits outside the K loop and every load gets a per-lane 64-bit pointer
+    //                   (v_lshl_add_u64 from the scalar origin, then global_load_dwordx4 v, v[ptr], off) -- NOT the saddr + voffset form
+    //                   this comment used to claim.  In the eight-wave fp64 NT block that cost one register too many (a spill).
+    //   load_uniform(): buffer loads -- a scalar resource, one 32-bit offset register per operand, scalar offsets between a lane's vectors.
     __device__ __forceinline__ void init(long ld, int tid) {
 #pragma unroll
         for (int q = 0; q < NV; ++q) {
@@ -54,9 +55,26 @@ template <typename T, int R, bool KCONT, int BKT = BK, int NTH = 256> struct Sta
 #pragma unroll
         for (int q = 0; q < NV; ++q) v[q] = *reinterpret_cast<const vec_t*>(b + (size_t)boff[q]);
     }
+    // The same loads as buffer loads: a scalar resource (base = `org`, made wave-uniform with readfirstlane; one scalar add per K tile
+    // moves it), ONE 32-bit per-lane offset, and the distance between a lane's vectors -- a whole number of rows, the same for every
+    // lane -- as the instruction's scalar offset: buffer_load_dwordx4 v, v_off, s[rsrc], s_off offen.  No per-lane 64-bit pointers.
+    __device__ __forceinline__ void load_uniform(const T* __restrict__ org, long ld) {
+        static_assert(KCONT ? NTH % (BKT / VE) == 0 : NTH % (R / VE) == 0, "a lane's vectors must lie whole rows apart");
+        const unsigned long u = reinterpret_cast<unsigned long>(org);
+        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
+        void* b = reinterpret_cast<void*>(((unsigned long)hi << 32) | lo);
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(b, 0, -1, 0x00020000);   // raw buffer, 32-bit data format
+        const unsigned qs = (unsigned)((KCONT ? NTH / (BKT / VE) : NTH / (R / VE)) * ld * (long)sizeof(T));
+#pragma unroll
+        for (int q = 0; q < NV; ++q)
+            v[q] = __builtin_bit_cast(vec_t, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)boff[0], (int)(q * qs), 0));
+    }
     __device__ __forceinline__ void store(T* s, int tid) const {
 #pragma unroll
-        for (int q = 0; q < NV; ++q) {
+        for (int q = 0; q < NV; ++q) store_one(s, tid, q);
+    }
+    __device__ __forceinline__ void store_one(T* s, int tid, int q) const {
+        {
             const int idx = tid + NTH * q;
             if (KCONT) {
                 const int row = idx / (BKT / VE), kv = idx % (BKT / VE);
@@ -166,6 +184,10 @@ template <typename T> __device__ __forceinline__ int gemm_xcd_order(const GemmP<
 template <typename T, bool TA, bool TB, int BM, int BN, int EPI, int BKT, int NW>
 __device__ __forceinline__ void gemm_tile(const GemmP<T>& p, int ti, int tj, char* smem_raw) {
     constexpr int NTH = 64 * NW;
+    // The eight-wave fp64 NT block sits at the 128-register limit of four waves per SIMD.  With per-lane 64-bit pointers it needed one
+    // register more (one spill, reloaded in the K loop); with buffer loads (Stage::load_uniform) it takes 124 and runs 1.5-2.4 % faster
+    // (DESIGN 4.1).  The other eight-wave forms keep their loads: NN and TT measured slower with buffer loads.
+    constexpr bool UL = sizeof(T) == 8 && BM == 128 && BN == 128 && NW == 8 && EPI == 0 && !TA && TB;
     typedef Stage<T, BM, !TA, BKT, NTH> SA;   // A: K-contiguous when not transposed
     typedef Stage<T, BN, TB, BKT, NTH> SB;    // B: K-contiguous when transposed
     typedef typename Mfma<T>::acc_t acc_t;
@@ -217,8 +239,13 @@ __device__ __forceinline__ void gemm_tile(const GemmP<T>& p, int ti, int tj, cha
     const bool rev = p.klo != 0 && p.krev != 0;
     const int kfirst = rev ? kend - BKT : kbeg, kstep = rev ? -BKT : BKT;
     if (nk > 0) {
-        sa.load(SA::origin(A, p.lda, m0, kfirst));
-        sb.load(SB::origin(B, p.ldb, n0, kfirst));
+        if (UL) {
+            sa.load_uniform(SA::origin(A, p.lda, m0, kfirst), p.lda);
+            sb.load_uniform(SB::origin(B, p.ldb, n0, kfirst), p.ldb);
+        } else {
+            sa.load(SA::origin(A, p.lda, m0, kfirst));
+            sb.load(SB::origin(B, p.ldb, n0, kfirst));
+        }
         sa.store(As, tid);
         sb.store(Bs, tid);
     }
@@ -229,8 +256,13 @@ __device__ __forceinline__ void gemm_tile(const GemmP<T>& p, int ti, int tj, cha
         const int cur = kt & 1;
         const int k0 = kfirst + kt * kstep;
         if (kt + 1 < nk) {
-            sa.load(SA::origin(A, p.lda, m0, k0 + kstep));
-            sb.load(SB::origin(B, p.ldb, n0, k0 + kstep));
+            if (UL) {
+                sa.load_uniform(SA::origin(A, p.lda, m0, k0 + kstep), p.lda);
+                sb.load_uniform(SB::origin(B, p.ldb, n0, k0 + kstep), p.ldb);
+            } else {
+                sa.load(SA::origin(A, p.lda, m0, k0 + kstep));
+                sb.load(SB::origin(B, p.ldb, n0, k0 + kstep));
+            }
         }
         if (k0 + BKT > kbw && k0 < kew) {   // wave-uniform
             const T* as = As + cur * SA::LDS_ELEMS;
@@ -326,6 +358,206 @@ __device__ __forceinline__ void gemm_tile(const GemmP<T>& p, int ti, int tj, cha
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Software-pipelined form of the fp64 128 x 128 tile: four waves of 64 x 64 (two per SIMD, a 256-register budget), 16-deep K tile,
+// EPI == 0.  Same LDS images, tile order, K ranges, per-wave skip and epilogue as gemm_tile, and the same order of k for every output
+// element, so the same bits.  What differs is the order of issue inside a K tile.  A K tile is two k-step PAIRS (k-steps 0,1 and 2,3);
+// a pair's fragments are one register set (4 + 4 doubles per k-step):
+//
+//     [barrier of the previous tile]  read set 0 <- pair 0 of this tile's buffer
+//     top       8 global loads of the NEXT tile (scalar base + 32-bit lane offset), 8 .. 16 LDS reads of set 1 <- pair 1
+//     M0.0-M0.2 24 MFMAs on set 0 (only set 0 is waited for: a counted lgkmcnt, set 1 stays in flight)
+//     W         2 ds_write (A, vectors 0-1; counted vmcnt)   M0.3  8 MFMAs
+//     W         2 ds_write (A, vectors 2-3)                  M1.0  8 MFMAs on set 1
+//     W         2 ds_write (B, vectors 0-1)                  M1.1  8 MFMAs
+//     W         2 ds_write (B, vectors 2-3)                  M1.2  8 MFMAs
+//     barrier, read set 0 of the next tile                   M1.3  8 MFMAs (registers only: they cover the read)
+//
+// The ds_writes of tile t + 1 go into the OTHER buffer while tile t is being read.  That is legal with two buffers because the other
+// buffer's last readers were the MFMAs of tile t - 1, and every wave consumed those fragments (the reads had returned) before it
+// reached the barrier that ended tile t - 1, which every wave passed before any wave writes here.  The one barrier per tile then
+// orders these writes before the reads of tile t + 1.  pl_step is one K tile; NEXT: a next tile exists (loads, writes, read-ahead),
+// MMA: this wave's K range holds the tile (a wave that skips still loads, writes and meets the barrier).
+#define PL_FENCE() __builtin_amdgcn_sched_barrier(0)
+template <bool TA, bool TB> struct PlTile {
+    typedef double T;
+    static constexpr int BM = 128, BN = 128, BKT = BK, NTH = 256, MIM = 4, MIN = 4;
+    typedef Stage<T, BM, !TA, BKT, NTH> SA;
+    typedef Stage<T, BN, TB, BKT, NTH> SB;
+    typedef Mfma<T>::acc_t acc_t;
+
+    // fragments of k-step pair `pr` (k-steps 2 pr, 2 pr + 1) of the buffers as / bs
+    static __device__ __forceinline__ void read_pair(T (&a)[2][MIM], T (&b)[2][MIN], const T* as, const T* bs, int ra, int rb, int fk, int pr) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+#pragma unroll
+            for (int i = 0; i < MIM; ++i) a[s][i] = SA::frag(as, ra + i * 16, (2 * pr + s) * 4 + fk);
+#pragma unroll
+            for (int j = 0; j < MIN; ++j) b[s][j] = SB::frag(bs, rb + j * 16, (2 * pr + s) * 4 + fk);
+        }
+    }
+    // eight MFMAs: k-step s of a set, accumulator rows i0, i0 + 1
+    static __device__ __forceinline__ void mma8(acc_t (&acc)[MIM][MIN], const T (&a)[2][MIM], const T (&b)[2][MIN], int s, int i0) {
+#pragma unroll
+        for (int i = i0; i < i0 + 2; ++i)
+#pragma unroll
+            for (int j = 0; j < MIN; ++j) acc[i][j] = Mfma<T>::run(a[s][i], b[s][j], acc[i][j]);
+    }
+    template <bool NEXT, bool MMA>
+    static __device__ __forceinline__ void step(acc_t (&acc)[MIM][MIN], T (&a0)[2][MIM], T (&b0)[2][MIN], SA& sa, SB& sb, const T* as,
+                                                const T* bs, T* asn, T* bsn, const T* ga, const T* gb, long p_lda, long p_ldb, int tid, int ra, int rb, int fk) {
+        T a1[2][MIM], b1[2][MIN];
+        if (NEXT) {
+            sa.load_uniform(ga, p_lda);
+            sb.load_uniform(gb, p_ldb);
+        }
+        PL_FENCE();
+        if (MMA) {
+            read_pair(a1, b1, as, bs, ra, rb, fk, 1);
+            PL_FENCE();
+            mma8(acc, a0, b0, 0, 0);
+            PL_FENCE();
+            mma8(acc, a0, b0, 0, 2);
+            PL_FENCE();
+            mma8(acc, a0, b0, 1, 0);
+            PL_FENCE();
+        }
+        if (NEXT) { sa.store_one(asn, tid, 0); sa.store_one(asn, tid, 1); }
+        PL_FENCE();
+        if (MMA) { mma8(acc, a0, b0, 1, 2); PL_FENCE(); }
+        if (NEXT) { sa.store_one(asn, tid, 2); sa.store_one(asn, tid, 3); }
+        PL_FENCE();
+        if (MMA) { mma8(acc, a1, b1, 0, 0); PL_FENCE(); }
+        if (NEXT) { sb.store_one(bsn, tid, 0); sb.store_one(bsn, tid, 1); }
+        PL_FENCE();
+        if (MMA) { mma8(acc, a1, b1, 0, 2); PL_FENCE(); }
+        if (NEXT) { sb.store_one(bsn, tid, 2); sb.store_one(bsn, tid, 3); }
+        PL_FENCE();
+        if (MMA) { mma8(acc, a1, b1, 1, 0); PL_FENCE(); }
+        // The barrier stands in front of the tile's last eight MFMAs, not behind them: they need registers only, and the next tile's
+        // set 0 is then in flight behind them.  (This wave's reads of the current buffer returned before M1.0, its writes are waited
+        // for here: all the barrier has to order.)
+        if (NEXT) {   // (the last tile ends without a barrier: nothing is written after it)
+            __syncthreads();
+            read_pair(a0, b0, asn, bsn, ra, rb, fk, 0);   // (a wave that skips the next tile reads it all the same: the data is there)
+            PL_FENCE();
+        }
+        if (MMA) { mma8(acc, a1, b1, 1, 2); PL_FENCE(); }
+    }
+
+    static __device__ __forceinline__ void run(const GemmP<T>& p, int ti, int tj, char* smem_raw) {
+        static_assert(SA::NV == 4 && SB::NV == 4, "pl_step places four vectors per operand");
+        const int ze = (int)blockIdx.y / p.batch;
+        T* As = reinterpret_cast<T*>(smem_raw);
+        T* Bs = As + 2 * SA::LDS_ELEMS;
+        const int tid = threadIdx.x, lane = tid & 63;
+        const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: the skip below is a scalar branch, kbw / kew scalar registers
+        const int wm = wave >> 1, wn = wave & 1;
+        const long zb = (int)blockIdx.y % p.batch;
+        const T* __restrict__ A = p.A + zb * p.sA + ze * p.eA;
+        const T* __restrict__ B = p.B + zb * p.sB + ze * p.eB;
+        T* __restrict__ C = p.C + zb * p.sC + ze * p.eC;
+
+        const int m0 = ti * BM, n0 = tj * BN;
+        int kbeg = 0, kend = p.K;
+        int kbw = 0, kew = p.K;   // this wave's own useful K range, as in gemm_tile
+        if (p.klo == 1) { kbeg = m0; kbw = m0 + wm * 64; }
+        if (p.klo == 2) { kbeg = n0; kbw = n0 + wn * 64; }
+        if (p.khi == 1) { kend = min(p.K, m0 + BM); kew = min(p.K, m0 + (wm + 1) * 64); }
+        if (p.khi == 2) { kend = min(p.K, n0 + BN); kew = min(p.K, n0 + (wn + 1) * 64); }
+
+        acc_t acc[MIM][MIN];
+#pragma unroll
+        for (int i = 0; i < MIM; ++i)
+#pragma unroll
+            for (int j = 0; j < MIN; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.0;
+
+        const int fr = lane & 15, fk = lane >> 4;
+        const int ra = wm * 64 + fr, rb = wn * 64 + fr;
+        const int nk = (kend - kbeg) / BKT;
+        const bool rev = p.klo != 0 && p.krev != 0;
+        const int kfirst = rev ? kend - BKT : kbeg, kstep = rev ? -BKT : BKT;
+        if (nk > 0) {   // (nk == 0: an empty range, C = beta C below)
+            SA sa;
+            SB sb;
+            sa.init(p.lda, tid);
+            sb.init(p.ldb, tid);
+            // prologue: tile 0 into buffer 0, set 0 from it
+            const T* ga = SA::origin(A, p.lda, m0, kfirst);
+            const T* gb = SB::origin(B, p.ldb, n0, kfirst);
+            const long p_lda = p.lda, p_ldb = p.ldb;
+            const long da = (long)kstep * (TA ? p.lda : 1), db = (long)kstep * (TB ? 1 : p.ldb);   // one scalar add per K tile
+            sa.load_uniform(ga, p_lda);
+            sb.load_uniform(gb, p_ldb);
+            sa.store(As, tid);
+            sb.store(Bs, tid);
+            __syncthreads();
+            T a0[2][MIM], b0[2][MIN];
+            read_pair(a0, b0, As, Bs, ra, rb, fk, 0);
+            PL_FENCE();
+            // This wave's useful tiles are one run [u0, u1) of the walk (kbw / kew cut a prefix or a suffix off it, whichever way it is
+            // walked), so the walk is three loops of one body each -- skip, multiply, skip -- and no K tile tests anything.
+            const int lo = max(kbw, kbeg), hi = min(kew, kend);
+            int u0 = 0, u1 = 0;
+            if (hi > lo) {
+                u0 = (rev ? kend - hi : lo - kbeg) / BKT;
+                u1 = (rev ? kend - lo : hi - kbeg) / BKT;
+            }
+            // steady state: tiles 0 .. nk - 2, each staging its successor into the other buffer (nk == 1: none; nk == 2: one, buffer
+            // 0 -> 1; the last tile's buffer is (nk - 1) & 1)
+            const int e0 = min(u0, nk - 1), e1 = min(max(u1, e0), nk - 1);
+            int kt = 0;
+#define PL_TILE(MMA_)                                                                                                               \
+    {                                                                                                                               \
+        const int cur = kt & 1;                                                                                                     \
+        ga += da;                                                                                                                   \
+        gb += db;                                                                                                                   \
+        step<true, MMA_>(acc, a0, b0, sa, sb, As + cur * SA::LDS_ELEMS, Bs + cur * SB::LDS_ELEMS, As + (cur ^ 1) * SA::LDS_ELEMS,   \
+                         Bs + (cur ^ 1) * SB::LDS_ELEMS, ga, gb, p_lda, p_ldb, tid, ra, rb, fk);                                    \
+    }
+            for (; kt < e0; ++kt) PL_TILE(false)
+            for (; kt < e1; ++kt) PL_TILE(true)
+            for (; kt < nk - 1; ++kt) PL_TILE(false)
+#undef PL_TILE
+            // epilogue of the pipeline: the last tile, nothing to stage
+            if (u0 < nk && u1 == nk) {
+                const int cur = (nk - 1) & 1;
+                step<false, true>(acc, a0, b0, sa, sb, As + cur * SA::LDS_ELEMS, Bs + cur * SB::LDS_ELEMS, nullptr, nullptr, nullptr, nullptr, 0, 0, tid, ra, rb, fk);
+            }
+        }
+
+        const T alpha = p.alpha, beta = p.beta;
+#pragma unroll
+        for (int i = 0; i < MIM; ++i)
+#pragma unroll
+            for (int j = 0; j < MIN; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = m0 + wm * 64 + i * 16 + Mfma<T>::row(lane, r);
+                    const int col = n0 + wn * 64 + j * 16 + fr;
+                    T* c = C + (long)row * p.ldc + col;
+                    T v = alpha * acc[i][j][r];
+                    if (p.atomic_c) {   // beta == 1: one no-return add per element, as in gemm_tile
+                        unsafeAtomicAdd(c, v);
+                        continue;
+                    }
+                    if (beta != 0.0) v += beta * *c;
+                    *c = v;
+                }
+    }
+};
+
+template <bool TA, bool TB> __global__ __launch_bounds__(256, 2) void pg_gemm_pl_kernel(GemmP<double> p) {
+    const int ze = (int)blockIdx.y / p.batch;
+    if (p.info && p.info[(long)ze * p.einfo] != 0) return;
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    int ti, tj;
+    gemm_decode<double, 128, 128>(p, gemm_xcd_order(p, blockIdx.x, gridDim.x), ti, tj);
+    PlTile<TA, TB>::run(p, ti, tj, smem_raw);
+}
+
 template <typename T, bool TA, bool TB, int BM, int BN, int EPI, int BKT = BK, int NW = 4>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 4) void pg_gemm_kernel(GemmP<T> p) {
     const int ze = (int)blockIdx.y / p.batch;                      // which of the batched problems (experts)
@@ -360,13 +592,20 @@ __global__ __launch_bounds__(512, 4) void pg_gemm_mixed_kernel(GemmP<T> p, int t
     }
 }
 
-template <typename T, bool TA, bool TB, int BM, int BN, int EPI, int BKT = BK, int NW = 4>
+template <typename T, bool TA, bool TB, int BM, int BN, int EPI, int BKT, int NW, bool PL> static auto gemm_kernel_of() {
+    if constexpr (PL) return pg_gemm_pl_kernel<TA, TB>;
+    else return pg_gemm_kernel<T, TA, TB, BM, BN, EPI, BKT, NW>;
+}
+
+// PL: the software-pipelined four-wave kernel (fp64, 128 x 128, EPI == 0) on the same grid, LDS size and checks
+template <typename T, bool TA, bool TB, int BM, int BN, int EPI, int BKT = BK, int NW = 4, bool PL = false>
 static int launch(hipStream_t st, const GemmP<T>& p) {
+    static_assert(!PL || (sizeof(T) == 8 && BM == 128 && BN == 128 && EPI == 0 && BKT == BK && NW == 4), "the pipelined form is one tile");
     typedef Stage<T, BM, !TA, BKT, 64 * NW> SA;
     typedef Stage<T, BN, TB, BKT, 64 * NW> SB;
     const size_t lds = 2 * (SA::LDS_ELEMS + SB::LDS_ELEMS) * sizeof(T);
     static bool attr_done = false;
-    auto kern = pg_gemm_kernel<T, TA, TB, BM, BN, EPI, BKT, NW>;
+    auto kern = gemm_kernel_of<T, TA, TB, BM, BN, EPI, BKT, NW, PL>();
     if (!attr_done) {
         PG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -476,6 +715,17 @@ template <typename T> int pg_gemm(pg_ctx* ctx, hipStream_t st, int variant_in, c
             }
         }
     }
+    // fp64 TN and NN launches of 128 x 128 tiles go to the software-pipelined four-wave form (PlTile) where it measured faster than the
+    // eight-wave form by more than that form's own spread (tools/probe_gemm_pipelined.py): TN at every depth and grid
+    // measured (+4 .. +11 %, longest K range 384 .. 16384, a quarter of a round of workgroup slots upwards), NN without K ranges
+    // (+1 .. +3 %; with khi = 1 the two forms tie).  NT and TT stay: there the pipelined form ties or loses.  Launches on the CU-masked
+    // update stream, beside the coupled chain, keep their form.  Same bits either way.
+    constexpr int PL_MIN_K = 384;   // the shortest range measured
+    if (sizeof(T) == 8 && !p.exact && !w4env && !(ctx && ctx->upd && st == ctx->upd) &&
+        (variant == GEMM_TN_128 || (variant == GEMM_NN_128 && !p.klo && !p.khi))) {
+        const int kmax = p.khi == 1 ? std::min(p.K, p.M) : (p.khi == 2 ? std::min(p.K, p.N) : p.K);
+        if (kmax >= PL_MIN_K) variant = variant == GEMM_TN_128 ? GEMM_TN_128_PL : GEMM_NN_128_PL;
+    }
     switch (variant) {
         case -1: rc = 0; break;
         case GEMM_NT_128: rc = w4 ? launch<T, false, true, 128, 128, 0>(st, p) : launch<T, false, true, 128, 128, 0, BK, 8>(st, p); break;
@@ -494,6 +744,17 @@ template <typename T> int pg_gemm(pg_ctx* ctx, hipStream_t st, int variant_in, c
         case GEMM_TT_64: rc = launch<T, true, true, 64, 64, 0>(st, p); break;
         case GEMM_TN_64: rc = launch<T, true, false, 64, 64, 0>(st, p); break;
         case GEMM_NT_32x32: rc = launch<T, false, true, 32, 32, 0, 64>(st, p); break;
+        case GEMM_NT_128_PL: case GEMM_NN_128_PL: case GEMM_TN_128_PL: case GEMM_TT_128_PL:
+            if constexpr (sizeof(T) == 8) {
+                rc = variant == GEMM_NT_128_PL   ? launch<T, false, true, 128, 128, 0, BK, 4, true>(st, p)
+                     : variant == GEMM_NN_128_PL ? launch<T, false, false, 128, 128, 0, BK, 4, true>(st, p)
+                     : variant == GEMM_TN_128_PL ? launch<T, true, false, 128, 128, 0, BK, 4, true>(st, p)
+                                                 : launch<T, true, true, 128, 128, 0, BK, 4, true>(st, p);
+            } else {
+                pg_set_error("pg_gemm: variant %d (pipelined 128 x 128 tile) is fp64 only", variant);
+                return -2;
+            }
+            break;
         default: pg_set_error("pg_gemm: unknown variant %d", variant); return -2;
     }
     if (rc) return rc;

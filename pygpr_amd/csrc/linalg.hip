@@ -390,7 +390,7 @@ template <typename T> static GemmP<T> gp0() {
     p.tri = p.klo = p.khi = 0; p.krev = 0;
     p.sA = p.sB = p.sC = 0; p.batch = 1;
     p.nexp = 1; p.eA = p.eB = p.eC = 0; p.einfo = 0;
-    p.part = nullptr; p.ldp = 0; p.info = nullptr; p.noxcd = 0;
+    p.part = nullptr; p.ldp = 0; p.info = nullptr; p.noxcd = 0; p.exact = 0;
     return p;
 }
 
