@@ -21,7 +21,8 @@ moves C by far more than J.  fp32: J = sigma_n^2 = 0.09 puts C + J I at the cond
 (tests/test_append_gpu.py); at 1e-7 the fp32 latent covariance is not reliably positive definite (tests/test_sample_gpu.py).
 
 The scripted sequences and the plans of the random walks are here, so that the CPU tier (tests/test_state_walk_cpu.py, on the oracle
-double `WalkOracleOps`) and the GPU tier (tests/test_state_walk_gpu.py, on the library) run the same ones."""
+double `WalkOracleOps`) and the GPU tier (tests/test_state_walk_gpu.py, on the library) run the same ones.  The committee (GRBCM and
+GRBCM_MLE) is walked by tests/state_walk_grbcm.py, on this module's `Env`, `Spies`, `Fit` and double."""
 import collections
 import gc
 import random
