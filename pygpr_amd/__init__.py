@@ -6,7 +6,8 @@ inducing points, and the `Selection` it returns, and `Iterative_GP`, the matrix-
 raises, and `Stochastic_MLE`, the loss that trains it from probe vectors, and `FunctionSamples`, the pathwise function samples
 `Iterative_GP.function_samples` returns, with `spectral_features`, the random Fourier features they are drawn from, and
 `VarianceCache`, the cached variances with certified bounds `Iterative_GP.variance_cache` returns, and `nlml_of_inputs`, the marginal
-likelihood as a torch function of the training inputs)."""
+likelihood as a torch function of the training inputs, and `Vecchia_GP` with its loss `Vecchia_MLE`, the nearest-neighbour model that
+scales linearly in n)."""
 from .gpr import GPR, Exact_GP, PosteriorSampler, randn
 from .covar import Squared_exponential, Matern52, Matern32, Matern12, Rational_quadratic, Periodic, Product, Covar, Compose, White_noise
 from .loss import Loss, MLE, LOO
@@ -16,6 +17,7 @@ from .stochastic import Stochastic_MLE
 from .pathwise import FunctionSamples, spectral_features
 from .varcache import VarianceCache
 from .inputs import nlml_of_inputs
+from .vecchia import Vecchia_GP, Vecchia_MLE
 from .opt import Opt, CG, Nelder_Mead, BFGS_Quad, CG_Quad, hessian
 from .gr_bcm import GRBCM, GRBCM_MLE, log_likelihood_batched
 from .hp_update import get_learn_rate
@@ -27,5 +29,5 @@ __all__ = [
     "CG", "Nelder_Mead", "BFGS_Quad", "CG_Quad", "hessian", "GRBCM", "GRBCM_MLE", "get_learn_rate", "SK_WRAP",
     "UNIFORM", "MATERN1", "cluster_samples", "euclidean_dist", "sample_gp", "log_likelihood_batched", "PosteriorSampler", "randn",
     "Sparse_GP", "VFE", "select_inducing", "Selection", "Iterative_GP", "NotConverged", "Stochastic_MLE", "FunctionSamples", "spectral_features",
-    "VarianceCache", "nlml_of_inputs",
+    "VarianceCache", "nlml_of_inputs", "Vecchia_GP", "Vecchia_MLE",
 ]

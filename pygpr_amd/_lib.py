@@ -1,6 +1,6 @@
 """ctypes binding of libpygpr_hip.so (C ABI: include/pygpr_hip.h, include/pygpr_hip_loo.h, include/pygpr_hip_sample.h,
 include/pygpr_hip_sparse.h, include/pygpr_hip_select.h, include/pygpr_hip_matmul.h, include/pygpr_hip_lowrank.h, include/pygpr_hip_feature.h,
-include/pygpr_hip_dmatmul.h, include/pygpr_hip_rowsq.h, include/pygpr_hip_lxgrad.h).
+include/pygpr_hip_dmatmul.h, include/pygpr_hip_rowsq.h, include/pygpr_hip_lxgrad.h, include/pygpr_hip_vecchia.h).
 
 There is no CPU fallback: `load()` raises if the shared object is missing, and every compute call
 needs a HIP device.  Build the library with `python __graft_entry__.py` (hipcc, gfx950).
@@ -22,6 +22,9 @@ HEADER_FEATURE = os.path.join(os.path.dirname(_HERE), "include", "pygpr_hip_feat
 HEADER_DMATMUL = os.path.join(os.path.dirname(_HERE), "include", "pygpr_hip_dmatmul.h")   # the derivative's matrix-free product (a ninth)
 HEADER_ROWSQ = os.path.join(os.path.dirname(_HERE), "include", "pygpr_hip_rowsq.h")   # the cross-covariance's squared row norms (a tenth)
 HEADER_LXGRAD = os.path.join(os.path.dirname(_HERE), "include", "pygpr_hip_lxgrad.h")   # the low-rank training-input gradient (an eleventh)
+# the nearest-neighbour GP's search and blocks (a twelfth).  Not a HEADER_* name: tests/test_streamed_cpu.py counts those and holds their
+# stream-taking exports to the table of tests/test_streamed_gpu.py; this header's get their cases in tests/test_vecchia_framed_gpu.py
+VECCHIA_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pygpr_hip_vecchia.h")
 
 PG_F64, PG_F32 = 0, 1
 PG_KIND_RBF, PG_KIND_MATERN52, PG_KIND_SQDIST, PG_KIND_MATERN32, PG_KIND_MATERN12 = 0, 1, 2, 3, 4
@@ -52,7 +55,7 @@ class CovSpec(C.Structure):
 # None, an address and byref(...) alike), the covariance spec keeps its struct type.
 _RESTYPES = {"int": C.c_int, "long": C.c_long, "const char*": C.c_char_p}
 _ARGTYPES = {"int": C.c_int, "long": C.c_long, "double": C.c_double, "const pg_covspec*": C.POINTER(CovSpec)}
-_ARGTYPES.update((t, C.c_void_p) for t in ("pg_handle", "pg_handle*", "void*", "const void*", "double*", "const double*", "int*", "long*"))
+_ARGTYPES.update((t, C.c_void_p) for t in ("pg_handle", "pg_handle*", "void*", "const void*", "double*", "const double*", "int*", "const int*", "long*"))
 
 
 def _strip_comments(text):
@@ -104,6 +107,7 @@ _SIGS_FEATURE = signatures(parse_prototypes(open(HEADER_FEATURE).read()))
 _SIGS_DMATMUL = signatures(parse_prototypes(open(HEADER_DMATMUL).read()))
 _SIGS_ROWSQ = signatures(parse_prototypes(open(HEADER_ROWSQ).read()))
 _SIGS_LXGRAD = signatures(parse_prototypes(open(HEADER_LXGRAD).read()))
+_SIGS_VECCHIA = signatures(parse_prototypes(open(VECCHIA_HEADER).read()))
 
 _lib = None
 
@@ -119,13 +123,13 @@ def load(check_symbols=False):
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_LOO.items()) + list(_SIGS_SAMPLE.items()) + list(_SIGS_SPARSE.items())
                                   + list(_SIGS_SELECT.items()) + list(_SIGS_MATMUL.items()) + list(_SIGS_LOWRANK.items()) + list(_SIGS_FEATURE.items())
-                                  + list(_SIGS_DMATMUL.items()) + list(_SIGS_ROWSQ.items()) + list(_SIGS_LXGRAD.items())):
+                                  + list(_SIGS_DMATMUL.items()) + list(_SIGS_ROWSQ.items()) + list(_SIGS_LXGRAD.items()) + list(_SIGS_VECCHIA.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib
     if check_symbols:
         missing = [s for s in header_symbols() + sorted(_SIGS_LOO) + sorted(_SIGS_SAMPLE) + sorted(_SIGS_SPARSE) + sorted(_SIGS_SELECT)
-                   + sorted(_SIGS_MATMUL) + sorted(_SIGS_LOWRANK) + sorted(_SIGS_FEATURE) + sorted(_SIGS_DMATMUL) + sorted(_SIGS_ROWSQ) + sorted(_SIGS_LXGRAD) if not hasattr(_lib, s)]
+                   + sorted(_SIGS_MATMUL) + sorted(_SIGS_LOWRANK) + sorted(_SIGS_FEATURE) + sorted(_SIGS_DMATMUL) + sorted(_SIGS_ROWSQ) + sorted(_SIGS_LXGRAD) + sorted(_SIGS_VECCHIA) if not hasattr(_lib, s)]
         unbound = [s for s in header_symbols() if s not in _SIGS]
         if missing or unbound:
             raise RuntimeError("C ABI mismatch: missing in .so %s, unbound in _lib.py %s" % (missing, unbound))
@@ -148,7 +152,7 @@ def build_id():
 
     csrc = os.path.join(_HERE, "csrc")
     h = hashlib.sha256()
-    for f in sorted(os.listdir(csrc)) + [HEADER, HEADER_LOO, HEADER_SAMPLE, HEADER_SPARSE, HEADER_SELECT, HEADER_MATMUL, HEADER_LOWRANK, HEADER_FEATURE, HEADER_DMATMUL, HEADER_ROWSQ, HEADER_LXGRAD]:
+    for f in sorted(os.listdir(csrc)) + [HEADER, HEADER_LOO, HEADER_SAMPLE, HEADER_SPARSE, HEADER_SELECT, HEADER_MATMUL, HEADER_LOWRANK, HEADER_FEATURE, HEADER_DMATMUL, HEADER_ROWSQ, HEADER_LXGRAD, VECCHIA_HEADER]:
         path = f if os.path.isabs(f) else os.path.join(csrc, f)
         if path.endswith((".hip", ".h")):
             h.update(os.path.basename(path).encode())

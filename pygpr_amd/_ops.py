@@ -494,6 +494,68 @@ class HipOps:
                    int(out.stride(0)) if nr > 1 else 1, _p(work), self._st())
         return out
 
+    # -- the nearest-neighbour GP (include/pygpr_hip_vecchia.h) -------------------------------------
+    @staticmethod
+    def _rows(name, t, shape, dtype=torch.float64):
+        if not (t.is_cuda and t.dim() == 2 and tuple(t.shape) == tuple(shape) and t.dtype == dtype and (t.stride(1) == 1 or t.shape[1] <= 1)):
+            raise ValueError("%s must be %s %s on the device, unit stride along a row" % (name, list(shape), dtype))
+        return max(int(t.stride(0)), int(shape[1]), 1) if t.shape[0] > 1 else max(int(shape[1]), 1)
+
+    def knn(self, xq, xc, m, s=None, causal=False, out=None):
+        """out[i] = the up to m nearest candidates of xc [n, d] for query xq[i] (pg_knn): int32 [q, m], ordered by (scaled squared
+        distance, index), -1 in unfilled slots.  s [d]: per-coordinate scales (None: ones).  causal: candidates of query i are j < i
+        (xq is then xc or its leading rows)."""
+        q, d = xq.shape
+        n = xc.shape[0]
+        ldq, ldc = self._rows("xq", xq, (q, d)), self._rows("xc", xc, (n, d))
+        if out is None:
+            out = self.empty(q, int(m), dtype=torch.int32)
+        ldn = self._rows("out", out, (q, int(m)), torch.int32)
+        if s is not None:
+            self._chk(s)
+            assert s.dtype == torch.float64 and s.numel() == d
+        self._call("pg_knn", PG_F64, _p(xq), ldq, q, _p(xc), ldc, n, d, _p(s), int(m), int(bool(causal)), _p(out), ldn, self._st())
+        return out
+
+    def vecchia_nlml_grad_worksize(self, count, d, nhp):
+        return int(self.lib.pg_vecchia_nlml_grad_worksize(int(count), int(d), int(nhp)))
+
+    def vecchia_nlml_grad(self, spec, hp, x, y, nbr, first, count, jitter, want_grad, cmean, cvar, out, grad, info, work=None):
+        """The conditional terms of targets first .. first + count - 1 (pg_vecchia_nlml_grad): cmean / cvar [count], out [1] the loss
+        summed over them, grad [nhp] its gradient (want_grad), info [1] int32.  nbr [count, m] int32: row t holds the neighbours of
+        point first + t (indices into x, -1 padding).  One pg_covspec only."""
+        (sp,) = _passes(spec)
+        self._chk(hp, y, cmean, cvar, out, grad, info, work)
+        n, d = x.shape
+        m = nbr.shape[1]
+        ldx, ldn = self._rows("x", x, (n, d)), self._rows("nbr", nbr, (int(count), m), torch.int32)
+        nhp = hp.numel()
+        size = self.vecchia_nlml_grad_worksize(count, d, nhp)
+        if work is None:
+            work = self.empty(max(size, 1), dtype=torch.float64)
+        assert work.dtype == torch.float64 and work.numel() >= size and hp.dtype == torch.float64
+        self._call("pg_vecchia_nlml_grad", PG_F64, C.byref(sp), _p(hp), nhp, _p(x), ldx, n, d, _p(y), _p(nbr), ldn, m, int(first), int(count),
+                   float(jitter), int(bool(want_grad)), _p(cmean), _p(cvar), _p(out), _p(grad), _p(info), _p(work), self._st())
+
+    def vecchia_predict_worksize(self, q, d):
+        return int(self.lib.pg_vecchia_predict_worksize(int(q), int(d)))
+
+    def vecchia_predict(self, spec, hp, x, y, xq, nbr, jitter, mean, var, info, work=None):
+        """mean / var [q] of the q points xq, each conditioned on row t of nbr [q, m] (indices into x; pg_vecchia_predict).  var may be
+        None."""
+        (sp,) = _passes(spec)
+        self._chk(hp, y, mean, var, info, work)
+        n, d = x.shape
+        q, m = nbr.shape
+        ldx, ldq = self._rows("x", x, (n, d)), self._rows("xq", xq, (q, d))
+        ldn = self._rows("nbr", nbr, (q, m), torch.int32)
+        size = self.vecchia_predict_worksize(q, d)
+        if work is None:
+            work = self.empty(max(size, 1), dtype=torch.float64)
+        assert work.dtype == torch.float64 and work.numel() >= size and hp.dtype == torch.float64
+        self._call("pg_vecchia_predict", PG_F64, C.byref(sp), _p(hp), _p(x), ldx, n, d, _p(y), _p(xq), ldq, q, _p(nbr), ldn, m, float(jitter),
+                   _p(mean), _p(var), _p(info), _p(work), self._st())
+
     # -- the random-feature product (include/pygpr_hip_feature.h) ----------------------------------
     def feature_matmul_worksize(self, nr, nf, nrhs):
         return int(self.lib.pg_feature_matmul_worksize(int(nr), int(nf), int(nrhs)))

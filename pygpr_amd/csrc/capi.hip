@@ -14,6 +14,7 @@
 #include "fmatmul.h"
 #include "lowrank.h"
 #include "lxgrad.h"
+#include "vecchia.h"
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -1291,6 +1292,75 @@ int pg_gemm_raw(pg_handle h, int dtype, int variant, int M, int N, int K, double
     return dispatch(dtype, __func__, [&](auto t) {
         return gemm_raw_t<decltype(t)>(h, variant, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, tri, klo, khi, stream);
     });
+}
+
+// ---- the nearest-neighbour (Vecchia) GP (include/pygpr_hip_vecchia.h)
+int pg_knn(pg_handle h, int dtype, const void* Xq, long ldq, int q, const void* Xc, long ldc, int n, int d, const double* s, int m, int causal,
+           int* nbr, long ldn, void* stream) {
+    JOIN(h, stream);
+    NEED(dtype == PG_F64, "float64 only (dtype must be PG_F64)");
+    if (!(q >= 0 && n >= 0 && d >= 1 && d <= PG_MAX_DIM && m >= 1 && m <= 63)) {
+        pg_set_error("%s: bad shape (0 <= q, n; 1 <= d <= PG_MAX_DIM; 1 <= m <= 63)", __func__);
+        return -2;
+    }
+    NEED(ldq >= d && ldc >= d && ldn >= m, "ldq, ldc >= d and ldn >= m");
+    NEED(!causal || q <= n, "a causal search takes its queries from the candidates (q <= n)");
+    NEED(h, "null handle");
+    if (q == 0) return 0;
+    NEED(Xq && nbr && (Xc || n == 0), "null pointer");
+    return pg_knn_impl(ST(stream), (const double*)Xq, ldq, q, (const double*)Xc, ldc, n, d, s, m, causal, nbr, ldn);
+}
+
+// what pg_vecchia_nlml_grad and pg_vecchia_predict ask of their common arguments; nhp < 0: the offsets are not held to an extent
+static int check_vecchia(const char* fn, pg_handle h, int dtype, const pg_covspec* spec, const double* hp, int nhp, int n, int d, int m, long ldx,
+                         long ldn) {
+    if (!spec) { pg_set_error("%s: null covariance spec", fn); return -1; }
+    if (dtype != PG_F64) { pg_set_error("%s: float64 only (dtype must be PG_F64)", fn); return -1; }
+    if (check_spec(spec, fn)) return -1;      // (PG_KIND_SQDIST is refused: it is no covariance)
+    if (!(n >= 0 && d >= 1 && d <= PG_MAX_DIM && m >= 1 && m <= 63)) {
+        pg_set_error("%s: bad shape (0 <= n; 1 <= d <= PG_MAX_DIM; 1 <= m <= 63)", fn);
+        return -2;
+    }
+    for (int c = 0; c < (spec->ncomp & ~PG_SPEC_PRODUCT); ++c) {
+        const int w = spec->kind[c] == PG_KIND_PERIODIC ? 2 * d + 1 : (spec->kind[c] == PG_KIND_RQ ? d + 2 : d + 1);
+        if (spec->off[c] < 0 || (nhp >= 0 && spec->off[c] + w > nhp)) { pg_set_error("%s: a component's block lies outside hp", fn); return -1; }
+    }
+    for (int c = 0; c < spec->nnoise; ++c)
+        if (spec->noise_off[c] < 0 || (nhp >= 0 && spec->noise_off[c] >= nhp)) { pg_set_error("%s: a noise entry lies outside hp", fn); return -1; }
+    if (ldx < d || ldn < m) { pg_set_error("%s: ldx >= d and ldn >= m", fn); return -1; }
+    if (!h || !hp) { pg_set_error("%s: null handle or hp", fn); return -1; }      // (last: the refusals above need no device)
+    return 0;
+}
+
+long pg_vecchia_nlml_grad_worksize(int count, int d, int nhp) {
+    return (count >= 0 && d >= 1 && d <= PG_MAX_DIM && nhp >= 0) ? pg_vecchia_worksize_impl(count, d, nhp) : -1;
+}
+
+int pg_vecchia_nlml_grad(pg_handle h, int dtype, const pg_covspec* spec, const double* hp, int nhp, const void* X, long ldx, int n, int d,
+                         const void* Y, const int* nbr, long ldn, int m, int first, int count, double jitter, int want_grad, void* cmean,
+                         void* cvar, double* out, double* grad, int* info, void* work, void* stream) {
+    JOIN(h, stream);
+    NEED(nhp >= 0, "negative nhp");
+    NEED(n < 0 || (first >= 0 && count >= 0 && (long)first + count <= n), "0 <= first, count and first + count <= n");
+    if (int rc = check_vecchia(__func__, h, dtype, spec, hp, nhp, n, d, m, ldx, ldn)) return rc;
+    NEED(out && info && (work || count == 0) && (grad || !want_grad), "null pointer");
+    NEED(count == 0 || (X && Y && nbr && cmean && cvar), "null pointer");
+    return pg_vecchia_nlml_grad_impl(ST(stream), *spec, hp, nhp, (const double*)X, ldx, n, d, (const double*)Y, nbr, ldn, m, first, count, jitter,
+                                     want_grad, (double*)cmean, (double*)cvar, out, grad, info, (double*)work);
+}
+
+long pg_vecchia_predict_worksize(int q, int d) { return (q >= 0 && d >= 1 && d <= PG_MAX_DIM) ? pg_vecchia_worksize_impl(q, d, 0) : -1; }
+
+int pg_vecchia_predict(pg_handle h, int dtype, const pg_covspec* spec, const double* hp, const void* X, long ldx, int n, int d, const void* Y,
+                       const void* Xq, long ldq, int q, const int* nbr, long ldn, int m, double jitter, void* mean, void* var, int* info,
+                       void* work, void* stream) {
+    JOIN(h, stream);
+    NEED(q >= 0 && ldq >= d, "q >= 0 and ldq >= d");
+    if (int rc = check_vecchia(__func__, h, dtype, spec, hp, -1, n, d, m, ldx, ldn)) return rc;
+    NEED(info && (work || q == 0), "null pointer");
+    NEED(q == 0 || (Xq && nbr && mean && (n == 0 || (X && Y))), "null pointer");
+    return pg_vecchia_predict_impl(ST(stream), *spec, hp, (const double*)X, ldx, n, d, (const double*)Y, (const double*)Xq, ldq, q, nbr, ldn, m,
+                                   jitter, (double*)mean, (double*)var, info, (double*)work);
 }
 
 }  // extern "C"
